@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the MultiModalVAE training hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          # N > 1 without WORLD_SIZE in the environment: starts the N ranks itself
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]   # N > 1 without WORLD_SIZE: starts the N ranks itself
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -16,6 +16,10 @@ GEMM launch of the timed steps; the dominant launch (largest share of a step) is
 its algorithmic bytes (operands read once + outputs written once) over its
 mean duration.  `cpu_baseline` times oracle/torch_ref.py (stock PyTorch, fp32) on the host cores
 for a bounded number of steps of the SAME workload (rank 0, N=1 only).
+
+`--dump-outputs DIR`: after the measurement the state is set back to the seeded start (weights, batch, Philox noise, empty
+AdamW state) and the timed path runs one more step; rank 0 writes what that step hands its caller, one .npy file per array.
+Its inputs are the same in every run, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -108,6 +112,23 @@ def cpu_baseline(B, steps):
                        f"same synthetic workload; {dt * 1e3:.0f} ms/step; `points`: the same step at batch 32 (100 steps) and 4096 (10 steps)")
 
 
+def dump_outputs(path, model, losses, grads):
+    """The results of one training step as its caller sees them: `loss` = [total, recon, class, kld] (float32), every
+    state_dict entry after AdamW (parameters and BatchNorm buffers; float32, the int64 batch counters as float64) and
+    `grad.<parameter>` (float32) from `grads`.  About 9 MB for the bench model, whatever the batch.  Returns the bytes written."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {"loss": np.asarray(losses, dtype=np.float32)}
+    for k, v in model.state_dict().items():
+        arrays[k] = v.detach().cpu().numpy().astype(np.float32 if v.is_floating_point() else np.float64)
+    for k, g in grads.items():
+        if g is not None:
+            arrays["grad." + k] = g.detach().float().cpu().numpy()
+    for name, x in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), x)
+    return sum(x.nbytes for x in arrays.values())
+
+
 def spawn_ranks(n):
     """One child process per GPU (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in its environment, the same command line), as
     `python -m torch.distributed.run --nproc-per-node n` would start them; rank 0's stdout (the ONE JSON line) is ours.  Returns the
@@ -161,7 +182,10 @@ def main():
     ap.add_argument("--eager", action="store_true", help="issue every launch from Python instead of replaying the captured hipGraph")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only for rehearsals)")
     ap.add_argument("--single-device", action="store_true", help="rehearsal: put every rank on cuda:0 (needs --backend gloo)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after timing, run one step of the timed path from the seeded start and write its losses, parameters and gradients to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N` without a launcher: start the N ranks ourselves.  This process has not touched the GPU yet
@@ -193,7 +217,7 @@ def main():
         else:
             dist.init_process_group(args.backend)
 
-    from mmvae import ops, parallel
+    from mmvae import engine, ops, parallel
     from mmvae.optim import FusedAdamW
     from src.models import MultiModalVAE
     from src.utils import vae_loss
@@ -208,6 +232,13 @@ def main():
     B = args.batch
     a, b, site = synth_batch(B, rank, dev)
     model.train()
+    # the seeded starting point: weights, BatchNorm buffers, empty AdamW state, Philox offset.  --dump-outputs runs one more step
+    # of the timed path from here after the measurement: the float atomics of the kernels make every step's result differ in
+    # the last bits from run to run, and dozens of training steps amplify that, so the end of the timed run is not reproducible
+    start = (({k: v.clone() for k, v in model.state_dict().items()}, opt.snapshot(), engine.GLOBAL_NOISE.state_dict(dev))
+             if args.dump_outputs else None)
+
+    eager_losses = []                      # (total tensor, recon, class, kld) of the last eager_step
 
     def eager_step():
         ra, rb, rc, mu, lv = model(a=a, b=b, site=site)
@@ -215,6 +246,7 @@ def main():
         opt.zero_grad()
         loss.backward()
         opt.step()
+        eager_losses[:] = [loss, rec, cls, kld]
         return rec
 
     # Step 0, eager and CHECKED: fresh seed-0 weights, Philox offset 0 -> the total loss must be the stored expectation
@@ -247,6 +279,8 @@ def main():
         # explicit way to measure Python-issued launches
         graphed = GraphedTrainStep(model, opt, a, b, site, beta=1e-3, gamma=1.0, warmup=2, reduce=reduce)
         steps_done += 2
+        # the gradient arena the replays write: the eager probe passes below point .grad at tensors of their own
+        graph_grads = {k: p.grad for k, p in model.named_parameters()}
 
     def graph_step():
         # every step's loss floats reach the host, one step behind the launches (GraphedTrainStep.step_logged): the host never
@@ -319,6 +353,25 @@ def main():
         dt = float(t.item())
     if not (last == last):
         raise SystemExit("loss became NaN during the benchmark")
+    dumped = None
+    if start is not None:
+        # written in place: the captured graph keeps its addresses (every rank: the step holds the gradient all-reduce)
+        with torch.no_grad():
+            cur = model.state_dict()
+            for k, v in start[0].items():
+                cur[k].copy_(v)
+        opt.restore(start[1])
+        engine.GLOBAL_NOISE.load_state_dict(start[2], dev)
+        if graphed is not None:
+            graphed()
+            losses, grads = graphed.losses(), graph_grads
+        else:
+            eager_step()
+            losses = [eager_losses[0].detach().item()] + eager_losses[1:]
+            grads = {k: p.grad for k, p in model.named_parameters()}
+        if rank == 0:
+            dumped = dict(dir=args.dump_outputs, step="one step of the timed path from the seeded start",
+                          bytes=dump_outputs(args.dump_outputs, model, losses, grads))
 
     ms = dt / args.steps * 1e3
     value = world * B * args.steps / dt
@@ -340,6 +393,8 @@ def main():
         "step_tflops": FLOPS_PER_SAMPLE * B / (ms * 1e-3) / 1e12,
         "step_mfma_frac": FLOPS_PER_SAMPLE * B / (ms * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS[args.precision],
     }
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     if rank == 0:
         if probe is not None:
             summ = ssum
