@@ -13,6 +13,9 @@
  *   - every call only ENQUEUES work on `stream` (a hipStream_t passed as void*); nothing
  *     synchronises, so calls are graph-capturable.
  *   - return value: 0 = ok; <0 = argument check failed (MMVAE_ERR_*); >0 = hipError_t of the launch.
+ *     A call that returns MMVAE_ERR_ARG or MMVAE_ERR_DTYPE has enqueued NOTHING: the caller may issue another form of the same work
+ *     (a separate finalisation launch, a call without pro_out) and nothing is counted twice.
+ *   - the library reads no environment variables: one build is one configuration (mmvae_set_tuning only serves tests).
  *   - matrices are row-major with an explicit leading dimension in ELEMENTS.
  *   - "activation type" = float in MMVAE_PREC_F32 mode, bfloat16 in MMVAE_PREC_BF16 mode.
  */
@@ -37,7 +40,7 @@ enum { MMVAE_ACT_NONE = 0, MMVAE_ACT_RELU = 1, MMVAE_ACT_SIGMOID = 2 };
 #define MMVAE_TILE 128          /* GEMM output tile edge */
 
 int mmvae_abi_version(void);    /* bumped on any struct change; the ctypes binding checks it */
-/* Tuning knobs (tests / A-B runs): key 0 = minimum M for the 128x256-tile NT kernels (default 32768); key 2 = LDS-DMA generation of the
+/* Tuning knobs (tests compare kernel forms inside one process): key 0 = minimum M for the 128x256-tile NT kernels (default 32768); key 2 = LDS-DMA generation of the
  * NT kernel (gemm_nt2.h) on/off; key 3 = log2 of the operand size in bytes from which row blocks are used (17..32; 0 = default 32):
  * mmvae_gemm_nt / mmvae_gemm_tn address their row operands with 32-bit offsets, so an operand of 4 GiB or more (65 536 x 27 000 fp32
  * at the scaled omics widths) is processed in row blocks of at most half that threshold inside the entry point, and key 3 lowers it so
@@ -110,7 +113,7 @@ typedef struct {
        i.e. the previous layer's post-activation (encoders.py:33-34,37-38) -- is also written here ([M][ld_pro_out] bf16, K columns) so
        that the layer's dW GEMM can read it as a plain operand.  Only the wave-specialised kernel writes it (its producer waves hold the
        values anyway): MMVAE_ERR_ARG when the problem is not one of its (M >= 16384, M % 128 == 0, N % 128 == 0, N <= 256, K % 64 == 0,
-       K <= 512, bf16 C with whole 128-byte rows). */
+       K <= 512, bf16 C with whole 128-byte rows, operands below 4 GiB: the row-block path refuses pro_out before its first block). */
     void* pro_out; int64_t ld_pro_out;
     /* optional, MMVAE_PRO_BN_RELU_DROP: `const mmvae_bn_finalize_args*` (host memory, read during the call).  mmvae_bn_finalize of the
        layer that produced A is folded into this launch: every workgroup forms scale / shift of A's columns from the f64 column sums

@@ -130,6 +130,35 @@ def test_entry_points_reject_bad_block_size():
     assert lib.mmvae_set_tuning(3, 8) == -1 and lib.mmvae_set_tuning(3, 40) == -1 and lib.mmvae_set_tuning(3, 0) == 0
 
 
+def test_row_blocks_refuse_pro_out_before_the_first_block():
+    """pro_out is written by the wave-specialised kernel only, which refuses a block with M % 128 != 0.  The row-block path must refuse
+    pro_out before it enqueues any block: a refusal after the first blocks ran would leave their BatchNorm sums in the accumulators,
+    and the engine's retry without pro_out would add them a second time.  Key 3 = 25 (32 MiB) splits M = 65 600 rows of 512 bytes
+    into blocks of 22 016, 22 016 and 21 568 rows: the wave-specialised kernel would take the first two and refuse the last."""
+    from mmvae import ops
+    M, N, K = 16384 * 4 + 64, 256, 256
+    g = torch.Generator(device=DEV).manual_seed(5)
+    Y = torch.randn(M, K, device=DEV, generator=g).bfloat16()
+    scale = torch.rand(K, device=DEV, generator=g) + 0.5
+    shift = torch.randn(K, device=DEV, generator=g) * 0.3
+    mask = (torch.rand(M, K, device=DEV, generator=g) > 0.1).to(torch.uint8)
+    pl = ops.PreparedLinear([torch.randn(N, K, device=DEV, generator=g) / K ** 0.5], [torch.zeros(N, device=DEV)], ops.PREC_BF16, DEV)
+    ops.WeightPrep([pl], DEV).run()
+    out = torch.full((M, N), 3.0, dtype=torch.bfloat16, device=DEV)
+    H = torch.full((M, K), 7.0, dtype=torch.bfloat16, device=DEV)
+    stats = torch.zeros(2, N, dtype=torch.float64, device=DEV)
+    lib = _lib.load()
+    assert lib.mmvae_set_tuning(3, 25) == 0
+    try:
+        with pytest.raises(_lib.MMVAEArgError, match="invalid argument"):
+            ops.gemm_nt(ops.PREC_BF16, Y, pl.w, N, K, out, bias=pl.bias, prologue=(scale, shift, mask, 1.0 / 0.9), stats=stats, pro_out=H)
+        torch.cuda.synchronize()
+    finally:
+        lib.mmvae_set_tuning(3, 0)
+    assert torch.count_nonzero(stats).item() == 0
+    assert bool((out == 3.0).all()) and bool((H == 7.0).all())
+
+
 @pytest.mark.parametrize("prec,L", [("bf16", 128), ("fp32", 128), ("bf16", 20)])
 def test_scaled_widths_at_batch_65536(prec, L):
     """BASELINE.json configs[4] on one GPU at the bench batch -- RNA = 20 000, DNA = 27 000, latent = 128, B = 65 536 (and latent 20,

@@ -44,6 +44,18 @@ def test_argument_checks_reject_before_launch():
     assert lib.mmvae_vae_loss(C.byref(la), None) == -1
 
 
+def test_check_separates_argument_refusals_from_hip_errors():
+    """The engine falls back to another form of a call only on MMVAEArgError (the library enqueued nothing); HIP errors propagate."""
+    _lib.check(0, "ok")
+    with pytest.raises(_lib.MMVAEArgError, match="invalid argument"):
+        _lib.check(-1, "mmvae_gemm_nt")
+    with pytest.raises(_lib.MMVAEArgError, match="dtype not supported"):
+        _lib.check(-2, "mmvae_gemm_nt")
+    with pytest.raises(RuntimeError, match="hipError 700") as e:
+        _lib.check(700, "mmvae_gemm_nt")
+    assert not isinstance(e.value, _lib.MMVAEArgError)
+
+
 def test_ctypes_structs_match_c_layout(tmp_path):
     """sizeof/offsetof of every args struct as gcc lays the header out == the ctypes mirror."""
     import ctypes as C

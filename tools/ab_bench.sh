@@ -1,5 +1,6 @@
 #!/bin/bash
-# A/B of two environments on ONE box, interleaved rounds:  tools/ab_bench.sh "ENV_A=.." "ENV_B=.." [rounds]   ("-" = no variable)
+# A/B of two library builds on ONE box, interleaved rounds: each side is an MMVAE_LIB_PATH setting, e.g. the product library against a
+# `make VARIANT=name` build:  tools/ab_bench.sh "-" "MMVAE_LIB_PATH=vae-los-angeles_amd/mmvae/libmmvae_name.so" [rounds]   ("-" = product library)
 # prints ms/step of every run (bench.py --no-probe --cpu-steps 0 --steps 30 --warmup 10)
 A="$1"; B="$2"; R=${3:-3}
 for i in $(seq $R); do

@@ -1,5 +1,6 @@
 #!/bin/bash
-# kernel-time A/B under rocprofv3 on ONE box:  tools/ab_prof.sh "ENV_A" "ENV_B" 'regex of kernel names'   ("-" = no variable)
+# kernel-time A/B of two library builds under rocprofv3 on ONE box: each side is an MMVAE_LIB_PATH setting (see tools/ab_bench.sh)
+#   tools/ab_prof.sh "-" "MMVAE_LIB_PATH=vae-los-angeles_amd/mmvae/libmmvae_name.so" 'regex of kernel names'   ("-" = product library)
 # prints name, calls, average ns of the matching rows of each run's kernel_stats.csv
 A="$1"; B="$2"; RE="${3:-.}"
 i=0

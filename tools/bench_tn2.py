@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""A/B of the hot TN (dW) shapes with plain bf16 operands; run under different MMVAE_* settings."""
+"""A/B of the hot TN (dW) shapes with plain bf16 operands; run under different MMVAE_LIB_PATH builds."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "tools"), os.path.join(ROOT, "vae-los-angeles_amd")]

@@ -910,18 +910,14 @@ static int launch_loss(const mmvae_loss_args* a, hipStream_t st) {
     // vectors of the stream parts + the per-row class term + the latent elements: without the reconstruction parts (their loss runs
     // inside the decoder GEMMs) the class / KL terms alone must still fill the chip (a row per thread, not four rows on 64 workgroups)
     const long work = (long)a->B * ((a->recon_a ? a->A / va : 0) + (a->recon_b ? a->D / vd : 0) + (a->logits ? 4 * a->S : 0) + (a->mu ? a->L : 0) + 1);
-    static const int wg_cap = getenv("MMVAE_LOSS_WG") ? atoi(getenv("MMVAE_LOSS_WG")) * 256 : 1024;
-    int grid = mm::grid_for(work, 256 * 4, wg_cap);
-    // class / KL terms alone (reconstruction terms inside the decoder GEMMs): every workgroup ends in f64 atomics on the same few
-    // addresses; with the row and element loops unrolled 512 workgroups are enough to cover the latency and halve that tail
-    if (!a->recon_a && !a->recon_b && grid > 512) grid = 512;
+    int grid = mm::grid_for(work, 256 * 4, 1024);
 #define MM_LOSS(VA, VD) hipLaunchKernelGGL((vae_loss_kernel<GT, VA, VD>), dim3(grid), dim3(256), 0, st, *a, ce_vec ? 1 : 0)
-    static const int tail_env = getenv("MMVAE_LOSS_TAIL") ? atoi(getenv("MMVAE_LOSS_TAIL")) : 2;          // A/B switch: 0 general form, 1 without ce_vec
-    const bool ce_vec = tail_env == 2 && a->logits && a->S <= 32 && a->S % 4 == 0 && a->ld_logits % 4 == 0 && ((uintptr_t)a->logits & 15) == 0 &&
+    const bool ce_vec = a->logits && a->S <= 32 && a->S % 4 == 0 && a->ld_logits % 4 == 0 && ((uintptr_t)a->logits & 15) == 0 &&
                         (!a->g_c || (a->ld_gc % 4 == 0 && ((uintptr_t)a->g_c & 15) == 0));
-    if (tail_env && !a->recon_a && !a->recon_b) {
-        // every workgroup ends in f64 atomics on the same addresses (~13 ns each, one after the other): a row per thread, no more
-        if (ce_vec) grid = (int)std::min<long>(512, (a->B + 255) / 256);
+    if (!a->recon_a && !a->recon_b) {
+        // class / KL terms alone (reconstruction terms inside the decoder GEMMs): every workgroup ends in f64 atomics on the same few
+        // addresses (~13 ns each, one after the other): a row per thread, at most 512 workgroups
+        grid = ce_vec ? (int)std::min<long>(512, (a->B + 255) / 256) : std::min(grid, 512);
         hipLaunchKernelGGL((vae_loss_kernel<GT, 1, 1, true>), dim3(grid), dim3(256), 0, st, *a, ce_vec ? 1 : 0);
     } else
     if (va == 4 && vd == 4) MM_LOSS(4, 4); else if (va == 4 && vd == 2) MM_LOSS(4, 2); else if (va == 4) MM_LOSS(4, 1);

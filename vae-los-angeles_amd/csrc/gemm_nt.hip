@@ -288,9 +288,9 @@ static int launch_nt_wn(const Src& src, const void* W, long ldw, int M, int N, i
 }
 
 static int g_wide_min_m = 256 * 128;      // 128x256 tiles only when there are >= 256 row tiles (mmvae_set_tuning key 0)
-// kernel-generation switch (mmvae_set_tuning key 2; initial value from MMVAE_NO_NT2): tests flip it inside one process to compare
-// the register-staged and the LDS-DMA generation on the same data
-static int g_nt2_on = getenv("MMVAE_NO_NT2") ? 0 : 1;
+// kernel-generation switch (mmvae_set_tuning key 2): tests flip it inside one process to compare the register-staged and the
+// LDS-DMA generation on the same data
+static int g_nt2_on = 1;
 void tn_wide_enable(int on);             // gemm_tn_wide.hip (mmvae_set_tuning key 4)
 int ntp_dispatch(const mmvae_gemm_nt_args* a, hipStream_t st);      // gemm_ntp.hip: the wave-specialised kernel; 1 << 30 = not taken
 void ntp_set(int key, int value);        // mmvae_set_tuning keys 8 (on / off), 9 (minimum M)
@@ -298,14 +298,13 @@ long g_block_bytes = 1L << 31;          // row-block size for operands of >= 4 G
 long g_split_bytes = 1L << 32;          // operands of at least this many bytes are processed in row blocks
 
 static inline bool nt_wide_ok(int M, int N) {
-    static const bool off = getenv("MMVAE_NO_WIDE_TILES") != nullptr;      // A/B switch
     // the prepared W has ceil128(N) rows: whole 256-column tiles only; one 8-wave workgroup per CU: at least 256 tiles (M >= 32768 at
     // N = 256; a 16 384-row block of a 512-wide layer qualifies too)
-    return !off && N % 256 == 0 && ((long)M * (N / 256) >= (long)g_wide_min_m || M >= g_wide_min_m);
+    return N % 256 == 0 && ((long)M * (N / 256) >= (long)g_wide_min_m || M >= g_wide_min_m);
 }
 
-static int g_bnbwd_stream = getenv("MMVAE_NO_BNBWD_STREAM") ? 0 : 1;          // mmvae_set_tuning key 6
-static int g_relu_stream = getenv("MMVAE_NO_RELU_STREAM") ? 0 : 1;            // mmvae_set_tuning key 7
+static int g_bnbwd_stream = 1;          // mmvae_set_tuning key 6
+static int g_relu_stream = 1;           // mmvae_set_tuning key 7
 template <typename T> struct IsPlainBf16 { static constexpr bool value = false; };
 template <> struct IsPlainBf16<SrcPlain<bf16, bf16, 8>> { static constexpr bool value = true; };
 
@@ -313,13 +312,11 @@ template <typename CT, typename Src, typename Epi>
 static int launch_nt(const Src& src, const void* W, long ldw, int M, int N, int K, const Epi& epi, hipStream_t st) {
     if constexpr (sizeof(CT) == 2 && IsPlainBf16<Src>::value) {
         // second-generation kernel (gemm_nt2.h): operands that go into the MFMA as they are, at least two K steps
-        const bool off = !g_nt2_on;
         // ... and for epilogues without operands of their own: with a saved activation / keep mask to fetch, the epilogue's loads
         // queue behind the next tile's DMA and its stores in front of the next wait (one in-order vmcnt for everything): measured
-        // 5-20 % SLOWER than the first generation there, 5-10 % faster on the plain store epilogues (tools/bench_nt2.py)
-        if (!off && K > 64 && !epi.accumulate_requested() && Epi::NEED == 0) {
-            static const bool narrow = getenv("MMVAE_NT2_NARROW") != nullptr;      // A/B switch: 128x128 tiles only
-            if (!narrow && nt_wide_ok(M, N)) return launch_nt2<Epi, 4>(src.p, src.lda, W, ldw, M, N, K, epi, st);
+        // 5-20 % SLOWER than the first generation there, 5-10 % faster on the plain store epilogues
+        if (g_nt2_on && K > 64 && !epi.accumulate_requested() && Epi::NEED == 0) {
+            if (nt_wide_ok(M, N)) return launch_nt2<Epi, 4>(src.p, src.lda, W, ldw, M, N, K, epi, st);
             return launch_nt2<Epi, 2>(src.p, src.lda, W, ldw, M, N, K, epi, st);
         }
     }
@@ -494,7 +491,9 @@ extern "C" int mmvae_gemm_nt(const mmvae_gemm_nt_args* a, void* stream) {
     long row_bytes = a_row > (long)a->ld_pro_mask ? a_row : (long)a->ld_pro_mask;
     if (!mm::bn_fin_ok(a)) return MMVAE_ERR_ARG;
     if ((long)a->M * row_bytes >= mm::g_split_bytes) {
-        if (a->pro_finalize) return MMVAE_ERR_ARG;           // every row block would update the running statistics
+        // refused here, before any block is enqueued (mmvae_hip.h): pro_finalize -- every row block would update the running
+        // statistics; pro_out -- a block the wave-specialised kernel does not take would refuse it after the earlier blocks ran
+        if (a->pro_finalize || a->pro_out) return MMVAE_ERR_ARG;
         long rows = mm::g_block_bytes / row_bytes;          // block < split threshold: the recursion below ends after one level
         if (rows <= 0) return MMVAE_ERR_ARG;
         const long nblk = (a->M + rows - 1) / rows;         // equal blocks (65 536 rows -> 4 x 16 384, not 3 x 19 712 + 6 400: a short
@@ -512,7 +511,6 @@ extern "C" int mmvae_gemm_nt(const mmvae_gemm_nt_args* a, void* stream) {
             const long hsz = (a->prec == MMVAE_PREC_BF16 && !loss_epi) ? 2 : 4;
             if (a->h) s.h = (const char*)a->h + r0 * a->ldh * hsz;
             if (a->pro_mask) s.pro_mask = a->pro_mask + r0 * a->ld_pro_mask;
-            if (a->pro_out) s.pro_out = (char*)a->pro_out + r0 * a->ld_pro_out * 2;
             if (a->epi_mask) s.epi_mask = a->epi_mask + r0 * a->ld_epi_mask;
             const int rc = mmvae_gemm_nt(&s, stream);
             if (rc) return rc;

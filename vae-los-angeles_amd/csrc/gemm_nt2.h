@@ -413,9 +413,7 @@ static int launch_nt2(const void* A, long lda, const void* W, long ldw, int M, i
     }
     const int gx = (M + TILE - 1) / TILE, gy = (N + 64 * WN - 1) / (64 * WN);
     const int ntiles = ((gx + 7) / 8) * 8 * gy;
-    static const int wg_env = getenv("MMVAE_NT2_WGS") ? atoi(getenv("MMVAE_NT2_WGS")) : 0;      // A/B knob: workgroups per CU
-    const int per_cu = wg_env > 0 ? wg_env : (WN == 2 ? 2 : 1);
-    int grid = 256 * per_cu;
+    int grid = 256 * (WN == 2 ? 2 : 1);
     if (grid > ntiles) grid = ntiles;
     hipLaunchKernelGGL((gemm_nt2_kernel<Epi, WN>), dim3(grid), dim3(128 * WN), LD::TOTAL, st,
                        (const bf16*)A, lda, (const bf16*)W, ldw, M, N, K, gx, gy, epi);

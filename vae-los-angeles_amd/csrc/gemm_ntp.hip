@@ -6,7 +6,7 @@
 namespace mm {
 
 BnFin bn_fin_of(const mmvae_gemm_nt_args* a);               // gemm_nt.hip
-static int g_ntp_on = getenv("MMVAE_NO_NTP") ? 0 : 1;        // mmvae_set_tuning key 8 (tests flip it to compare with the tile kernels)
+static int g_ntp_on = 1;                                      // mmvae_set_tuning key 8 (tests flip it to compare with the tile kernels)
 static int g_ntp_min_m = 16384;                               // key 9: below this a persistent 256-workgroup grid has < 1 tile per CU
 void ntp_set(int key, int value) { if (key == 8) g_ntp_on = value; else g_ntp_min_m = value; }
 
@@ -52,9 +52,8 @@ int ntp_dispatch(const mmvae_gemm_nt_args* a, hipStream_t st) {
     if (!g_ntp_on || a->prec != MMVAE_PREC_BF16 || a->epilogue != MMVAE_EPI_STORE || a->accumulate) return NTP_SKIP;
     if (a->K <= 64 || a->M < g_ntp_min_m || a->M % 8) return NTP_SKIP;      // M % 8: see the A producers' row groups
     if (a->prologue == MMVAE_PRO_BN_RELU_DROP) {
-        static const bool off = getenv("MMVAE_NO_NTP_PRO") != nullptr;      // A/B switch
         if (a->pro_out && (a->ld_pro_out % 8 || ((uintptr_t)a->pro_out & 15) || a->ld_pro_out < a->K)) return NTP_SKIP;
-        if (off || a->a_dtype != MMVAE_BF16 || a->K % 64 || a->K > 512 || a->lda % 8 || ((uintptr_t)a->a & 15) || (!a->pro_finalize && (!a->pro_scale || !a->pro_shift))) return NTP_SKIP;
+        if (a->a_dtype != MMVAE_BF16 || a->K % 64 || a->K > 512 || a->lda % 8 || ((uintptr_t)a->a & 15) || (!a->pro_finalize && (!a->pro_scale || !a->pro_shift))) return NTP_SKIP;
         if (a->pro_mask) {
             if (a->ld_pro_mask % 8 || ((uintptr_t)a->pro_mask & 7)) return NTP_SKIP;      // 8 keep bytes per lane and load
             return ntp_pro(a, NtpProBn<true>{a->pro_scale, a->pro_shift, a->pro_mask, a->ld_pro_mask, a->pro_inv_keep, (bf16*)a->pro_out, a->ld_pro_out, bn_fin_of(a)}, st);
@@ -67,8 +66,7 @@ int ntp_dispatch(const mmvae_gemm_nt_args* a, hipStream_t st) {
         return ntp_epi<float>(a, st);
     }
     // plain bf16 A (the decoders' hidden Linear + ReLU, decoders.py:29-30): the producers copy 16-byte chunks; 35 -> 31 us at 256 -> 512
-    static const bool no_bf16 = getenv("MMVAE_NO_NTP_BF16") != nullptr;      // A/B switch
-    if (!no_bf16 && a->a_dtype == MMVAE_BF16 && a->lda % 8 == 0 && ((uintptr_t)a->a & 15) == 0) return ntp_epi<bf16>(a, st);
+    if (a->a_dtype == MMVAE_BF16 && a->lda % 8 == 0 && ((uintptr_t)a->a & 15) == 0) return ntp_epi<bf16>(a, st);
     return NTP_SKIP;
 }
 

@@ -417,10 +417,7 @@ void gemm_tn_kernel(PSrc ps, QSrc qs, float* __restrict__ dW, long ldw, float* _
 template <typename T> struct TnPlainBf16 { static constexpr bool value = false; };
 template <> struct TnPlainBf16<SrcPlain<bf16, bf16, 8>> { static constexpr bool value = true; };
 // DMA form: plain bf16 operands and every split a whole number of full batch steps
-static inline bool tn_dma_ok(int M, int MT) {
-    static const bool off = getenv("MMVAE_NO_TN_DMA") != nullptr;           // A/B switch
-    return !off && M % MT == 0;
-}
+static inline bool tn_dma_ok(int M, int MT) { return M % MT == 0; }
 
 // ------------------------------------------------------------------------------------------
 // Grouped launch: several SMALL-output dW GEMMs (latent / class widths: the heads of the encoders, the first layers of the
@@ -583,11 +580,10 @@ static int launch_tn(const mmvae_gemm_tn_args* a, const PSrc& ps, const QSrc& qs
         // multiples of 8 splits (XCD balance) on >= 7/8 of the CUs -- 8 or 7 tiles (512x256, 256x512, 782x128: 36-38 against 40-41 us
         // with the reduce).  The 20 tiles of 572x512 would make 160 workgroups, or 240 with 12 splits of which the last four are
         // shared by two XCDs each (tried: 69 against 64-65 us alone, the same inside the step).
-        static const int ng_env = getenv("MMVAE_TN_NG") ? atoi(getenv("MMVAE_TN_NG")) : 0;      // A/B switch: 1 / 2 = never / always
         bool two = false;
-        if (tn_dma_ok(a->M, G::MT) && ng_env != 1) {
+        if (tn_dma_ok(a->M, G::MT)) {
             tn_split(a->M, a->N, a->K, G::MT, a->nsplit, ntk, ntiles, nsplit, rps, 256);
-            two = ng_env == 2 || (a->nsplit <= 0 && nsplit % 8 == 0 && nsplit * ntiles >= 224);
+            two = a->nsplit <= 0 && nsplit % 8 == 0 && nsplit * ntiles >= 224;
             if (!two) tn_split(a->M, a->N, a->K, G::MT, a->nsplit, ntk, ntiles, nsplit, rps);
         }
         if (two) {

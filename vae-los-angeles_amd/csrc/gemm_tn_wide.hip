@@ -549,7 +549,7 @@ static int tnw_launch(TnwArgs& w, hipStream_t st) {
     return 0;
 }
 
-static int g_tn_wide_on = getenv("MMVAE_NO_TN_WIDE") ? 0 : 1;
+static int g_tn_wide_on = 1;
 void tn_wide_enable(int on) { g_tn_wide_on = on; }
 
 // Returns 0 after launching the GEMM (the caller then runs the slab reduce over *nsplit_out splits), > 0 on a launch error,

@@ -147,6 +147,10 @@ class MMVAELibraryError(RuntimeError):
     pass
 
 
+class MMVAEArgError(RuntimeError):
+    """The library refused the arguments (MMVAE_ERR_ARG / MMVAE_ERR_DTYPE) and enqueued nothing (mmvae_hip.h)."""
+
+
 def load():
     """Load libmmvae_hip.so once; raise loudly if it is absent or stale."""
     global _lib
@@ -170,6 +174,8 @@ def load():
 
 
 def check(status, what):
+    if status in (-1, -2):
+        kind = "invalid argument" if status == -1 else "dtype not supported for this precision"
+        raise MMVAEArgError(f"{what} failed: {kind}")
     if status != 0:
-        kind = {-1: "invalid argument", -2: "dtype not supported for this precision"}.get(status, f"hipError {status}")
-        raise RuntimeError(f"{what} failed: {kind}")
+        raise RuntimeError(f"{what} failed: hipError {status}")

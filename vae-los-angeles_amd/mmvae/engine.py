@@ -20,9 +20,6 @@ from .ops import (PREC_BF16, PREC_F32, ACT_NONE, ACT_RELU, ACT_SIGMOID, EPI_RELU
 
 _PRECISIONS = {"bf16": PREC_BF16, "fp32": PREC_F32, "f32": PREC_F32}
 _default_precision = _PRECISIONS[os.environ.get("MMVAE_PRECISION", "bf16").lower()]
-_FUSE_BN_APPLY = os.environ.get("MMVAE_FUSE_BN_APPLY", "1") == "1"       # A/B switch: BN-backward correction of first layers inside the dW GEMM
-_GROUP_TINY_DW = os.environ.get("MMVAE_GROUP_TINY_DW", "1") == "1"       # A/B switch: small-output dW GEMMs as grouped launches
-_FOLD_BN_FINALIZE = os.environ.get("MMVAE_NO_FOLD_BN_FINALIZE") is None      # A/B switch: mmvae_bn_finalize / mmvae_bn_bwd_finalize inside their consumers
 _TINY_DW_MAX = 16384                                                       # N*K at or below which a dW GEMM counts as small-output
 
 
@@ -137,9 +134,6 @@ def zeros_pack(device, specs):
 _ITEMSIZE = {torch.float32: 4, torch.float64: 8, torch.uint8: 1, torch.int64: 8}
 
 
-_MERGE_DECODER_STEM = os.environ.get("MMVAE_NO_DECODER_STEM") is None          # A/B switch
-
-
 class BNState:
     """Per-layer BatchNorm vectors: rows of one [4][N] fp32 buffer (mean, rstd, scale, shift)."""
 
@@ -191,12 +185,12 @@ class EncoderMLP:
         def consume(N, K, out, bias, w, tag, stats=None, pro_out=None):
             """GEMM on (h, pro) that also finalises h's BatchNorm statistics when the library can fold that in; else the launch of its own."""
             nonlocal fin
-            if fin is not None and _FOLD_BN_FINALIZE:
+            if fin is not None:
                 try:
                     ops.gemm_nt(prec, h, w, N, K, out, bias=bias, prologue=pro, stats=stats, tag=tag, pro_out=pro_out, pro_finalize=fin)
                     fin = None
                     return pro_out
-                except RuntimeError:
+                except L_.MMVAEArgError:
                     pass                                   # refused before anything was enqueued (argument check)
             if fin is not None:
                 ops.bn_finalize(0, 0, None, None, None, None, None, None, None, None, None, None, args=fin)
@@ -204,7 +198,7 @@ class EncoderMLP:
             try:
                 ops.gemm_nt(prec, h, w, N, K, out, bias=bias, prologue=pro, stats=stats, tag=tag, pro_out=pro_out)
                 return pro_out
-            except RuntimeError:
+            except L_.MMVAEArgError:
                 if pro_out is None:
                     raise
                 # the library did not take the problem on the kernel that writes pro_out: the ordinary call, and the backward redoes
@@ -274,27 +268,22 @@ class EncoderMLP:
             fin = (stats, bn.weight, grads[bn.weight], grads[bn.bias], not train)
             # (not for very wide inputs -- the scaled omics widths: the dW GEMM then has hundreds of K tiles and every one of them
             # would redo the correction of its P rows; one pass over d is cheaper)
-            if i == 0 and _FUSE_BN_APPLY and K <= 4096:
+            if i == 0 and K <= 4096:
                 # first layer: only the dW GEMM consumes dL/dy -> the correction rides on its operand load, no pass over d
-                if _FOLD_BN_FINALIZE and prec == PREC_BF16 and B >= 8192 and N >= 128 and K >= 256:
+                if prec == PREC_BF16 and B >= 8192 and N >= 128 and K >= 256:
                     try:
                         tn(prec, d, h_in, grads[lin.weight], grads[lin.bias], N, K, q_prologue=pro_in,
                            p_prologue=(y, st.mean, st.rstd, None, fin), tag=f"{self.name}.L{i}.dW")
                         continue
-                    except RuntimeError:
+                    except L_.MMVAEArgError:
                         pass                                   # refused before anything was enqueued
                 ops.bn_bwd_finalize(B, N, stats, bn.weight, st.rstd, grads[bn.weight], grads[bn.bias], coef, eval_mode=not train)
                 tn(prec, d, h_in, grads[lin.weight], grads[lin.bias], N, K, q_prologue=pro_in,
                    p_prologue=(y, st.mean, st.rstd, coef), tag=f"{self.name}.L{i}.dW")
                 continue
-            done = False
-            if _FOLD_BN_FINALIZE:
-                try:
-                    ops.bn_bwd_finalize_apply(d, y, B, N, st.mean, st.rstd, *fin)
-                    done = True
-                except RuntimeError:
-                    pass
-            if not done:
+            try:
+                ops.bn_bwd_finalize_apply(d, y, B, N, st.mean, st.rstd, *fin)
+            except L_.MMVAEArgError:
                 ops.bn_bwd_finalize(B, N, stats, bn.weight, st.rstd, grads[bn.weight], grads[bn.bias], coef, eval_mode=not train)
                 ops.bn_bwd_apply(d, y, N, st.mean, st.rstd, coef)
             tn(prec, d, h_in, grads[lin.weight], grads[lin.bias], N, K, q_prologue=pro_in, tag=f"{self.name}.L{i}.dW")
@@ -444,7 +433,7 @@ class VAEGraph:
         out = []
         for d in self.decoders:
             for l in d.linears:
-                if _GROUP_TINY_DW and l.weight.numel() <= _TINY_DW_MAX:
+                if l.weight.numel() <= _TINY_DW_MAX:
                     out += [l.weight, l.bias]
         return out
 
@@ -477,7 +466,7 @@ class VAEGraph:
             # backward.  Each decoder continues from / writes into its column slice (widths must keep the slices 16-byte aligned).
             self.dec_stem = None
             decs = self.decoders
-            if (_MERGE_DECODER_STEM and len(decs) >= 2 and all(isinstance(d, DecoderMLP) and len(d.linears) >= 2 for d in decs)
+            if (len(decs) >= 2 and all(isinstance(d, DecoderMLP) and len(d.linears) >= 2 for d in decs)
                     and all(d.linears[0].in_features == decs[0].linears[0].in_features and d.linears[0].out_features % 8 == 0 for d in decs)):
                 self.dec_stem = ops.PreparedLinear([d.linears[0].weight for d in decs], [d.linears[0].bias for d in decs], prec, device)
                 pls.append(self.dec_stem)
@@ -485,16 +474,17 @@ class VAEGraph:
             self._prep_key = key
         self._prep.run()
 
-    def forward(self, prec, xa, xb, site, train):
-        """Returns (outs(list, fp32), mu, logvar, saved)."""
+    def forward(self, prec, xa, xb, site, train, want_bwd=False):
+        """Returns (outs(list, fp32), mu, logvar, saved).  want_bwd: a backward will follow (training only) -- decided by the caller
+        (functional.run_graph) BEFORE it enters the autograd.Function, inside which grad mode is always off."""
         ref = xa if xa is not None else (xb if xb is not None else site)
         if not ref.is_cuda:
             raise RuntimeError(f"the MI355X path needs inputs and parameters on one CUDA/HIP device (input on {ref.device}); "
                                "there is no CPU fallback")
         with ops.pinned_stream():
-            return self._forward(prec, xa, xb, site, train)
+            return self._forward(prec, xa, xb, site, train, train and want_bwd)
 
-    def _forward(self, prec, xa, xb, site, train):
+    def _forward(self, prec, xa, xb, site, train, want_bwd):
         ref = xa if xa is not None else (xb if xb is not None else site)
         dev, B = ref.device, ref.shape[0]
         if not ref.is_cuda or any(p.device != dev for p in self.param_list()):
@@ -510,8 +500,6 @@ class VAEGraph:
         # ONE memset for everything this step needs zeroed: forward BatchNorm sums, the loss accumulators, and -- when a backward will
         # follow -- the flat gradient arena with the backward's BatchNorm sums and embedding-table gradient (three fills before)
         st_all = []
-        # decided by the caller (functional.run_graph) BEFORE it enters the autograd.Function, inside which grad mode is always off
-        want_bwd = train and (bool(getattr(self, "_want_bwd", False)) or (torch.is_grad_enabled() and any(p.requires_grad for p in self.param_list())))
         if train:
             specs = [(2 * w, torch.float64) for w in widths_a + widths_b]
             nst = len(specs)
@@ -625,7 +613,7 @@ class VAEGraph:
         tiny = []
 
         def tn(prec_, p, q, dw, db, N, K, q_prologue=None, p_prologue=None, tag=None):
-            if _GROUP_TINY_DW and p_prologue is None and N * K <= _TINY_DW_MAX:
+            if p_prologue is None and N * K <= _TINY_DW_MAX:
                 tiny.append(dict(p=p, q=q, dw=dw, db=db, N=N, K=K, q_prologue=q_prologue))
                 return
             ops.gemm_tn(prec_, p, q, dw, db, N, K, q_prologue=q_prologue, p_prologue=p_prologue, slab=slab, tag=tag)

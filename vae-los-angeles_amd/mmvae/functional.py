@@ -20,9 +20,9 @@ from .ops import ceil_to, act_dtype
 
 class VAEGraphFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, graph, prec, train, xa, xb, site, *params):
+    def forward(ctx, graph, prec, train, want_bwd, xa, xb, site, *params):
         ctx.set_materialize_grads(False)
-        outs, mu, logvar, saved = graph.forward(prec, xa, xb, site, train)
+        outs, mu, logvar, saved = graph.forward(prec, xa, xb, site, train, want_bwd)
         ctx.graph, ctx.saved, ctx.n_out = graph, saved, len(outs)
         ctx.param_ids = [id(p) for p in graph.param_list()]
         graph._last_saved = saved
@@ -61,7 +61,7 @@ class VAEGraphFn(torch.autograd.Function):
         for p in graph.param_list():
             out.append(grads[p] if id(p) in used else None)
         del grads                                     # keep the views unique so autograd can adopt them
-        return (None, None, None, None, None, None, *out)
+        return (None, None, None, None, None, None, None, *out)
 
 
 def _as_rows(g):
@@ -100,11 +100,8 @@ def run_graph(graph, prec, train, xa, xb, site):
     params = graph.param_list()
     # a backward will follow: the forward's ONE memset then also zeroes the gradient arena, the backward's BatchNorm sums, the table
     # gradient and the loss accumulators (3 fill launches per step -> 1)
-    graph._want_bwd = train and torch.is_grad_enabled() and any(p.requires_grad for p in params)
-    try:
-        res = VAEGraphFn.apply(graph, prec, train, xa, xb, site, *params)
-    finally:
-        graph._want_bwd = False
+    want_bwd = train and torch.is_grad_enabled() and any(p.requires_grad for p in params)
+    res = VAEGraphFn.apply(graph, prec, train, want_bwd, xa, xb, site, *params)
     n = len(graph.decoders)
     outs, mu, logvar = list(res[:n]), res[n], res[n + 1]
     saved = graph._last_saved

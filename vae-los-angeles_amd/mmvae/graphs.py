@@ -14,12 +14,11 @@ torch.cuda.CUDAGraph, i.e. hipStreamBeginCapture) and replays it with a single l
 Data parallel (`reduce=` given): nothing of RCCL is captured (no graph support needed from the collective library); the
 step is cut into graphs at the points where a collective is issued eagerly on the flat gradient arena:
   * overlap=True (default): THREE graphs -- [forward, loss, decoder backward] | [fusion + encoder backward] | [AdamW].  The cut
-    sits where engine.VAEGraph.backward calls grad_sync.early(): the decoder gradients (tail of the arena) are final there and
-    their SUM all-reduce is launched asynchronously, then graph 2 replays while RCCL runs on its own stream; the encoder half
-    is reduced after graph 2 and both are waited for before graph 3 ("overlapped with encoder backward").
+    sits where engine.VAEGraph.backward calls grad_sync.early(): the large decoder gradients (tail of the arena, from
+    VAEGraph.early_cut() on) are final there and their SUM all-reduce is launched asynchronously, then graph 2 replays while RCCL
+    runs on its own stream; the head of the arena -- the encoders and the decoders' small-output tensors, whose grouped dW launch
+    ends the backward -- is reduced after graph 2 and both are waited for before graph 3 ("overlapped with encoder backward").
   * overlap=False: TWO graphs -- [forward, loss, backward] | [AdamW] -- with ONE all-reduce of the whole arena in between."""
-import os
-
 import torch
 
 from . import functional as F_
@@ -92,18 +91,17 @@ class GraphedTrainStep:
         # The step never looks at the reconstructions themselves: their loss terms and gradients are computed inside the decoders'
         # last GEMMs (engine.VAEGraph.fused_recon) instead of writing them as fp32 and reading them back with their targets.
         g = self.model._graph()
-        fuse = os.environ.get("MMVAE_NO_LOSS_EPILOGUE") is None
         try:
             if self.kind == "multimodal":
-                g.fused_recon = [self.a, self.b, None] if fuse else None
+                g.fused_recon = [self.a, self.b, None]
                 ra, rb, rc, mu, lv = self.model(a=self.a, b=self.b, site=self.site)
                 terms = {"a": (ra, self.a), "b": (rb, self.b), "c": (rc, self.site), "kl": (mu, lv)}
             elif self.kind == "dna2rna":
-                g.fused_recon = [self.a] if fuse else None
+                g.fused_recon = [self.a]
                 rec, mu, lv = self.model(dna=self.b, site=self.site)
                 terms = {"a": (rec, self.a), "kl": (mu, lv)}
             else:
-                g.fused_recon = [self.b] if fuse else None
+                g.fused_recon = [self.b]
                 rec, mu, lv = self.model(rna=self.a, site=self.site)
                 terms = {"b": (rec, self.b), "kl": (mu, lv)}
         finally:

@@ -7,8 +7,10 @@ SUM, not mean: every loss term of the reference is reduction='sum' (src/utils/lo
 stay per shard (the north_star's "all-reduce and nothing else"), i.e. N ranks reproduce N
 independent reference shards whose gradients are summed.
 
-The arena is laid out encoders first, decoders last; backward produces the decoder part first,
-so with `overlap=True` that tail is reduced asynchronously while the encoder backward runs.
+The arena is laid out as `engine.VAEGraph.param_list()` orders it: the encoders, then the decoders'
+small-output tensors (latent / class widths, whose grouped dW launch ends the backward), then the
+large decoder tensors.  Backward finishes that tail first, so with `overlap=True` it is reduced
+asynchronously from `early_cut()` on while the encoder backward runs.
 """
 import torch
 import torch.distributed as dist
