@@ -90,7 +90,10 @@ int mmvae_prep_weights(const mmvae_prep_item* items_dev, int32_t n_items, void* 
  *                                 (bf16 mode, bf16 A, K > 64): x = acc + bias is not stored; *stat1 (ONE f64) += sum (x - h)^2, or
  *                                 += sum BCE(sigmoid(x), h) with the log clamp at -100 (losses.py:31,34); C (bf16, ldc % 8 == 0,
  *                                 pad columns zeroed) = 2 (x - h), or sigmoid(x) - h = the gradient w.r.t. the logit; h = fp32 target
- *                                 [M][ldh].  Same arithmetic as mmvae_vae_loss on the stored output; saves writing and re-reading it.
+ *                                 [M][ldh] of h_dtype.  Same arithmetic as mmvae_vae_loss on the stored output; saves writing and re-reading it.
+ *                                 h_dtype MMVAE_BF16: the target is read as bf16 (rows aligned to 2 bytes; padded bf16 rows, see
+ *                                 mmvae_rows_to_bf16, give the widest loads) and widened to fp32 on load: on equal values the gradient
+ *                                 elements are bit-identical to the fp32-target form and the loss sum differs only by the f64 atomics' order.
  * Replaces: nn.Linear forward = aten::addmm (encoders.py:13,18-19,31,35,40-41,54-55;
  *   decoders.py:13,15,27,29,31,44,46), relu/sigmoid (decoders.py:14,28,30,32), batch-norm
  *   statistics, and the dX mm of each Linear backward (optimize_hyperparameters.py:112).
@@ -121,6 +124,9 @@ typedef struct {
        running statistics and num_batches_tracked -- for the backward pass.  fin->N must equal K.  Not for operands of 4 GiB or more
        (MMVAE_ERR_ARG: the row blocks would each update the running statistics). */
     const void* pro_finalize;
+    /* element type of h for MMVAE_EPI_LOSS_MSE / MMVAE_EPI_LOSS_BCE_LOGIT: MMVAE_F32 (0, the zero-initialised default) or MMVAE_BF16.
+       Ignored by the other epilogues (their h is activation-typed). */
+    int32_t h_dtype;
 } mmvae_gemm_nt_args;
 int mmvae_gemm_nt(const mmvae_gemm_nt_args* args, void* stream);
 
@@ -266,8 +272,8 @@ int mmvae_fuse_reparam_bwd(const mmvae_fuse_bwd_args* args, void* stream);
  * ------------------------------------------------------------------------------------------- */
 typedef struct {
     int32_t B, A, D, S, L;
-    const float* recon_a; const float* a; int64_t ld_ra, ld_a;
-    const float* recon_b; const float* b; int64_t ld_rb, ld_b;
+    const float* recon_a; const void* a; int64_t ld_ra, ld_a;          /* a: element type a_dtype (below) */
+    const float* recon_b; const void* b; int64_t ld_rb, ld_b;          /* b: element type b_dtype (below) */
     const float* logits; int64_t ld_logits; const int64_t* site; const float* class_weights;
     const float* mu; const float* logvar;
     float beta, gamma;
@@ -278,6 +284,10 @@ typedef struct {
     float* g_mu; float* g_lv;
     const float* beta_gamma_dev;      /* optional {beta, gamma} in device memory: overrides the by-value fields, so a captured hipGraph
                                          follows the beta warm-up (optimize_hyperparameters.py:103) without re-capture */
+    /* element types of the MSE / BCE targets a and b: MMVAE_F32 (0, the zero-initialised default) or MMVAE_BF16 (a dataset kept in
+       bf16 storage; any row stride, rows 2-byte aligned).  bf16 targets are widened on load: on equal values the gradients are
+       bit-identical to the fp32-target call and the sums differ only by the order of the f64 atomics. */
+    int32_t a_dtype, b_dtype;
 } mmvae_loss_args;
 int mmvae_vae_loss(const mmvae_loss_args* args, void* stream);
 /* out5 = {recon + gamma*class + beta*kld, recon, class, kld, labels out of range} (float) from sums[5]. */
@@ -320,6 +330,18 @@ int mmvae_counter_add(uint64_t* counter_dev, uint64_t inc, void* stream);      /
 typedef struct { const void* src; void* dst; int64_t src_row_stride; int64_t dst_row_stride; int32_t row_bytes; int32_t pad_; } mmvae_gather_item;
 int mmvae_gather_rows(const mmvae_gather_item* items_host, int32_t n_items, const int64_t* idx_dev, int32_t rows,
                       int64_t src_rows, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Inputs in bf16 storage ("padded bf16 rows"): a bf16 matrix [rows][ld_dst] with ld_dst % 8 == 0, a 16-byte aligned base and ZEROS in
+ * the pad columns cols .. ld_dst-1 -- the layout of every bf16 A operand above, so the first-layer GEMMs, their dW GEMMs (Q) and the
+ * loss epilogues read such a dataset directly.  One launch (graph-capturable):
+ *   dst[r][c] = bf16(src[r][c]) for c < cols, 0 for cols <= c < ld_dst;  src: fp32 or bf16 (src_dtype), any row stride ld_src, rows
+ *   aligned to the element size.  dst holds rows * ld_dst elements.  fp32 values are rounded to nearest even exactly as
+ *   torch.Tensor.to(torch.bfloat16) does (every NaN -> 0x7FC0, +-Inf kept, denormals rounded, not flushed); bf16 is copied bit for bit.
+ * Replaces: the per-step fp32 -> bf16 conversion the GEMM producers do on fp32 inputs (a dataset is converted once per run).
+ * ------------------------------------------------------------------------------------------- */
+int mmvae_rows_to_bf16(const void* src, int32_t src_dtype, int64_t ld_src, void* dst, int64_t ld_dst, int32_t rows, int32_t cols,
+                       void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * AdamW (torch.optim.AdamW, constructed by the caller: optimize_hyperparameters.py:93-97,

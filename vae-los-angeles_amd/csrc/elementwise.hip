@@ -368,8 +368,9 @@ constexpr int LOSS_U = 4;
 // term of one element and its gradient.  The hot loop has no per-vector conditions: iterations in which all U vectors of the
 // thread exist run unchecked, the (< U) vectors left are taken one at a time, and the pad columns of the gradient rows (the GEMM
 // operand contract: zeros up to the next multiple of 8) are written by a separate row loop.
-template <typename GT, int V, bool HAS_G, typename F>
-__device__ __forceinline__ float stream_part(const float* __restrict__ pred, long ld_p, const float* __restrict__ tgt, long ld_t,
+// TT: the target's element type (float, or bf16 for a dataset stored as padded bf16 rows: widened on load, the same arithmetic).
+template <typename GT, int V, bool HAS_G, typename TT, typename F>
+__device__ __forceinline__ float stream_part(const float* __restrict__ pred, long ld_p, const TT* __restrict__ tgt, long ld_t,
                                              GT* g_out, long ld_g, int B, int W, long tid0, long stride, F f) {
     float acc = 0.f;
     const unsigned vpr = (unsigned)(W / V);
@@ -388,7 +389,7 @@ __device__ __forceinline__ float stream_part(const float* __restrict__ pred, lon
 #pragma unroll
         for (int u = 0; u < LOSS_U; ++u) {
             VLoad<float, V>::ld(pred + w.o[0], x[u]);
-            VLoad<float, V>::ld(tgt + w.o[1], t[u]);
+            VLoad<TT, V>::ld(tgt + w.o[1], t[u]);
             og[u] = w.o[2];
             w.next();
         }
@@ -398,7 +399,7 @@ __device__ __forceinline__ float stream_part(const float* __restrict__ pred, lon
     for (; i < total; i += stride) {
         float x[V], t[V];
         VLoad<float, V>::ld(pred + w.o[0], x);
-        VLoad<float, V>::ld(tgt + w.o[1], t);
+        VLoad<TT, V>::ld(tgt + w.o[1], t);
         const long og = w.o[2];
         w.next();
         one(x, t, og);
@@ -412,14 +413,15 @@ __device__ __forceinline__ float stream_part(const float* __restrict__ pred, lon
     return acc;
 }
 
-template <typename GT, int V>
+template <typename GT, int V, typename TT>
 __device__ __forceinline__ float mse_part(const mmvae_loss_args& a, long tid0, long stride) {
     auto f = [](float x, float t, float& g) { const float d = x - t; g = 2.f * d; return d * d; };
-    if (a.g_a) return stream_part<GT, V, true>(a.recon_a, a.ld_ra, a.a, a.ld_a, (GT*)a.g_a, a.ld_ga, a.B, a.A, tid0, stride, f);
-    return stream_part<GT, V, false>(a.recon_a, a.ld_ra, a.a, a.ld_a, (GT*)nullptr, 0, a.B, a.A, tid0, stride, f);
+    const TT* t = (const TT*)a.a;
+    if (a.g_a) return stream_part<GT, V, true>(a.recon_a, a.ld_ra, t, a.ld_a, (GT*)a.g_a, a.ld_ga, a.B, a.A, tid0, stride, f);
+    return stream_part<GT, V, false>(a.recon_a, a.ld_ra, t, a.ld_a, (GT*)nullptr, 0, a.B, a.A, tid0, stride, f);
 }
 
-template <typename GT, int V, bool WRT_LOGIT>
+template <typename GT, int V, bool WRT_LOGIT, typename TT>
 __device__ __forceinline__ float bce_part_g(const mmvae_loss_args& a, long tid0, long stride) {
     auto f = [](float pe, float te, float& g) {
         const float lp = fmaxf(fast_ln(pe), -100.f), l1p = fmaxf(fast_ln(1.f - pe), -100.f);   // v_log_f32: 1 ulp, clamp as torch
@@ -429,13 +431,14 @@ __device__ __forceinline__ float bce_part_g(const mmvae_loss_args& a, long tid0,
         else g = d * __builtin_amdgcn_rcpf(fmaxf(pq, 1e-12f));
         return -(te * lp + (1.f - te) * l1p);
     };
-    if (a.g_b) return stream_part<GT, V, true>(a.recon_b, a.ld_rb, a.b, a.ld_b, (GT*)a.g_b, a.ld_gb, a.B, a.D, tid0, stride, f);
-    return stream_part<GT, V, false>(a.recon_b, a.ld_rb, a.b, a.ld_b, (GT*)nullptr, 0, a.B, a.D, tid0, stride, f);
+    const TT* t = (const TT*)a.b;
+    if (a.g_b) return stream_part<GT, V, true>(a.recon_b, a.ld_rb, t, a.ld_b, (GT*)a.g_b, a.ld_gb, a.B, a.D, tid0, stride, f);
+    return stream_part<GT, V, false>(a.recon_b, a.ld_rb, t, a.ld_b, (GT*)nullptr, 0, a.B, a.D, tid0, stride, f);
 }
 
-template <typename GT, int V>
+template <typename GT, int V, typename TT>
 __device__ __forceinline__ float bce_part(const mmvae_loss_args& a, long tid0, long stride) {
-    return a.grad_b_wrt_logit ? bce_part_g<GT, V, true>(a, tid0, stride) : bce_part_g<GT, V, false>(a, tid0, stride);
+    return a.grad_b_wrt_logit ? bce_part_g<GT, V, true, TT>(a, tid0, stride) : bce_part_g<GT, V, false, TT>(a, tid0, stride);
 }
 
 // TAIL: the class + KL terms alone (the reconstruction terms run inside the decoder GEMMs).  The launch is then a few dependent
@@ -445,14 +448,15 @@ __device__ __forceinline__ float bce_part(const mmvae_loss_args& a, long tid0, l
 // ce_vec (S % 4 == 0, S <= 32, 16-byte aligned rows): the class term as ONE ROW PER THREAD -- S / 4 16-byte loads, max, one exp
 // per logit kept in registers, S / 4 16-byte gradient stores -- instead of a row per half wave, whose two 5-step butterflies + the
 // label pick are eleven DEPENDENT ds_bpermute round trips per row (~1 500 cycles; 17 of this launch's 25 us at B = 65 536).
-template <typename GT, int VA, int VD, bool TAIL = false>
+// TA / TB: element types of the MSE / BCE targets (a_dtype / b_dtype).
+template <typename GT, int VA, int VD, bool TAIL = false, typename TA = float, typename TB = float>
 __global__ __launch_bounds__(256) void vae_loss_kernel(mmvae_loss_args a, int ce_vec) {
     if (a.beta_gamma_dev) { a.beta = a.beta_gamma_dev[0]; a.gamma = a.beta_gamma_dev[1]; }     // hyper-parameters a captured graph can change
     const long tid0 = (long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long)gridDim.x * blockDim.x;
     float s[4] = {0.f, 0.f, 0.f, 0.f};
     float n_bad = 0.f;
-    if (!TAIL && a.recon_a) s[0] = mse_part<GT, VA>(a, tid0, stride);
-    if (!TAIL && a.recon_b) s[1] = bce_part<GT, VD>(a, tid0, stride);
+    if (!TAIL && a.recon_a) s[0] = mse_part<GT, VA, TA>(a, tid0, stride);
+    if (!TAIL && a.recon_b) s[1] = bce_part<GT, VD, TB>(a, tid0, stride);
     constexpr int KL_U = TAIL ? 10 : 4;
     const long total = a.mu ? (long)a.B * a.L : 0;
     float mu0[KL_U], lv0[KL_U];
@@ -721,6 +725,38 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const GatherBatch b, c
 }
 
 // ------------------------------------------------------------------------------------------
+// fp32 / bf16 rows of any row stride -> padded bf16 rows (the layout the bf16-A GEMM producers read in 16-byte chunks): one thread per
+// 16-byte destination chunk, the pad columns cols .. ld_dst-1 written as zeros.  Rounding is torch's (c10::BFloat16): round to nearest
+// even on the bits, every NaN -> 0x7FC0; denormals are rounded like any other value (no flush).  bf16 sources are copied bit for bit.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint16_t bf16_bits_rne(float f) {
+    const uint32_t u = __float_as_uint(f);
+    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return 0x7FC0;
+    return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+}
+__device__ __forceinline__ uint16_t bf16_bits_of(float v) { return bf16_bits_rne(v); }
+__device__ __forceinline__ uint16_t bf16_bits_of(uint16_t v) { return v; }
+
+template <typename ST>       // float, or uint16_t (bf16 bits)
+__global__ __launch_bounds__(256) void rows_to_bf16_kernel(const ST* __restrict__ src, long ld_src, uint16_t* __restrict__ dst, long ld_dst,
+                                                           int rows, int cols) {
+    const long chunks = ld_dst >> 3, total = (long)rows * chunks;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const long r = i / chunks;
+        const int c0 = (int)(i - r * chunks) << 3;
+        const ST* sp = src + r * ld_src;
+        uint32_t w[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int c = c0 + 2 * e;
+            const uint32_t lo = c < cols ? bf16_bits_of(sp[c]) : 0u, hi = c + 1 < cols ? bf16_bits_of(sp[c + 1]) : 0u;
+            w[e] = lo | (hi << 16);
+        }
+        *(uint4*)(dst + r * ld_dst + c0) = uint4{w[0], w[1], w[2], w[3]};
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // AdamW, all tensors in one launch
 // ------------------------------------------------------------------------------------------
 // Blocks are dealt out in proportion to the tensors' sizes (first[i] .. first[i+1] belong to tensor i): a (blocks x tensors) grid gave
@@ -782,7 +818,7 @@ static inline int grid_for(long items, int per_block = 256, int cap = 2048) {
 
 using namespace mm;
 
-extern "C" int mmvae_abi_version(void) { return 19; }
+extern "C" int mmvae_abi_version(void) { return 20; }
 
 extern "C" int mmvae_prep_weights(const mmvae_prep_item* items_dev, int32_t n_items, void* stream) {
     if (!items_dev || n_items <= 0) return MMVAE_ERR_ARG;
@@ -899,19 +935,19 @@ extern "C" int mmvae_fuse_reparam_bwd(const mmvae_fuse_bwd_args* a, void* stream
     return 0;
 }
 
-template <typename GT>
+template <typename GT, typename TA, typename TB>
 static int launch_loss(const mmvae_loss_args* a, hipStream_t st) {
     auto al = [](const void* p, int64_t ld, int v, size_t es) { return p == nullptr || (ld % v == 0 && ((uintptr_t)p % (v * es)) == 0); };
     int va = 1, vd = 1;
     for (int v : {4, 2}) {
-        if (va == 1 && a->recon_a && a->A % v == 0 && al(a->recon_a, a->ld_ra, v, 4) && al(a->a, a->ld_a, v, 4) && al(a->g_a, a->ld_ga, v, sizeof(GT))) va = v;
-        if (vd == 1 && a->recon_b && a->D % v == 0 && al(a->recon_b, a->ld_rb, v, 4) && al(a->b, a->ld_b, v, 4) && al(a->g_b, a->ld_gb, v, sizeof(GT))) vd = v;
+        if (va == 1 && a->recon_a && a->A % v == 0 && al(a->recon_a, a->ld_ra, v, 4) && al(a->a, a->ld_a, v, sizeof(TA)) && al(a->g_a, a->ld_ga, v, sizeof(GT))) va = v;
+        if (vd == 1 && a->recon_b && a->D % v == 0 && al(a->recon_b, a->ld_rb, v, 4) && al(a->b, a->ld_b, v, sizeof(TB)) && al(a->g_b, a->ld_gb, v, sizeof(GT))) vd = v;
     }
     // vectors of the stream parts + the per-row class term + the latent elements: without the reconstruction parts (their loss runs
     // inside the decoder GEMMs) the class / KL terms alone must still fill the chip (a row per thread, not four rows on 64 workgroups)
     const long work = (long)a->B * ((a->recon_a ? a->A / va : 0) + (a->recon_b ? a->D / vd : 0) + (a->logits ? 4 * a->S : 0) + (a->mu ? a->L : 0) + 1);
     int grid = mm::grid_for(work, 256 * 4, 1024);
-#define MM_LOSS(VA, VD) hipLaunchKernelGGL((vae_loss_kernel<GT, VA, VD>), dim3(grid), dim3(256), 0, st, *a, ce_vec ? 1 : 0)
+#define MM_LOSS(VA, VD) hipLaunchKernelGGL((vae_loss_kernel<GT, VA, VD, false, TA, TB>), dim3(grid), dim3(256), 0, st, *a, ce_vec ? 1 : 0)
     const bool ce_vec = a->logits && a->S <= 32 && a->S % 4 == 0 && a->ld_logits % 4 == 0 && ((uintptr_t)a->logits & 15) == 0 &&
                         (!a->g_c || (a->ld_gc % 4 == 0 && ((uintptr_t)a->g_c & 15) == 0));
     if (!a->recon_a && !a->recon_b) {
@@ -928,6 +964,16 @@ static int launch_loss(const mmvae_loss_args* a, hipStream_t st) {
     return 0;
 }
 
+// the target types (a_dtype / b_dtype: fp32 or bf16) -> template arguments; a term that is absent takes fp32 (no extra instances)
+template <typename GT>
+static int launch_loss_t(const mmvae_loss_args* a, hipStream_t st) {
+    const bool a16 = a->recon_a && a->a_dtype == MMVAE_BF16, b16 = a->recon_b && a->b_dtype == MMVAE_BF16;
+    if (a16 && b16) return launch_loss<GT, bf16, bf16>(a, st);
+    if (a16) return launch_loss<GT, bf16, float>(a, st);
+    if (b16) return launch_loss<GT, float, bf16>(a, st);
+    return launch_loss<GT, float, float>(a, st);
+}
+
 extern "C" int mmvae_vae_loss(const mmvae_loss_args* a, void* stream) {
     if (!a || a->B <= 0 || !a->sums) return MMVAE_ERR_ARG;
     if (a->recon_a && (!a->a || a->A <= 0)) return MMVAE_ERR_ARG;
@@ -935,10 +981,14 @@ extern "C" int mmvae_vae_loss(const mmvae_loss_args* a, void* stream) {
     if (a->logits && (!a->site || a->S <= 0)) return MMVAE_ERR_ARG;
     if (a->mu && (!a->logvar || a->L <= 0)) return MMVAE_ERR_ARG;
     if ((long)a->B * (a->A > a->D ? a->A : a->D) >= (1L << 32)) return MMVAE_ERR_ARG;
+    if ((a->a_dtype != MMVAE_F32 && a->a_dtype != MMVAE_BF16) || (a->b_dtype != MMVAE_F32 && a->b_dtype != MMVAE_BF16)) return MMVAE_ERR_DTYPE;
+    // targets: element-aligned rows (2 bytes for bf16, 4 for fp32); the vector width follows the alignment (launch_loss)
+    if (a->recon_a && ((uintptr_t)a->a & (a->a_dtype == MMVAE_BF16 ? 1 : 3))) return MMVAE_ERR_ARG;
+    if (a->recon_b && ((uintptr_t)a->b & (a->b_dtype == MMVAE_BF16 ? 1 : 3))) return MMVAE_ERR_ARG;
     const int gdt = a->g_a ? a->g_a_dtype : a->g_b_dtype;
     if (a->g_a && a->g_b && a->g_a_dtype != a->g_b_dtype) return MMVAE_ERR_DTYPE;
-    if (gdt == MMVAE_BF16) return launch_loss<bf16>(a, (hipStream_t)stream);
-    return launch_loss<float>(a, (hipStream_t)stream);
+    if (gdt == MMVAE_BF16) return launch_loss_t<bf16>(a, (hipStream_t)stream);
+    return launch_loss_t<float>(a, (hipStream_t)stream);
 }
 
 extern "C" int mmvae_loss_finalize(const double* sums, float beta, float gamma, const float* beta_gamma_dev, float* out4, void* stream) {
@@ -1024,6 +1074,23 @@ extern "C" int mmvae_gather_rows(const mmvae_gather_item* items_host, int32_t n_
     int grid = (int)((waves + 3) / 4);
     if (grid > 4096) grid = 4096;
     hipLaunchKernelGGL(gather_rows_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, b, idx_dev, rows, (long)src_rows);
+    MM_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int mmvae_rows_to_bf16(const void* src, int32_t src_dtype, int64_t ld_src, void* dst, int64_t ld_dst, int32_t rows,
+                                  int32_t cols, void* stream) {
+    if (!src || !dst || rows <= 0 || cols <= 0 || ld_src < 0 || (rows > 1 && ld_src < cols)) return MMVAE_ERR_ARG;
+    if (ld_dst < cols || ld_dst % 8 || ((uintptr_t)dst & 15)) return MMVAE_ERR_ARG;
+    if (src_dtype != MMVAE_F32 && src_dtype != MMVAE_BF16) return MMVAE_ERR_DTYPE;
+    if ((uintptr_t)src & (src_dtype == MMVAE_BF16 ? 1 : 3)) return MMVAE_ERR_ARG;
+    const int grid = grid_for((long)rows * (ld_dst / 8), 256, 4096);
+    if (src_dtype == MMVAE_F32)
+        hipLaunchKernelGGL(rows_to_bf16_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const float*)src, (long)ld_src,
+                           (uint16_t*)dst, (long)ld_dst, rows, cols);
+    else
+        hipLaunchKernelGGL(rows_to_bf16_kernel<uint16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)src, (long)ld_src,
+                           (uint16_t*)dst, (long)ld_dst, rows, cols);
     MM_CHECK_LAUNCH();
     return 0;
 }

@@ -394,15 +394,23 @@ static int dispatch_epi(const mmvae_gemm_nt_args* a, const Src& src, hipStream_t
         // reconstruction loss inside a decoder's last GEMM: bf16 mode, plain bf16 A, second-generation kernel, 128 x 128 tiles
         if constexpr (sizeof(CT) == 2 && IsPlainBf16<Src>::value) {
             if (!a->h || !a->c || !a->stat1 || a->c_dtype != MMVAE_BF16 || a->accumulate || a->K <= 64) return MMVAE_ERR_ARG;
-            if (a->ldc % 8 || ((uintptr_t)a->c & 15) || ((uintptr_t)a->h & 3)) return MMVAE_ERR_ARG;
-            if ((long)a->M * a->ldh * 4 >= (1L << 40)) return MMVAE_ERR_ARG;
+            // the target: fp32, or bf16 (h_dtype; a dataset kept as padded bf16 rows), rows aligned to its element size
+            const bool h16 = a->h_dtype == MMVAE_BF16;
+            if (a->h_dtype != MMVAE_F32 && !h16) return MMVAE_ERR_DTYPE;
+            const long hsz = h16 ? 2 : 4;
+            if (a->ldc % 8 || ((uintptr_t)a->c & 15) || ((uintptr_t)a->h & (hsz - 1))) return MMVAE_ERR_ARG;
+            if ((long)a->M * a->ldh * hsz >= (1L << 40)) return MMVAE_ERR_ARG;
             const uintptr_t hp = (uintptr_t)a->h;
-            const int vt = (a->ldh % 4 == 0 && a->N % 4 == 0 && (hp & 15) == 0) ? 4 : (a->ldh % 2 == 0 && a->N % 2 == 0 && (hp & 7) == 0) ? 2 : 1;
+            const int vt = (a->ldh % 4 == 0 && a->N % 4 == 0 && (hp & (4 * hsz - 1)) == 0) ? 4 :
+                           (a->ldh % 2 == 0 && a->N % 2 == 0 && (hp & (2 * hsz - 1)) == 0) ? 2 : 1;
             const bool mse = a->epilogue == MMVAE_EPI_LOSS_MSE;
-#define MM_LOSS_EPI(MODE, VT) { EpiLoss<MODE, VT> e{(bf16*)a->c, a->ldc, (const float*)a->h, a->ldh, a->bias, a->stat1}; \
-                                return launch_nt2<EpiLoss<MODE, VT>, 2>(src.p, src.lda, a->w, a->ldw, a->M, a->N, a->K, e, st); }
-            if (mse) { if (vt == 4) MM_LOSS_EPI(0, 4) if (vt == 2) MM_LOSS_EPI(0, 2) MM_LOSS_EPI(0, 1) }
-            if (vt == 4) MM_LOSS_EPI(1, 4) if (vt == 2) MM_LOSS_EPI(1, 2) MM_LOSS_EPI(1, 1)
+#define MM_LOSS_EPI(MODE, VT, TT) { EpiLoss<MODE, VT, TT> e{(bf16*)a->c, a->ldc, (const TT*)a->h, a->ldh, a->bias, a->stat1}; \
+                                    return launch_nt2<EpiLoss<MODE, VT, TT>, 2>(src.p, src.lda, a->w, a->ldw, a->M, a->N, a->K, e, st); }
+#define MM_LOSS_VT(MODE, TT) { if (vt == 4) MM_LOSS_EPI(MODE, 4, TT) if (vt == 2) MM_LOSS_EPI(MODE, 2, TT) MM_LOSS_EPI(MODE, 1, TT) }
+            if (h16) { if (mse) MM_LOSS_VT(0, bf16) MM_LOSS_VT(1, bf16) }
+            if (mse) MM_LOSS_VT(0, float)
+            MM_LOSS_VT(1, float)
+#undef MM_LOSS_VT
 #undef MM_LOSS_EPI
         }
         return MMVAE_ERR_ARG;
@@ -506,9 +514,9 @@ extern "C" int mmvae_gemm_nt(const mmvae_gemm_nt_args* a, void* stream) {
             s.M = (int32_t)((a->M - r0 < rows) ? a->M - r0 : rows);
             s.a = (const char*)a->a + r0 * a_row;
             if (a->c) s.c = (char*)a->c + r0 * a->ldc * (a->c_dtype == MMVAE_BF16 ? 2 : 4);
-            // H is activation-typed, except for the loss epilogues, whose H is the fp32 target
+            // H is activation-typed, except for the loss epilogues, whose H is the target (fp32 or bf16: h_dtype)
             const bool loss_epi = a->epilogue == MMVAE_EPI_LOSS_MSE || a->epilogue == MMVAE_EPI_LOSS_BCE_LOGIT;
-            const long hsz = (a->prec == MMVAE_PREC_BF16 && !loss_epi) ? 2 : 4;
+            const long hsz = loss_epi ? (a->h_dtype == MMVAE_BF16 ? 2 : 4) : (a->prec == MMVAE_PREC_BF16 ? 2 : 4);
             if (a->h) s.h = (const char*)a->h + r0 * a->ldh * hsz;
             if (a->pro_mask) s.pro_mask = a->pro_mask + r0 * a->ld_pro_mask;
             if (a->epi_mask) s.epi_mask = a->epi_mask + r0 * a->ld_epi_mask;

@@ -52,7 +52,8 @@ __device__ __forceinline__ void nt2_loss_epilogue(unsigned char* smem, const flo
     const int li = lane & 15, lg = lane >> 4;
     const int c = tid & 31, r0 = tid >> 5;                         // row-coalesced pass: 8 rows per pass, 16 passes, 4 columns per thread
     const int colg = col0 + 4 * c;
-    const float* __restrict__ T = epi.T;
+    typedef typename Epi::t_t TT;
+    const TT* __restrict__ T = epi.T;
     bf16* __restrict__ G = epi.G;
     // ALL 16 target vectors of the thread are requested first (64 registers -- the accumulators die in the LDS image below): with 4
     // in flight per thread the pass ran at the latency-bound 3.6 TB/s of 32 KB in flight per CU; the LDS transposition now covers
@@ -63,16 +64,16 @@ __device__ __forceinline__ void nt2_loss_epilogue(unsigned char* smem, const flo
     if (interior) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const float* tp = T + (long)(row0 + r0 + 8 * i) * epi.ldt + colg;
+            const TT* tp = T + (long)(row0 + r0 + 8 * i) * epi.ldt + colg;
 #pragma unroll
-            for (int e = 0; e < 4; e += Epi::VT) VLoad<float, Epi::VT>::ld(tp + e, &t[i][e]);
+            for (int e = 0; e < 4; e += Epi::VT) VLoad<TT, Epi::VT>::ld(tp + e, &t[i][e]);
         }
     } else {
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const float* tp = T + (long)min(row0 + r0 + 8 * i, M - 1) * epi.ldt;
+            const TT* tp = T + (long)min(row0 + r0 + 8 * i, M - 1) * epi.ldt;
 #pragma unroll
-            for (int e = 0; e < 4; e += Epi::VT) VLoad<float, Epi::VT>::ld(tp + min(colg + e, N - Epi::VT), &t[i][e]);
+            for (int e = 0; e < 4; e += Epi::VT) VLoad<TT, Epi::VT>::ld(tp + min(colg + e, N - Epi::VT), &t[i][e]);
         }
     }
     __syncthreads();                                               // every wave has finished reading the ring

@@ -119,15 +119,19 @@ struct EpiBnBwd {               // BatchNorm+ReLU+Dropout backward around the dX
 // backward); MODE 1: p = sigmoid(x), sum-BCE with torch's log clamp at -100 against T, gradient w.r.t. the LOGIT x
 // (losses.py:34, decoders.py:32) -- the arithmetic of vae_loss_kernel (elementwise.hip) on the values the store epilogue would
 // have written.  G: bf16 gradient rows (pad columns up to the next multiple of 8 are zeroed), sum: one f64 accumulator.
-// VT: widest vector the target rows allow (4: 16-byte aligned rows and N % 4 == 0; 2: 8-byte aligned, N % 2 == 0; 1).
-template <int MODE_, int VT_>
+// VT: widest vector the target rows allow (4: rows aligned to 4 elements and N % 4 == 0; 2: to 2 elements, N % 2 == 0; 1).
+// TT: element type of the target -- float, or bf16 (a dataset stored as padded bf16 rows: the values are widened on load, so per
+// element the arithmetic below sees the same floats as with the fp32 copy of the same data).  A thread of the row-coalesced pass
+// owns 4 consecutive columns, so a bf16 row piece is 8 bytes per thread (256 contiguous bytes per half wave).
+template <int MODE_, int VT_, typename TT = float>
 struct EpiLoss {
     static constexpr bool STATS = false;
     static constexpr bool LDS_STREAM = true;
     static constexpr int NEED = 0;
     static constexpr int MODE = MODE_, VT = VT_;
     typedef float out_t; typedef float h_t;           // 4-byte output layout: a lane's accumulator (m, n)[j] is column 16 n + 4 lg + j
-    bf16* G; long ldg; const float* T; long ldt; const float* bias; double* sum;
+    typedef TT t_t;
+    bf16* G; long ldg; const TT* T; long ldt; const float* bias; double* sum;
     struct Col { float b; };
     static constexpr int NCOL = 1;
     bool accumulate_requested() const { return false; }

@@ -6,3 +6,4 @@ launches, and exposes them to the reference-shaped modules in `src/`.
 """
 from . import _lib                                    # noqa: F401
 from ._lib import PREC_BF16, PREC_F32, MMVAELibraryError  # noqa: F401
+from .ops import to_bf16_rows, is_bf16_rows           # noqa: F401,E402  inputs in bf16 storage (padded bf16 rows)

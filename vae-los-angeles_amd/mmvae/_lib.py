@@ -9,7 +9,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MMVAE_LIB_PATH") or os.path.join(_HERE, "libmmvae_hip.so")     # override: experimental builds
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 F32, BF16 = 0, 1
 PREC_F32, PREC_BF16 = 0, 1
@@ -43,7 +43,7 @@ class GemmNtArgs(C.Structure):
                 ("epi_mask", vp), ("ld_epi_mask", i64), ("epi_inv_keep", f32),
                 ("bn_coef", vp), ("bn_phase", i32),
                 ("stat1", vp), ("stat2", vp),
-                ("pro_out", vp), ("ld_pro_out", i64), ("pro_finalize", vp)]
+                ("pro_out", vp), ("ld_pro_out", i64), ("pro_finalize", vp), ("h_dtype", i32)]
 
 
 class GemmTnArgs(C.Structure):
@@ -101,7 +101,7 @@ class LossArgs(C.Structure):
                 ("g_a", vp), ("g_a_dtype", i32), ("ld_ga", i64),
                 ("g_b", vp), ("g_b_dtype", i32), ("ld_gb", i64), ("grad_b_wrt_logit", i32),
                 ("g_c", vp), ("ld_gc", i64),
-                ("g_mu", vp), ("g_lv", vp), ("beta_gamma_dev", vp)]
+                ("g_mu", vp), ("g_lv", vp), ("beta_gamma_dev", vp), ("a_dtype", i32), ("b_dtype", i32)]
 
 
 class GatherItem(C.Structure):
@@ -131,6 +131,7 @@ _SIGNATURES = {
     "mmvae_vae_loss": [C.POINTER(LossArgs), vp],
     "mmvae_loss_finalize": [vp, f32, f32, vp, vp, vp],
     "mmvae_gather_rows": [vp, i32, vp, i32, i64, vp],
+    "mmvae_rows_to_bf16": [vp, i32, i64, vp, i64, i32, i32, vp],
     "mmvae_sigmoid_bwd": [i32, i32, vp, i64, vp, i64, vp, i32, i64, vp],
     "mmvae_scale_if_needed": [vp, i32, i64, vp, vp],
     "mmvae_scale_many": [C.POINTER(ScaleItem), i32, vp, vp],

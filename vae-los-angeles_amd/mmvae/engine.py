@@ -109,12 +109,20 @@ GLOBAL_NOISE = NoiseSource()
 # --------------------------------------------------------------------------------------------
 # helpers
 # --------------------------------------------------------------------------------------------
-def _check_input(x, name, cols):
+def _check_input(x, name, cols, prec):
+    """The operand of a first-layer GEMM.  bf16 inputs ("bf16 storage"): in bf16 mode a matrix in the padded-row
+    layout (ops.is_bf16_rows; what mmvae.to_bf16_rows returns) is used as it is -- the forward GEMM's A, the dW GEMM's Q, the
+    reconstruction loss's target, no copy; any other bf16 matrix is converted into that layout once per call (the slow path: one
+    mmvae_rows_to_bf16 launch and a copy of the input).  In fp32 mode a bf16 input is widened to fp32 (exact)."""
     if x.dim() != 2 or x.shape[1] != cols:
         raise RuntimeError(f"{name}: expected shape (B, {cols}), got {tuple(x.shape)}")
     if not x.is_cuda:
         raise RuntimeError(f"{name}: the MI355X path needs CUDA/HIP tensors (got {x.device}); there is no CPU fallback")
-    if x.dtype not in (torch.float32, torch.bfloat16):
+    if x.dtype == torch.bfloat16:
+        if prec != PREC_BF16:
+            return x.float()
+        return x if ops.is_bf16_rows(x) else ops.to_bf16_rows(x)
+    if x.dtype != torch.float32:
         x = x.float()
     if x.stride(1) != 1:
         x = x.contiguous()
@@ -346,7 +354,7 @@ class DecoderMLP:
         return prec == ops.PREC_BF16 and len(self.pl) >= 2 and self.pl[-1].K > 64
 
     def forward(self, prec, z, fused_loss=None, first=None):
-        """fused_loss = (target fp32 [B][N], one-element float64 accumulator): the last layer does not store its output; its GEMM
+        """fused_loss = (target fp32 or bf16 [B][N], one-element float64 accumulator): the last layer does not store its output; its GEMM
         epilogue adds the reconstruction loss (sum-MSE, or sum-BCE behind the final Sigmoid: losses.py:31,34) to the accumulator and
         writes the bf16 gradient w.r.t. the pre-activation output.  Returns (gradient, acts) then instead of (output, acts).
         first: output of layer 0 computed elsewhere (VAEGraph's merged first layers of all decoders), a [B][N0] column slice."""
@@ -363,8 +371,11 @@ class DecoderMLP:
             last = j == len(self.pl) - 1
             if last and fused_loss is not None:
                 target, acc = fused_loss
-                if tuple(target.shape) != (B, pl.N) or target.dtype != torch.float32 or target.stride(1) != 1:
-                    raise ValueError(f"fused reconstruction loss: target must be fp32 [{B}, {pl.N}], got {tuple(target.shape)} {target.dtype}")
+                # fp32, or bf16 storage (padded bf16 rows read in the widest pieces; any bf16 rows are accepted by the kernel)
+                if tuple(target.shape) != (B, pl.N) or target.dtype not in (torch.float32, torch.bfloat16) or target.stride(1) != 1 \
+                        or not target.is_cuda:
+                    raise ValueError(f"fused reconstruction loss: target must be fp32 or bf16 [{B}, {pl.N}] with unit inner stride, "
+                                     f"got {tuple(target.shape)} {target.dtype}")
                 out = torch.empty(B, ceil_to(pl.N, 8), dtype=adt, device=dev)
                 ops.gemm_nt(prec, h, pl.w, pl.N, pl.K, out, bias=pl.bias, epilogue=ops.EPI_LOSS_BCE_LOGIT if self.final_sigmoid else ops.EPI_LOSS_MSE,
                             h=target, loss_sum=acc, tag=f"{self.name}.L{j}.fwd")
@@ -511,11 +522,11 @@ class VAEGraph:
                 saved["loss_ws"] = (packed[nst], packed[nst + 1])
                 saved["grad_pack"] = packed[nst + 2:]
         if xa is not None:
-            xa = _check_input(xa, "a", self.enc_a.in_dim)
+            xa = _check_input(xa, "a", self.enc_a.in_dim, prec)
             heads_a, saved["enc_a"] = self.enc_a.forward(prec, xa, train, masks[:len(widths_a)] if train else None,
                                                          st_all[:len(widths_a)] if train else None, want_bwd=want_bwd)
         if xb is not None:
-            xb = _check_input(xb.reshape(xb.shape[0], -1), "b", self.enc_b.in_dim)     # encoders.py:44 view
+            xb = _check_input(xb.reshape(xb.shape[0], -1), "b", self.enc_b.in_dim, prec)     # encoders.py:44 view
             heads_b, saved["enc_b"] = self.enc_b.forward(prec, xb, train, masks[len(widths_a):] if train else None,
                                                          st_all[len(widths_a):] if train else None, want_bwd=want_bwd)
         if site is not None:

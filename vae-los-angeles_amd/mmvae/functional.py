@@ -240,7 +240,10 @@ def _fused_loss(terms, beta, gamma, class_weights=None, unit_grad=False, beta_ga
 
     def prep(x):
         return None if x is None else (x if (x.dtype == torch.float32 and x.stride(-1) == 1) else x.float().contiguous())
-    ra_, a_, rb_, b_, lg_, mu_, lv_ = (prep(ra), prep(a), prep(rb), prep(b), prep(lg), prep(mu), prep(lv))
+
+    def prep_target(x):         # bf16 targets (bf16 storage) are read as they are: the kernel widens them on load
+        return x if (x is not None and x.dtype == torch.bfloat16 and x.stride(-1) == 1) else prep(x)
+    ra_, a_, rb_, b_, lg_, mu_, lv_ = (prep(ra), prep_target(a), prep(rb), prep_target(b), prep(lg), prep(mu), prep(lv))
     if mu_ is not None:
         mu_, lv_ = mu_.contiguous(), lv_.contiguous()
     if fused is not None:
@@ -391,7 +394,7 @@ class EncoderMLPFn(torch.autograd.Function):
     def forward(ctx, rt, prec, train, noise, x, *params):
         from .engine import _check_input
         ctx.set_materialize_grads(False)
-        x = _check_input(x.reshape(x.shape[0], -1), "x", rt.block.in_dim)
+        x = _check_input(x.reshape(x.shape[0], -1), "x", rt.block.in_dim, prec)
         rt.ensure(prec, x.device)
         masks = noise.draw(x.shape[0], rt.block.widths(), None, x.device)[0] if train else None
         heads, saved = rt.block.forward(prec, x, train, masks)

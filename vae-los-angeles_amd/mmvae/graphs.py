@@ -35,7 +35,9 @@ class GraphedTrainStep:
              "dna2rna":    model(dna=b, site=) + dna2rna_loss(recon_rna, a, ..)  (train_dna2rna.py:86-92)
              "rna2dna":    model(rna=a, site=) + rna2dna_loss(recon_dna, b, ..)  (train_rna2dna.py, same lines)
            dataset=(A, B, SITE) device-resident full tensors + batch_size: the static batch buffers are owned here and every step
-           begins with ONE gather launch through `self.index` (int64 (batch_size,)); call `set_indices(idx)` before a step."""
+           begins with ONE gather launch through `self.index` (int64 (batch_size,)); call `set_indices(idx)` before a step.
+           A / B may be in bf16 storage (mmvae.to_bf16_rows): the static buffers then get the same padded-row layout and the gather
+           moves whole padded rows.  The static-buffer form (a=, b=) takes such buffers too."""
         if kind not in self.KINDS:
             raise ValueError(f"kind must be one of {self.KINDS}")
         self.kind = kind
@@ -47,8 +49,8 @@ class GraphedTrainStep:
             if not dA.is_cuda:
                 raise RuntimeError("GraphedTrainStep needs CUDA/HIP tensors; there is no CPU fallback")
             dev = dA.device
-            a = torch.empty((batch_size,) + tuple(dA.shape[1:]), dtype=dA.dtype, device=dev)
-            b = torch.empty((batch_size,) + tuple(dB.shape[1:]), dtype=dB.dtype, device=dev)
+            a, b = (ops.zeros_bf16_rows(batch_size, t.shape[1], dev) if ops.is_bf16_rows(t)
+                    else torch.empty((batch_size,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev) for t in (dA, dB))
             site = torch.empty(batch_size, dtype=torch.int64, device=dev)
             self.index = torch.arange(batch_size, dtype=torch.int64, device=dev)
         if not a.is_cuda:

@@ -122,6 +122,57 @@ def _ld(t):
 
 
 # --------------------------------------------------------------------------------------------
+# inputs in bf16 storage ("padded bf16 rows", include/mmvae_hip.h: mmvae_rows_to_bf16)
+# --------------------------------------------------------------------------------------------
+def is_bf16_rows(t):
+    """t is a (B, F) bf16 device matrix in the padded-row layout: unit inner stride, leading dimension a multiple of 8 elements,
+    16-byte aligned base.  (The pad columns F .. ld-1 must hold zeros; that is the producer's promise -- to_bf16_rows keeps it.)"""
+    return (t.dtype == torch.bfloat16 and t.dim() == 2 and t.is_cuda and t.shape[0] > 0 and t.stride(1) == 1 and _ld(t) % 8 == 0
+            and _ld(t) >= t.shape[1] and t.data_ptr() % 16 == 0)
+
+
+def rows_to_bf16(src, dst):
+    """dst (a padded-bf16-rows view, see is_bf16_rows) <- bf16(src) with the pad columns zeroed, ONE launch (mmvae_rows_to_bf16).
+    src: fp32 or bf16 (B, F) with unit inner stride and any row stride; rounding is bit-identical to torch's .to(torch.bfloat16)."""
+    _mat(src, "src"); _mat(dst, "dst")
+    if tuple(src.shape) != tuple(dst.shape) or not is_bf16_rows(dst):
+        raise ValueError(f"rows_to_bf16: {tuple(src.shape)} {src.dtype} -> {tuple(dst.shape)} {dst.dtype} / {dst.stride()}")
+    B, F = src.shape
+    ld = _ld(dst)
+    if dst.untyped_storage().nbytes() < dst.storage_offset() * 2 + B * ld * 2:
+        raise ValueError("rows_to_bf16: dst must own whole padded rows (B x ld elements)")
+    with probe_span("rows_to_bf16", B * F * src.element_size() + B * ld * 2):
+        L.check(L.load().mmvae_rows_to_bf16(src.data_ptr(), _dt(src), _ld(src), dst.data_ptr(), ld, B, F, _stream()), "mmvae_rows_to_bf16")
+    return dst
+
+
+def zeros_bf16_rows(B, F, device):
+    """A zeroed (B, F) view of a (B, ceil8(F)) bf16 buffer: a static batch buffer in the padded-row layout."""
+    return torch.zeros(B, ceil_to(F, 8), dtype=torch.bfloat16, device=device)[:, :F]
+
+
+def to_bf16_rows(x):
+    """(N, F) fp32 or bf16 device tensor -> a NEW (N, F) bf16 view of an (N, ceil8(F)) buffer in the padded-row layout, pads zeroed,
+    values rounded as x.to(torch.bfloat16).  Convert a dataset once and hand it to the model / GraphedTrainStep(dataset=...): the
+    first-layer GEMMs, their dW GEMMs and the reconstruction losses then read 2 bytes per element instead of 4."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        dev = x.device if isinstance(x, torch.Tensor) else type(x).__name__
+        raise RuntimeError(f"to_bf16_rows: the MI355X path needs CUDA/HIP tensors (got {dev}); there is no CPU fallback")
+    if x.dim() != 2 or x.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"to_bf16_rows: need a 2-D fp32 or bf16 tensor, got {tuple(x.shape)} {x.dtype}")
+    if x.stride(1) != 1:
+        x = x.contiguous()
+    N, F = x.shape
+    out = torch.empty(N, ceil_to(F, 8), dtype=torch.bfloat16, device=x.device)[:, :F]
+    if N == 0 or F == 0:
+        return out
+    if _STREAM_OVERRIDE is not None:        # inside the engine's pinned span
+        return rows_to_bf16(x, out)
+    with pinned_stream():
+        return rows_to_bf16(x, out)
+
+
+# --------------------------------------------------------------------------------------------
 # prepared weights
 # --------------------------------------------------------------------------------------------
 class PreparedLinear:
@@ -209,7 +260,8 @@ def gemm_nt(prec, a, w_lp, N, K, out, *, bias=None, act=ACT_NONE, accumulate=Fal
     """out[M,N] = epi( pro(a)[M,K] @ W[N,K]^T ).  prologue = (scale, shift, mask|None, inv_keep);
     bn = (scale, shift, mean, rstd, mask|None, inv_keep) for EPI_BN_BWD (out=None, stats given:
     statistics phase; out and bn_coef given: apply phase).  stats: zeroed float64 [2][N] accumulator.
-    EPI_LOSS_MSE / EPI_LOSS_BCE_LOGIT: h = fp32 target, out = bf16 gradient, loss_sum = one-element float64 view that is added to."""
+    EPI_LOSS_MSE / EPI_LOSS_BCE_LOGIT: h = fp32 or bf16 target (rows 2-byte aligned; padded bf16 rows give the widest loads),
+    out = bf16 gradient, loss_sum = one-element float64 view that is added to."""
     _mat(a, "a"); _mat(w_lp, "w")
     if out is not None:
         _mat(out, "out")
@@ -244,8 +296,8 @@ def gemm_nt(prec, a, w_lp, N, K, out, *, bias=None, act=ACT_NONE, accumulate=Fal
         assert stats.dtype == torch.float64 and stats.shape[0] == 2 and stats.shape[1] >= N and stats.stride(1) == 1
         g.stat1, g.stat2 = stats[0].data_ptr(), stats[1].data_ptr()
     if loss_sum is not None:
-        assert loss_sum.dtype == torch.float64 and h is not None and h.dtype == torch.float32
-        g.stat1 = loss_sum.data_ptr()
+        assert loss_sum.dtype == torch.float64 and h is not None and h.dtype in (torch.float32, torch.bfloat16)
+        g.stat1, g.h_dtype = loss_sum.data_ptr(), _dt(h)
     t0 = PROBE.begin() if (PROBE is not None and PROBE.wants(tag)) else None
     L.check(L.load().mmvae_gemm_nt(C.byref(g), _stream()), "mmvae_gemm_nt")
     if t0 is not None:
@@ -430,10 +482,10 @@ def vae_loss(B, *, recon_a=None, a=None, recon_b=None, b=None, logits=None, site
     float32[2] = {beta, gamma} that overrides the by-value hyper-parameters (hipGraph replays follow the beta warm-up)."""
     x = L.LossArgs()
     x.B = B
-    if recon_a is not None:
-        x.A, x.recon_a, x.a, x.ld_ra, x.ld_a = recon_a.shape[1], recon_a.data_ptr(), a.data_ptr(), _ld(recon_a), _ld(a)
+    if recon_a is not None:                 # targets a / b: fp32 or bf16 (any row stride)
+        x.A, x.recon_a, x.a, x.ld_ra, x.ld_a, x.a_dtype = recon_a.shape[1], recon_a.data_ptr(), a.data_ptr(), _ld(recon_a), _ld(a), _dt(a)
     if recon_b is not None:
-        x.D, x.recon_b, x.b, x.ld_rb, x.ld_b = recon_b.shape[1], recon_b.data_ptr(), b.data_ptr(), _ld(recon_b), _ld(b)
+        x.D, x.recon_b, x.b, x.ld_rb, x.ld_b, x.b_dtype = recon_b.shape[1], recon_b.data_ptr(), b.data_ptr(), _ld(recon_b), _ld(b), _dt(b)
     if logits is not None:
         x.S, x.logits, x.ld_logits, x.site, x.class_weights = logits.shape[1], logits.data_ptr(), _ld(logits), site.data_ptr(), _p(class_weights)
     if mu is not None:
@@ -451,9 +503,9 @@ def vae_loss(B, *, recon_a=None, a=None, recon_b=None, b=None, logits=None, site
 
     def nbytes():
         n = 0
-        for pred, g in ((recon_a, g_a), (recon_b, g_b), (logits, g_c)):
+        for pred, tgt, g in ((recon_a, a, g_a), (recon_b, b, g_b), (logits, None, g_c)):
             if pred is not None:
-                n += 2 * B * pred.shape[1] * 4 + (0 if g is None else B * pred.shape[1] * g.element_size())
+                n += B * pred.shape[1] * (4 + (4 if tgt is None else tgt.element_size())) + (0 if g is None else B * pred.shape[1] * g.element_size())
         if mu is not None:
             n += B * mu.shape[1] * 4 * (2 + (g_mu is not None) + (g_lv is not None))
         return n
@@ -509,19 +561,35 @@ def counter_add(counter, inc):
     L.check(L.load().mmvae_counter_add(counter.data_ptr(), inc, _stream()), "mmvae_counter_add")
 
 
+def _gather_row(t):
+    """(row stride in bytes, bytes to move per row) of a gather operand: contiguous, or a (N, F) row-strided view with unit inner
+    stride -- padded bf16 rows move WHOLE padded rows (their pads are zeros on both sides), other views their F elements."""
+    es = t.element_size()
+    if t.is_contiguous():
+        n = t[0].numel() * es if t.dim() > 1 else es
+        return n, n
+    if t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1]:
+        if is_bf16_rows(t) and t.untyped_storage().nbytes() >= (t.storage_offset() + t.shape[0] * t.stride(0)) * es:
+            return t.stride(0) * es, ceil_to(t.shape[1], 8) * es
+        return t.stride(0) * es, t.shape[1] * es
+    raise ValueError(f"gather_rows: need contiguous tensors or (N, F) row-strided views, got {tuple(t.shape)} / {t.stride()}")
+
+
 def gather_rows(pairs, idx, src_rows):
     """pairs: [(src (N, ...) row-major, dst (B, ...))]: dst[i] = src[idx[i]] for every pair in ONE launch (idx: int64 (B,) on the
-    device).  The minibatch assembly of a device-resident dataset (reference: Dataset.__getitem__ + default collate per sample)."""
+    device).  The minibatch assembly of a device-resident dataset (reference: Dataset.__getitem__ + default collate per sample).
+    2-D operands may be row-strided views (stride(1) == 1); a padded-bf16-rows pair copies whole padded rows, so the pads stay zero."""
     items = (L.GatherItem * len(pairs))()
     B = idx.shape[0]
     nbytes = 0
     for j, (src, dst) in enumerate(pairs):
         if src.dtype != dst.dtype or src.shape[1:] != dst.shape[1:] or dst.shape[0] != B or src.shape[0] != src_rows:
             raise ValueError(f"gather_rows: pair {j}: {tuple(src.shape)} {src.dtype} -> {tuple(dst.shape)} {dst.dtype}")
-        if not (src.is_cuda and dst.is_cuda and src.is_contiguous() and dst.is_contiguous()):
-            raise ValueError("gather_rows needs contiguous device tensors")
-        row = src[0].numel() * src.element_size()
-        items[j] = L.GatherItem(src.data_ptr(), dst.data_ptr(), row, row, row, 0)
+        if not (src.is_cuda and dst.is_cuda):
+            raise ValueError("gather_rows needs device tensors")
+        (s_ld, s_row), (d_ld, d_row) = _gather_row(src), _gather_row(dst)
+        row = min(s_row, d_row)                 # a padded pair: both move ceil8(F) elements; a padded side with a plain one: F elements
+        items[j] = L.GatherItem(src.data_ptr(), dst.data_ptr(), s_ld, d_ld, row, 0)
         nbytes += 2 * B * row
     if idx.dtype != torch.int64 or not idx.is_cuda or not idx.is_contiguous():
         raise ValueError("gather_rows: idx must be a contiguous int64 device tensor")

@@ -74,6 +74,9 @@ def build_parser(kind):
     ap.add_argument("--batch-size", type=int, default=4096, help="rows per GPU")
     ap.add_argument("--epochs", type=int, default=Config.NUM_EPOCHS)
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32"])
+    ap.add_argument("--input-dtype", default="fp32", choices=["fp32", "bf16"],
+                    help="storage of the device-resident RNA / DNA matrices: bf16 converts them ONCE (mmvae.to_bf16_rows, padded bf16 rows); "
+                         "the first-layer GEMMs, their dW GEMMs and the reconstruction losses then read 2 bytes per element")
     ap.add_argument("--checkpoint-dir", default=Config.CHECKPOINT_DIR)
     ap.add_argument("--resume", default=None, help="training state written by --save-state (model + optimiser + scheduler + noise)")
     ap.add_argument("--save-state", default=None, help="write a resumable training state here after every epoch")
@@ -145,6 +148,10 @@ def run(kind, argv=None):
     lo, hi = parallel.shard_rows(train_idx.numel(), rank, world, equal=True)   # equal shards: every rank runs the same number of steps
     tr = [t[train_idx[lo:hi]].to(dev).contiguous() for t in (tpm, beta_v, site)]
     va = [t[val_idx].to(dev).contiguous() for t in (tpm, beta_v, site)]
+    if args.input_dtype == "bf16":                                              # bf16 storage: one conversion per run, not per step
+        from mmvae import to_bf16_rows
+        tr[:2] = [to_bf16_rows(t) for t in tr[:2]]
+        va[:2] = [to_bf16_rows(t) for t in va[:2]]
     class_weights = balanced_class_weights(site[train_idx], args.n_sites).to(dev) if kind == "multimodal" else None
     B = args.batch_size
     n_train = tr[0].shape[0]
@@ -169,7 +176,7 @@ def run(kind, argv=None):
             print(f"Resumed from {args.resume}: epoch {start_epoch}, best validation loss {best_val:.2f}")
     os.makedirs(args.checkpoint_dir, exist_ok=True)
     if rank == 0:
-        print(f"Starting {KINDS[kind]['title']} training run: {run_id}  ({n_train} rows/rank x {world} rank(s), batch {B}, {args.precision})")
+        print(f"Starting {KINDS[kind]['title']} training run: {run_id}  ({n_train} rows/rank x {world} rank(s), batch {B}, {args.precision}, {args.input_dtype} inputs)")
 
     graphed = None
     if args.eager:
