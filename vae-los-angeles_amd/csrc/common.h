@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "mmvae_hip.h"
 
 namespace mm {
 
@@ -121,6 +122,97 @@ struct Philox {
         for (int i = 0; i < 4; ++i) out[i] = c[i];
     }
 };
+
+// ------------------------------------------------------------------------------------------
+// Host-side dispatch plumbing shared by the GEMM entry points
+// ------------------------------------------------------------------------------------------
+
+// Dispatch knobs, set through mmvae_set_tuning (tests flip them inside one process to compare the kernel forms on the same data)
+struct Tuning {
+    int nt_wide_min_m = 256 * 128;   // key 0: 128x256 NT tiles only when there are >= 256 row tiles
+    int nt2_on = 1;                  // key 2: the LDS-DMA NT generation (gemm_nt2.h) against the register-staged one
+    long split_bytes = 1L << 32;     // key 3 (log2, 0 = default): operands of at least this many bytes are processed in row blocks
+    long block_bytes = 1L << 31;     //   ... of this size; key 3 sets half the threshold
+    int tn_wide_on = 1;              // key 4: the wide-tile dW kernels (gemm_tn_wide.hip)
+    int bnbwd_stream = 1;            // key 6: BatchNorm-backward NT epilogue through LDS (gemm_nt2.h)
+    int relu_stream = 1;             // key 7: ReLU-mask NT epilogue through LDS (gemm_nt2.h)
+    int ntp_on = 1;                  // key 8: the wave-specialised NT kernel (gemm_ntp.h)
+    int ntp_min_m = 16384;           // key 9: below this a persistent 256-workgroup grid has < 1 tile per CU
+};
+inline Tuning g_tuning;
+
+// Returned by a form's dispatch when the problem is not one of its own: the caller goes on to the next form.  Distinct from every
+// launch status (hipError_t > 0) and argument error (MMVAE_ERR_* < 0).
+constexpr int NOT_TAKEN = 1 << 30;
+
+// Launches a kernel with more dynamic LDS than the default limit.  The attribute is set once per kernel (Kernel is the template
+// parameter, so kernels that share a parameter list keep separate flags) and retried until it succeeds.  Returns the launch status.
+template <auto Kernel, typename... Args>
+inline int launch_lds(dim3 grid, dim3 block, int lds, hipStream_t st, const Args&... args) {
+    static bool attr_done = false;
+    if (!attr_done) {
+        hipError_t e = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (e != hipSuccess) return (int)e;
+        attr_done = true;
+    }
+    hipLaunchKernelGGL(Kernel, grid, block, lds, st, args...);
+    return (int)hipGetLastError();
+}
+
+// The kernels address their operands with 32-bit offsets from a scalar base.  Operands of 4 GiB or more (the scaled omics widths:
+// 65 536 x 27 000 fp32 = 7 GB) are processed in row blocks: M rows whose largest operand row has row_bytes bytes.
+inline bool needs_row_blocks(long M, long row_bytes) { return M * row_bytes >= g_tuning.split_bytes; }
+
+// Calls block(r0, rows) for consecutive row blocks of M rows and stops at the first non-zero status.  A block is below the split
+// threshold, so an entry point that recurses into itself for a block ends after one level.
+template <typename F>
+inline int for_row_blocks(long M, long row_bytes, F&& block) {
+    long rows = g_tuning.block_bytes / row_bytes;
+    if (rows <= 0) return MMVAE_ERR_ARG;                    // before any block is enqueued
+    const long nblk = (M + rows - 1) / rows;                // equal blocks (65 536 rows -> 4 x 16 384, not 3 x 19 712 + 6 400: a short
+    long even = (M + nblk - 1) / nblk;                      // last block falls below the sizes the wide-tile kernels take)
+    if (even >= 256) even = (even + 255) & ~255L;
+    if (even <= rows) rows = even;
+    else if (rows >= 256) rows &= ~255L;
+    for (long r0 = 0; r0 < M; r0 += rows) {
+        const int rc = block(r0, (int)(M - r0 < rows ? M - r0 : rows));
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+// Batch split of a dW GEMM: the M rows go to nsplit workgroups of rps rows each, a whole number of MT-row batch steps.
+// want > 0 asks for about that many splits.  want <= 0 plans ONE resident round of wg_target workgroups over ntiles output tiles,
+// in a multiple of 8 splits (split z runs on XCD z % 8: every XCD gets the same share; a 520-block grid costs a whole extra round).
+// An automatic count, and an asked one when limit > 0, keeps at least 4 batch steps per split (every split adds its partial tile to
+// each output element) and at most `limit` splits.
+struct SplitPlan { int nsplit, rps; };
+inline SplitPlan plan_splits(int M, int MT, int want, int ntiles, int wg_target, int limit = 0) {
+    int nsplit = want;
+    if (want <= 0) {
+        nsplit = wg_target / ntiles;
+        if (nsplit >= 8) nsplit &= ~7;
+    }
+    if (want <= 0 || limit > 0) {
+        const int max_split = (M + 4 * MT - 1) / (4 * MT);
+        if (nsplit > max_split) nsplit = max_split;
+        if (limit > 0 && nsplit > limit) nsplit = limit;
+        if (nsplit < 1) nsplit = 1;
+    }
+    int rps = (M + nsplit - 1) / nsplit;
+    rps = (rps + MT - 1) / MT * MT;
+    return {(M + rps - 1) / rps, rps};
+}
+
+// Elements per vector load (4, 2 or 1) of an operand whose rows of n elements of esize bytes lie ld elements apart from p: the
+// widest that divides ld and n and to which p is aligned.  Used for fp32 operands with whatever alignment the caller's tensor has
+// (e.g. (B, 782): 8-byte rows).
+inline int vec_width(long ld, long n, const void* p, long esize = 4) {
+    const uintptr_t a = (uintptr_t)p;
+    if (ld % 4 == 0 && n % 4 == 0 && (a & (4 * esize - 1)) == 0) return 4;
+    if (ld % 2 == 0 && n % 2 == 0 && (a & (2 * esize - 1)) == 0) return 2;
+    return 1;
+}
 
 }  // namespace mm
 

@@ -273,49 +273,28 @@ extern "C" int mmvae_debug_stamps(unsigned long long* out8, int reset) {
 
 template <typename CT, typename Src, typename Epi, int WN>
 static int launch_nt_wn(const Src& src, const void* W, long ldw, int M, int N, int K, const Epi& epi, hipStream_t st) {
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)gemm_nt_kernel<CT, Src, Epi, WN>, hipFuncAttributeMaxDynamicSharedMemorySize, NtLds<WN>::TOTAL);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
     const int gx = (M + TILE - 1) / TILE, gy = (N + 64 * WN - 1) / (64 * WN);
     const int grid = ((gx + 7) / 8) * 8 * gy;
-    hipLaunchKernelGGL((gemm_nt_kernel<CT, Src, Epi, WN>), dim3(grid), dim3(128 * WN), NtLds<WN>::TOTAL, st,
-                       src, (const CT*)W, ldw, M, N, K, gx, gy, epi);
-    MM_CHECK_LAUNCH();
-    return 0;
+    return launch_lds<gemm_nt_kernel<CT, Src, Epi, WN>>(dim3(grid), dim3(128 * WN), NtLds<WN>::TOTAL, st,
+                                                        src, (const CT*)W, ldw, M, N, K, gx, gy, epi);
 }
 
-static int g_wide_min_m = 256 * 128;      // 128x256 tiles only when there are >= 256 row tiles (mmvae_set_tuning key 0)
-// kernel-generation switch (mmvae_set_tuning key 2): tests flip it inside one process to compare the register-staged and the
-// LDS-DMA generation on the same data
-static int g_nt2_on = 1;
-void tn_wide_enable(int on);             // gemm_tn_wide.hip (mmvae_set_tuning key 4)
-int ntp_dispatch(const mmvae_gemm_nt_args* a, hipStream_t st);      // gemm_ntp.hip: the wave-specialised kernel; 1 << 30 = not taken
-void ntp_set(int key, int value);        // mmvae_set_tuning keys 8 (on / off), 9 (minimum M)
-long g_block_bytes = 1L << 31;          // row-block size for operands of >= 4 GiB (mmvae_set_tuning key 3 sets log2; shared with gemm_tn.hip)
-long g_split_bytes = 1L << 32;          // operands of at least this many bytes are processed in row blocks
+int ntp_dispatch(const mmvae_gemm_nt_args* a, hipStream_t st);      // gemm_ntp.hip: the wave-specialised kernel, or NOT_TAKEN
 
 static inline bool nt_wide_ok(int M, int N) {
     // the prepared W has ceil128(N) rows: whole 256-column tiles only; one 8-wave workgroup per CU: at least 256 tiles (M >= 32768 at
     // N = 256; a 16 384-row block of a 512-wide layer qualifies too)
-    return N % 256 == 0 && ((long)M * (N / 256) >= (long)g_wide_min_m || M >= g_wide_min_m);
+    return N % 256 == 0 && ((long)M * (N / 256) >= (long)g_tuning.nt_wide_min_m || M >= g_tuning.nt_wide_min_m);
 }
-
-static int g_bnbwd_stream = 1;          // mmvae_set_tuning key 6
-static int g_relu_stream = 1;           // mmvae_set_tuning key 7
-template <typename T> struct IsPlainBf16 { static constexpr bool value = false; };
-template <> struct IsPlainBf16<SrcPlain<bf16, bf16, 8>> { static constexpr bool value = true; };
 
 template <typename CT, typename Src, typename Epi>
 static int launch_nt(const Src& src, const void* W, long ldw, int M, int N, int K, const Epi& epi, hipStream_t st) {
-    if constexpr (sizeof(CT) == 2 && IsPlainBf16<Src>::value) {
+    if constexpr (sizeof(CT) == 2 && is_plain_bf16<Src>) {
         // second-generation kernel (gemm_nt2.h): operands that go into the MFMA as they are, at least two K steps
         // ... and for epilogues without operands of their own: with a saved activation / keep mask to fetch, the epilogue's loads
         // queue behind the next tile's DMA and its stores in front of the next wait (one in-order vmcnt for everything): measured
         // 5-20 % SLOWER than the first generation there, 5-10 % faster on the plain store epilogues
-        if (g_nt2_on && K > 64 && !epi.accumulate_requested() && Epi::NEED == 0) {
+        if (g_tuning.nt2_on && K > 64 && !epi.accumulate_requested() && Epi::NEED == 0) {
             if (nt_wide_ok(M, N)) return launch_nt2<Epi, 4>(src.p, src.lda, W, ldw, M, N, K, epi, st);
             return launch_nt2<Epi, 2>(src.p, src.lda, W, ldw, M, N, K, epi, st);
         }
@@ -334,18 +313,11 @@ static int dispatch_epi(const mmvae_gemm_nt_args* a, const Src& src, hipStream_t
     switch (a->epilogue) {
     case MMVAE_EPI_STORE: {
         const bool stats = a->stat1 != nullptr || a->stat2 != nullptr;
-        if (a->c_dtype == MMVAE_F32) {
-            if (stats) { EpiStore<float, true> e{(float*)a->c, a->ldc, a->bias, a->act, a->accumulate, nullptr, 0, nullptr, 0, a->stat1, a->stat2};
-                         return launch_nt<CT>(src, a->w, a->ldw, a->M, a->N, a->K, e, st); }
-            EpiStore<float, false> e{(float*)a->c, a->ldc, a->bias, a->act, a->accumulate, nullptr, 0, nullptr, 0, nullptr, nullptr};
-            return launch_nt<CT>(src, a->w, a->ldw, a->M, a->N, a->K, e, st);
-        }
+        auto go = [&](const auto& e) { return launch_nt<CT>(src, a->w, a->ldw, a->M, a->N, a->K, e, st); };
+        if (a->c_dtype == MMVAE_F32) return stats ? go(epi_store<float, true>(a)) : go(epi_store<float, false>(a));
         if constexpr (sizeof(CT) == 2) {
             if (a->ldc % 8 || ((uintptr_t)a->c & 15)) return MMVAE_ERR_ARG;
-            if (stats) { EpiStore<bf16, true> e{(bf16*)a->c, a->ldc, a->bias, a->act, a->accumulate, nullptr, 0, nullptr, 0, a->stat1, a->stat2};
-                         return launch_nt<CT>(src, a->w, a->ldw, a->M, a->N, a->K, e, st); }
-            EpiStore<bf16, false> e{(bf16*)a->c, a->ldc, a->bias, a->act, a->accumulate, nullptr, 0, nullptr, 0, nullptr, nullptr};
-            return launch_nt<CT>(src, a->w, a->ldw, a->M, a->N, a->K, e, st);
+            return stats ? go(epi_store<bf16, true>(a)) : go(epi_store<bf16, false>(a));
         }
         return MMVAE_ERR_DTYPE;
     }
@@ -353,8 +325,8 @@ static int dispatch_epi(const mmvae_gemm_nt_args* a, const Src& src, hipStream_t
         if (a->h == nullptr) return MMVAE_ERR_ARG;
         if ((a->c_dtype == MMVAE_BF16) != (sizeof(LP) == 2)) return MMVAE_ERR_DTYPE;
         if (sizeof(LP) == 2 && (a->ldc % 8 || a->ldh % 8 || ((uintptr_t)a->c & 15) || ((uintptr_t)a->h & 15))) return MMVAE_ERR_ARG;
-        if constexpr (sizeof(CT) == 2 && IsPlainBf16<Src>::value) {
-            if (g_relu_stream && g_nt2_on && a->ldh % 4 == 0 && a->ldc % 4 == 0 && ((uintptr_t)a->h & 7) == 0 && ((uintptr_t)a->c & 7) == 0) {
+        if constexpr (sizeof(CT) == 2 && is_plain_bf16<Src>) {
+            if (g_tuning.relu_stream && g_tuning.nt2_on && a->ldh % 4 == 0 && a->ldc % 4 == 0 && ((uintptr_t)a->h & 7) == 0 && ((uintptr_t)a->c & 7) == 0) {
                 EpiReluMaskStream e{(bf16*)a->c, a->ldc, (const bf16*)a->h, a->ldh};
                 return launch_nt2<EpiReluMaskStream, 2>(src.p, src.lda, a->w, a->ldw, a->M, a->N, a->K, e, st);
             }
@@ -374,10 +346,10 @@ static int dispatch_epi(const mmvae_gemm_nt_args* a, const Src& src, hipStream_t
             if (a->bn_phase && (a->ldc % 8 || ((uintptr_t)a->c & 15))) return MMVAE_ERR_ARG;
             if (a->epi_mask && (a->N % 16 || a->ld_epi_mask % 16 || ((uintptr_t)a->epi_mask & 15))) return MMVAE_ERR_ARG;
         }
-        if constexpr (sizeof(CT) == 2 && IsPlainBf16<Src>::value) {
+        if constexpr (sizeof(CT) == 2 && is_plain_bf16<Src>) {
             // phase 2 (store d + statistics) on plain bf16 operands: row-coalesced LDS epilogue (gemm_nt2.h); a single K step is fine here,
             // this epilogue's kernel starts no DMA for the next tile before it is done
-            if (g_bnbwd_stream && g_nt2_on && a->bn_phase == 2 && a->ldh % 4 == 0 && a->ldc % 4 == 0 &&
+            if (g_tuning.bnbwd_stream && g_tuning.nt2_on && a->bn_phase == 2 && a->ldh % 4 == 0 && a->ldc % 4 == 0 &&
                 (!a->epi_mask || (a->ld_epi_mask % 4 == 0 && ((uintptr_t)a->epi_mask & 3) == 0)) && ((uintptr_t)a->h & 7) == 0 && ((uintptr_t)a->c & 7) == 0) {
                 EpiBnBwdStream e{(bf16*)a->c, a->ldc, (const bf16*)a->h, a->ldh, a->epi_mask, a->ld_epi_mask,
                                  a->bn_scale, a->bn_shift, a->bn_mean, a->bn_rstd, a->epi_inv_keep, a->stat1, a->stat2};
@@ -392,7 +364,7 @@ static int dispatch_epi(const mmvae_gemm_nt_args* a, const Src& src, hipStream_t
     case MMVAE_EPI_LOSS_MSE:
     case MMVAE_EPI_LOSS_BCE_LOGIT: {
         // reconstruction loss inside a decoder's last GEMM: bf16 mode, plain bf16 A, second-generation kernel, 128 x 128 tiles
-        if constexpr (sizeof(CT) == 2 && IsPlainBf16<Src>::value) {
+        if constexpr (sizeof(CT) == 2 && is_plain_bf16<Src>) {
             if (!a->h || !a->c || !a->stat1 || a->c_dtype != MMVAE_BF16 || a->accumulate || a->K <= 64) return MMVAE_ERR_ARG;
             // the target: fp32, or bf16 (h_dtype; a dataset kept as padded bf16 rows), rows aligned to its element size
             const bool h16 = a->h_dtype == MMVAE_BF16;
@@ -400,9 +372,7 @@ static int dispatch_epi(const mmvae_gemm_nt_args* a, const Src& src, hipStream_t
             const long hsz = h16 ? 2 : 4;
             if (a->ldc % 8 || ((uintptr_t)a->c & 15) || ((uintptr_t)a->h & (hsz - 1))) return MMVAE_ERR_ARG;
             if ((long)a->M * a->ldh * hsz >= (1L << 40)) return MMVAE_ERR_ARG;
-            const uintptr_t hp = (uintptr_t)a->h;
-            const int vt = (a->ldh % 4 == 0 && a->N % 4 == 0 && (hp & (4 * hsz - 1)) == 0) ? 4 :
-                           (a->ldh % 2 == 0 && a->N % 2 == 0 && (hp & (2 * hsz - 1)) == 0) ? 2 : 1;
+            const int vt = vec_width(a->ldh, a->N, a->h, hsz);      // the target's element size, not fp32's
             const bool mse = a->epilogue == MMVAE_EPI_LOSS_MSE;
 #define MM_LOSS_EPI(MODE, VT, TT) { EpiLoss<MODE, VT, TT> e{(bf16*)a->c, a->ldc, (const TT*)a->h, a->ldh, a->bias, a->stat1}; \
                                     return launch_nt2<EpiLoss<MODE, VT, TT>, 2>(src.p, src.lda, a->w, a->ldw, a->M, a->N, a->K, e, st); }
@@ -454,35 +424,27 @@ static int dispatch_src(const mmvae_gemm_nt_args* a, hipStream_t st) {
         }
         return MMVAE_ERR_DTYPE;
     }
-    // f32 source with whatever alignment the caller's tensor has (e.g. (B,782): 8-byte rows)
-    const uintptr_t p = (uintptr_t)a->a;
-    if (a->lda % 4 == 0 && a->K % 4 == 0 && (p & 15) == 0) {
-        SrcPlain<CT, float, 4> s{(const float*)a->a, a->lda, a->M, a->K};
-        return dispatch_epi<CT>(a, s, st);
-    }
-    if (a->lda % 2 == 0 && a->K % 2 == 0 && (p & 7) == 0) {
-        SrcPlain<CT, float, 2> s{(const float*)a->a, a->lda, a->M, a->K};
-        return dispatch_epi<CT>(a, s, st);
-    }
-    SrcPlain<CT, float, 1> s{(const float*)a->a, a->lda, a->M, a->K};
-    return dispatch_epi<CT>(a, s, st);
+    return with_src_f32<CT>(a->a, a->lda, a->M, a->K, [&](const auto& s) { return dispatch_epi<CT>(a, s, st); });
 }
 
 }  // namespace mm
 
 extern "C" int mmvae_set_tuning(int32_t key, int32_t value) {
-    if (key == 0) { mm::g_wide_min_m = value; return 0; }
-    if (key == 2) { mm::g_nt2_on = value; return 0; }
-    if (key == 3) {         // tests: force the row-block path at moderate sizes (value = log2 of the block bytes; 0 restores the default)
+    mm::Tuning& t = mm::g_tuning;
+    switch (key) {
+    case 0: t.nt_wide_min_m = value; return 0;
+    case 2: t.nt2_on = value; return 0;
+    case 3:                 // tests: force the row-block path at moderate sizes (value = log2 of the block bytes; 0 restores the default)
         if (value != 0 && (value < 17 || value > 32)) return MMVAE_ERR_ARG;
-        mm::g_split_bytes = value ? 1L << value : 1L << 32;
-        mm::g_block_bytes = mm::g_split_bytes / 2;
+        t.split_bytes = value ? 1L << value : mm::Tuning{}.split_bytes;
+        t.block_bytes = t.split_bytes / 2;
         return 0;
+    case 4: t.tn_wide_on = value; return 0;
+    case 6: t.bnbwd_stream = value; return 0;
+    case 7: t.relu_stream = value; return 0;
+    case 8: t.ntp_on = value; return 0;
+    case 9: t.ntp_min_m = value; return 0;
     }
-    if (key == 4) { mm::tn_wide_enable(value); return 0; }
-    if (key == 6) { mm::g_bnbwd_stream = value; return 0; }
-    if (key == 7) { mm::g_relu_stream = value; return 0; }
-    if (key == 8 || key == 9) { mm::ntp_set(key, value); return 0; }
     return MMVAE_ERR_ARG;
 }
 
@@ -490,43 +452,33 @@ extern "C" int mmvae_gemm_nt(const mmvae_gemm_nt_args* a, void* stream) {
     if (!a || !a->a || !a->w || (!a->c && !(a->epilogue == MMVAE_EPI_BN_BWD && a->bn_phase == 0))) return MMVAE_ERR_ARG;
     if (a->M <= 0 || a->N <= 0 || a->K <= 0) return MMVAE_ERR_ARG;
     if (a->ldw % 64 || ((uintptr_t)a->w & 15)) return MMVAE_ERR_ARG;
-    // The kernels address A, W and the prologue mask with 32-bit offsets from a scalar base.  Operands of 4 GiB or more (the
-    // scaled omics widths: 65 536 x 27 000 fp32 = 7 GB) are processed in row blocks -- rows are independent in this product,
-    // and the column statistics of the epilogues accumulate atomically across launches.
+    // The kernels address A, W and the prologue mask with 32-bit offsets: operands of 4 GiB or more are processed in row blocks --
+    // rows are independent in this product, and the column statistics of the epilogues accumulate atomically across launches.
     const long lim = 1L << 32;
     if (((long)a->N + 256) * a->ldw * 4 >= lim) return MMVAE_ERR_ARG;
     const long a_row = (long)a->lda * (a->a_dtype == MMVAE_BF16 ? 2 : 4);
     long row_bytes = a_row > (long)a->ld_pro_mask ? a_row : (long)a->ld_pro_mask;
     if (!mm::bn_fin_ok(a)) return MMVAE_ERR_ARG;
-    if ((long)a->M * row_bytes >= mm::g_split_bytes) {
+    if (mm::needs_row_blocks(a->M, row_bytes)) {
         // refused here, before any block is enqueued (mmvae_hip.h): pro_finalize -- every row block would update the running
         // statistics; pro_out -- a block the wave-specialised kernel does not take would refuse it after the earlier blocks ran
         if (a->pro_finalize || a->pro_out) return MMVAE_ERR_ARG;
-        long rows = mm::g_block_bytes / row_bytes;          // block < split threshold: the recursion below ends after one level
-        if (rows <= 0) return MMVAE_ERR_ARG;
-        const long nblk = (a->M + rows - 1) / rows;         // equal blocks (65 536 rows -> 4 x 16 384, not 3 x 19 712 + 6 400: a short
-        long even = (a->M + nblk - 1) / nblk;               // last block falls below the sizes the wide-tile kernels take)
-        if (even >= 256) even = (even + 255) & ~255L;
-        if (even <= rows) rows = even;
-        else if (rows >= 256) rows &= ~255L;
-        for (long r0 = 0; r0 < a->M; r0 += rows) {
+        // H is activation-typed, except for the loss epilogues, whose H is the target (fp32 or bf16: h_dtype)
+        const bool loss_epi = a->epilogue == MMVAE_EPI_LOSS_MSE || a->epilogue == MMVAE_EPI_LOSS_BCE_LOGIT;
+        const long hsz = loss_epi ? (a->h_dtype == MMVAE_BF16 ? 2 : 4) : (a->prec == MMVAE_PREC_BF16 ? 2 : 4);
+        return mm::for_row_blocks(a->M, row_bytes, [&](long r0, int rows) {
             mmvae_gemm_nt_args s = *a;
-            s.M = (int32_t)((a->M - r0 < rows) ? a->M - r0 : rows);
+            s.M = rows;
             s.a = (const char*)a->a + r0 * a_row;
             if (a->c) s.c = (char*)a->c + r0 * a->ldc * (a->c_dtype == MMVAE_BF16 ? 2 : 4);
-            // H is activation-typed, except for the loss epilogues, whose H is the target (fp32 or bf16: h_dtype)
-            const bool loss_epi = a->epilogue == MMVAE_EPI_LOSS_MSE || a->epilogue == MMVAE_EPI_LOSS_BCE_LOGIT;
-            const long hsz = loss_epi ? (a->h_dtype == MMVAE_BF16 ? 2 : 4) : (a->prec == MMVAE_PREC_BF16 ? 2 : 4);
             if (a->h) s.h = (const char*)a->h + r0 * a->ldh * hsz;
             if (a->pro_mask) s.pro_mask = a->pro_mask + r0 * a->ld_pro_mask;
             if (a->epi_mask) s.epi_mask = a->epi_mask + r0 * a->ld_epi_mask;
-            const int rc = mmvae_gemm_nt(&s, stream);
-            if (rc) return rc;
-        }
-        return 0;
+            return mmvae_gemm_nt(&s, stream);
+        });
     }
     hipStream_t st = (hipStream_t)stream;
-    { const int rc = mm::ntp_dispatch(a, st); if (rc != (1 << 30)) return rc; }
+    { const int rc = mm::ntp_dispatch(a, st); if (rc != mm::NOT_TAKEN) return rc; }
     if (a->pro_out) return MMVAE_ERR_ARG;              // only the wave-specialised kernel writes the operand after its prologue (mmvae_hip.h)
     if (a->prec == MMVAE_PREC_BF16) return mm::dispatch_src<mm::bf16>(a, st);
     if (a->prec == MMVAE_PREC_F32) return mm::dispatch_src<float>(a, st);

@@ -405,21 +405,12 @@ void gemm_nt2_kernel(const bf16* __restrict__ A, long lda, const bf16* __restric
 // workgroup keeps to one XCD's tile list.
 template <typename Epi, int WN>
 static int launch_nt2(const void* A, long lda, const void* W, long ldw, int M, int N, int K, const Epi& epi, hipStream_t st) {
-    typedef Nt2Lds<WN> LD;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)gemm_nt2_kernel<Epi, WN>, hipFuncAttributeMaxDynamicSharedMemorySize, LD::TOTAL);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
     const int gx = (M + TILE - 1) / TILE, gy = (N + 64 * WN - 1) / (64 * WN);
     const int ntiles = ((gx + 7) / 8) * 8 * gy;
     int grid = 256 * (WN == 2 ? 2 : 1);
     if (grid > ntiles) grid = ntiles;
-    hipLaunchKernelGGL((gemm_nt2_kernel<Epi, WN>), dim3(grid), dim3(128 * WN), LD::TOTAL, st,
-                       (const bf16*)A, lda, (const bf16*)W, ldw, M, N, K, gx, gy, epi);
-    MM_CHECK_LAUNCH();
-    return 0;
+    return launch_lds<gemm_nt2_kernel<Epi, WN>>(dim3(grid), dim3(128 * WN), Nt2Lds<WN>::TOTAL, st,
+                                                (const bf16*)A, lda, (const bf16*)W, ldw, M, N, K, gx, gy, epi);
 }
 
 }  // namespace mm

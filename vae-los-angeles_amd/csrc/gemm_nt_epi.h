@@ -53,6 +53,12 @@ struct EpiStore {               // C = act(acc + bias) (+ C) ; stats = (sum C, s
     }
 };
 
+// the plain-store epilogue of an mmvae_gemm_nt call (output type OT; with STATS the column statistics go to stat1 / stat2)
+template <typename OT, bool STATS>
+inline EpiStore<OT, STATS> epi_store(const mmvae_gemm_nt_args* a) {
+    return {(OT*)a->c, a->ldc, a->bias, a->act, a->accumulate, nullptr, 0, nullptr, 0, STATS ? a->stat1 : nullptr, STATS ? a->stat2 : nullptr};
+}
+
 template <typename OT, typename HT>
 struct EpiReluMask {            // dH = (H > 0) ? acc : 0
     static constexpr bool STATS = false;

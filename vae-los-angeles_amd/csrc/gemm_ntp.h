@@ -52,8 +52,6 @@ __device__ unsigned long long mm_ntp_stamps[24];
 #define NTP_ACC(i, d)
 #endif
 
-constexpr int NTP_SKIP = 1 << 30;        // ntp_dispatch: "not my problem", the caller goes on to the other kernels
-
 template <int V> struct IntC { static constexpr int value = V; };
 
 template <int NT_, int WC_> struct NtpCfg {
@@ -679,20 +677,12 @@ void gemm_ntp_kernel(const AT* __restrict__ A, long lda, const bf16* __restrict_
 
 template <typename Cfg, typename AT, typename Epi, typename Pro = NtpProNone>
 static int launch_ntp(const void* A, long lda, const void* W, long ldw, int M, int N, int K, const Epi& epi, hipStream_t st, const Pro& pro = Pro{}) {
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)gemm_ntp_kernel<Cfg, AT, Epi, Pro>, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::TOTAL);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
     const int gx = (M + Cfg::BM - 1) / Cfg::BM, gy = (N + Cfg::BN - 1) / Cfg::BN;
     const int ntiles = ((gx + 7) / 8) * 8 * gy;
     int grid = 256;                                                  // one 8-wave workgroup per CU
     if (grid > ntiles) grid = ntiles;
-    hipLaunchKernelGGL((gemm_ntp_kernel<Cfg, AT, Epi, Pro>), dim3(grid), dim3(64 * Cfg::NWAVES), Cfg::TOTAL, st,
-                       (const AT*)A, lda, (const bf16*)W, ldw, M, N, K, gx, gy, epi, pro);
-    MM_CHECK_LAUNCH();
-    return 0;
+    return launch_lds<gemm_ntp_kernel<Cfg, AT, Epi, Pro>>(dim3(grid), dim3(64 * Cfg::NWAVES), Cfg::TOTAL, st,
+                                                          (const AT*)A, lda, (const bf16*)W, ldw, M, N, K, gx, gy, epi, pro);
 }
 
 }  // namespace mm

@@ -86,6 +86,21 @@ struct SrcPlain {
     }
 };
 
+// bf16 rows that go into the MFMA as they are: the operand form the LDS-DMA kernels take
+template <typename S> inline constexpr bool is_plain_bf16 = false;
+template <> inline constexpr bool is_plain_bf16<SrcPlain<bf16, bf16, 8>> = true;
+
+// f(SrcPlain<CT, float, V>) for the fp32 operand p[M][K] (row stride ld), V = vec_width(ld, K, p)
+template <typename CT, typename F>
+static int with_src_f32(const void* p, long ld, int M, int K, F&& f) {
+    const float* q = (const float*)p;
+    switch (vec_width(ld, K, p)) {
+    case 4: return f(SrcPlain<CT, float, 4>{q, ld, M, K});
+    case 2: return f(SrcPlain<CT, float, 2>{q, ld, M, K});
+    }
+    return f(SrcPlain<CT, float, 1>{q, ld, M, K});
+}
+
 // A = dropout(relu(y * scale + shift)) where y is the previous layer's pre-BatchNorm output,
 // scale = gamma * rstd, shift = beta - mean * scale (per column, staged in LDS), and the keep
 // mask is a uint8 [M][ldm] tensor (1 = kept) or NULL (eval / p = 0).

@@ -414,8 +414,6 @@ void gemm_tn_kernel(PSrc ps, QSrc qs, float* __restrict__ dW, long ldw, float* _
     tn_body<CT, PSrc, QSrc, DMA, NG>(ps, qs, dW, ldw, db, M, N, K, ntk, ntiles, nsplit, rows_per_split, slab, (int)blockIdx.x, smem);
 }
 
-template <typename T> struct TnPlainBf16 { static constexpr bool value = false; };
-template <> struct TnPlainBf16<SrcPlain<bf16, bf16, 8>> { static constexpr bool value = true; };
 // DMA form: plain bf16 operands and every split a whole number of full batch steps
 static inline bool tn_dma_ok(int M, int MT) { return M % MT == 0; }
 
@@ -548,82 +546,45 @@ static int tn_reduce(const mmvae_gemm_tn_args* a, int nsplit, hipStream_t st) {
     return 0;
 }
 
-static void tn_split(int M, int N, int K, int MT, int nsplit_req, int& ntk, int& ntiles, int& nsplit, int& rps, int wg_target = 512) {
-    const int ntn = (N + TILE - 1) / TILE;
-    ntk = (K + TILE - 1) / TILE; ntiles = ntn * ntk;
-    nsplit = nsplit_req;
-    if (nsplit <= 0) {
-        // ONE resident round: at most 2 workgroups per CU (512) in total and -- because split z runs on XCD z % 8 --
-        // a multiple of 8 splits so that every XCD gets the same share (a 520-block grid costs a whole extra round).
-        // Every split adds one f32 atomic per output element; keep at least 4 m-tiles of work per workgroup.
-        nsplit = wg_target / ntiles;
-        if (nsplit >= 8) nsplit &= ~7;
-        int max_split = (M + 4 * MT - 1) / (4 * MT);
-        if (nsplit > max_split) nsplit = max_split;
-        if (nsplit < 1) nsplit = 1;
-    }
-    rps = (M + nsplit - 1) / nsplit;
-    rps = ((rps + MT - 1) / MT) * MT;
-    nsplit = (M + rps - 1) / rps;
+// 128 x 128 output tiles of a dW GEMM and its batch split (plan_splits; wg_target 512: at most 2 workgroups per CU in total)
+struct TnPlan { int ntk, ntiles, nsplit, rps; };
+static TnPlan tn_plan(int M, int N, int K, int MT, int want, int wg_target = 512, int limit = 0) {
+    const int ntk = (K + TILE - 1) / TILE, ntiles = ((N + TILE - 1) / TILE) * ntk;
+    const SplitPlan sp = plan_splits(M, MT, want, ntiles, wg_target, limit);
+    return {ntk, ntiles, sp.nsplit, sp.rps};
+}
+
+// one launch of a 128 x 128 tile form over the splits of plan p, then the slab reduce if the partial tiles went there
+template <auto Kernel, typename PSrc, typename QSrc>
+static int tn_go(const mmvae_gemm_tn_args* a, const PSrc& ps, const QSrc& qs, const TnPlan& p, int threads, int lds, hipStream_t st) {
+    const int grid = ((p.nsplit + 7) / 8) * 8 * p.ntiles;
+    float* slab = tn_use_slab(a, p.nsplit) ? a->slab : nullptr;
+    const int rc = launch_lds<Kernel>(dim3(grid), dim3(threads), lds, st, ps, qs, a->dw, a->lddw, a->db, a->M, a->N, a->K,
+                                      p.ntk, p.ntiles, p.nsplit, p.rps, slab);
+    if (rc) return rc;
+    return slab ? tn_reduce(a, p.nsplit, st) : 0;
 }
 
 template <typename CT, typename PSrc, typename QSrc>
 static int launch_tn(const mmvae_gemm_tn_args* a, const PSrc& ps, const QSrc& qs, hipStream_t st) {
     typedef TnGeom<CT> G;
-    int ntk, ntiles, nsplit, rps;
-    tn_split(a->M, a->N, a->K, G::MT, a->nsplit, ntk, ntiles, nsplit, rps);
-    const int grid = ((nsplit + 7) / 8) * 8 * ntiles;
-    float* slab = tn_use_slab(a, nsplit) ? a->slab : nullptr;
+    const TnPlan p = tn_plan(a->M, a->N, a->K, G::MT, a->nsplit);
     constexpr int LDS = 4 * G::MT * G::ROWB + 4096 + 4096;
-    if constexpr (sizeof(CT) == 2 && TnPlainBf16<PSrc>::value && TnPlainBf16<QSrc>::value) {
-        // Two wave groups (one 8-wave workgroup per CU, half the slab) when an automatic split fills the chip that way: whole
-        // multiples of 8 splits (XCD balance) on >= 7/8 of the CUs -- 8 or 7 tiles (512x256, 256x512, 782x128: 36-38 against 40-41 us
-        // with the reduce).  The 20 tiles of 572x512 would make 160 workgroups, or 240 with 12 splits of which the last four are
-        // shared by two XCDs each (tried: 69 against 64-65 us alone, the same inside the step).
-        bool two = false;
+    if constexpr (sizeof(CT) == 2 && is_plain_bf16<PSrc> && is_plain_bf16<QSrc>) {
         if (tn_dma_ok(a->M, G::MT)) {
-            tn_split(a->M, a->N, a->K, G::MT, a->nsplit, ntk, ntiles, nsplit, rps, 256);
-            two = a->nsplit <= 0 && nsplit % 8 == 0 && nsplit * ntiles >= 224;
-            if (!two) tn_split(a->M, a->N, a->K, G::MT, a->nsplit, ntk, ntiles, nsplit, rps);
-        }
-        if (two) {
-            const int grid2 = ((nsplit + 7) / 8) * 8 * ntiles;
-            float* slab2 = tn_use_slab(a, nsplit) ? a->slab : nullptr;
-            constexpr int LDS2 = 8 * G::MT * G::ROWB + 4096;          // four 64-row P + Q buffers
-            static bool attr_dma2 = false;
-            if (!attr_dma2) {
-                hipError_t e = hipFuncSetAttribute((const void*)gemm_tn_kernel<CT, PSrc, QSrc, true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS2);
-                if (e != hipSuccess) return (int)e;
-                attr_dma2 = true;
+            // Two wave groups (one 8-wave workgroup per CU, half the slab) when an automatic split fills the chip that way: whole
+            // multiples of 8 splits (XCD balance) on >= 7/8 of the CUs -- 8 or 7 tiles (512x256, 256x512, 782x128: 36-38 against 40-41 us
+            // with the reduce).  The 20 tiles of 572x512 would make 160 workgroups, or 240 with 12 splits of which the last four are
+            // shared by two XCDs each (tried: 69 against 64-65 us alone, the same inside the step).
+            const TnPlan p2 = tn_plan(a->M, a->N, a->K, G::MT, a->nsplit, 256);
+            if (a->nsplit <= 0 && p2.nsplit % 8 == 0 && p2.nsplit * p2.ntiles >= 224) {
+                constexpr int LDS2 = 8 * G::MT * G::ROWB + 4096;          // four 64-row P + Q buffers
+                return tn_go<gemm_tn_kernel<CT, PSrc, QSrc, true, 2>>(a, ps, qs, p2, NTHREADS * 2, LDS2, st);
             }
-            hipLaunchKernelGGL((gemm_tn_kernel<CT, PSrc, QSrc, true, 2>), dim3(grid2), dim3(NTHREADS * 2), LDS2, st, ps, qs,
-                               a->dw, a->lddw, a->db, a->M, a->N, a->K, ntk, ntiles, nsplit, rps, slab2);
-            MM_CHECK_LAUNCH();
-            return slab2 ? tn_reduce(a, nsplit, st) : 0;
-        }
-        if (tn_dma_ok(a->M, G::MT)) {
-            static bool attr_dma = false;
-            if (!attr_dma) {
-                hipError_t e = hipFuncSetAttribute((const void*)gemm_tn_kernel<CT, PSrc, QSrc, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-                if (e != hipSuccess) return (int)e;
-                attr_dma = true;
-            }
-            hipLaunchKernelGGL((gemm_tn_kernel<CT, PSrc, QSrc, true>), dim3(grid), dim3(NTHREADS), LDS, st, ps, qs,
-                               a->dw, a->lddw, a->db, a->M, a->N, a->K, ntk, ntiles, nsplit, rps, slab);
-            MM_CHECK_LAUNCH();
-            return slab ? tn_reduce(a, nsplit, st) : 0;
+            return tn_go<gemm_tn_kernel<CT, PSrc, QSrc, true>>(a, ps, qs, p, NTHREADS, LDS, st);
         }
     }
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)gemm_tn_kernel<CT, PSrc, QSrc, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
-    hipLaunchKernelGGL((gemm_tn_kernel<CT, PSrc, QSrc, false>), dim3(grid), dim3(NTHREADS), LDS, st, ps, qs,
-                       a->dw, a->lddw, a->db, a->M, a->N, a->K, ntk, ntiles, nsplit, rps, slab);
-    MM_CHECK_LAUNCH();
-    return slab ? tn_reduce(a, nsplit, st) : 0;
+    return tn_go<gemm_tn_kernel<CT, PSrc, QSrc, false>>(a, ps, qs, p, NTHREADS, LDS, st);
 }
 
 template <typename CT, typename PSrc>
@@ -644,11 +605,7 @@ static int tn_dispatch_q(const mmvae_gemm_tn_args* a, const PSrc& ps, hipStream_
         }
         return MMVAE_ERR_DTYPE;
     }
-    const uintptr_t p = (uintptr_t)a->q;
-    if (a->ldq % 4 == 0 && a->K % 4 == 0 && (p & 15) == 0) { SrcPlain<CT, float, 4> q{(const float*)a->q, a->ldq, a->M, a->K}; return launch_tn<CT>(a, ps, q, st); }
-    if (a->ldq % 2 == 0 && a->K % 2 == 0 && (p & 7) == 0) { SrcPlain<CT, float, 2> q{(const float*)a->q, a->ldq, a->M, a->K}; return launch_tn<CT>(a, ps, q, st); }
-    SrcPlain<CT, float, 1> q{(const float*)a->q, a->ldq, a->M, a->K};
-    return launch_tn<CT>(a, ps, q, st);
+    return with_src_f32<CT>(a->q, a->ldq, a->M, a->K, [&](const auto& q) { return launch_tn<CT>(a, ps, q, st); });
 }
 
 template <typename CT>
@@ -671,11 +628,7 @@ static int tn_dispatch_p(const mmvae_gemm_tn_args* a, hipStream_t st) {
         }
         return MMVAE_ERR_DTYPE;
     }
-    const uintptr_t pp = (uintptr_t)a->p;
-    if (a->ldp % 4 == 0 && a->N % 4 == 0 && (pp & 15) == 0) { SrcPlain<CT, float, 4> p{(const float*)a->p, a->ldp, a->M, a->N}; return tn_dispatch_q<CT>(a, p, st); }
-    if (a->ldp % 2 == 0 && a->N % 2 == 0 && (pp & 7) == 0) { SrcPlain<CT, float, 2> p{(const float*)a->p, a->ldp, a->M, a->N}; return tn_dispatch_q<CT>(a, p, st); }
-    SrcPlain<CT, float, 1> p{(const float*)a->p, a->ldp, a->M, a->N};
-    return tn_dispatch_q<CT>(a, p, st);
+    return with_src_f32<CT>(a->p, a->ldp, a->M, a->N, [&](const auto& p) { return tn_dispatch_q<CT>(a, p, st); });
 }
 
 // host side of the grouped launch: classify every problem; -1 = not groupable (the caller launches it alone)
@@ -715,12 +668,8 @@ static int launch_tn_group(const mmvae_gemm_tn_args* args, int n, hipStream_t st
         TnProblem& r = g.pr[i];
         r.combo = tn_group_combo<CT>(a);
         if (r.combo < 0) return MMVAE_ERR_ARG;
-        int want = a->nsplit > 0 ? a->nsplit : auto_split;
-        const int max_split = (a->M + 4 * G::MT - 1) / (4 * G::MT);
-        if (want > max_split) want = max_split;
-        if (want > MMVAE_TN_GROUP_SPLITS) want = MMVAE_TN_GROUP_SPLITS;
-        if (want < 1) want = 1;
-        tn_split(a->M, a->N, a->K, G::MT, want, r.ntk, r.ntiles, r.nsplit, r.rps);
+        const TnPlan p = tn_plan(a->M, a->N, a->K, G::MT, a->nsplit > 0 ? a->nsplit : auto_split, 512, MMVAE_TN_GROUP_SPLITS);
+        r.ntk = p.ntk; r.ntiles = p.ntiles; r.nsplit = p.nsplit; r.rps = p.rps;
         if ((long)r.nsplit * a->N * a->K > a->slab_elems) return MMVAE_ERR_ARG;
         r.M = a->M; r.N = a->N; r.K = a->K;
         r.dma = (r.combo == 1 && sizeof(CT) == 2 && tn_dma_ok(a->M, G::MT)) ? 1 : 0;
@@ -733,14 +682,8 @@ static int launch_tn_group(const mmvae_gemm_tn_args* args, int n, hipStream_t st
     for (int i = n; i <= MMVAE_TN_GROUP_MAX; ++i) rd.first[i] = elems;
     for (int i = n; i < MMVAE_TN_GROUP_MAX; ++i) g.pr[i].block0 = 1 << 30;
     constexpr int LDS = 4 * G::MT * G::ROWB + 4096 + 4096;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)gemm_tn_group_kernel<CT>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
-    hipLaunchKernelGGL((gemm_tn_group_kernel<CT>), dim3(block), dim3(NTHREADS), LDS, st, g);
-    MM_CHECK_LAUNCH();
+    const int rc = launch_lds<gemm_tn_group_kernel<CT>>(dim3(block), dim3(NTHREADS), LDS, st, g);
+    if (rc) return rc;
     hipLaunchKernelGGL(tn_group_reduce_kernel, dim3((elems + 255) / 256), dim3(256), 0, st, rd);
     MM_CHECK_LAUNCH();
     return 0;
@@ -766,45 +709,35 @@ extern "C" int mmvae_gemm_tn_group(const mmvae_gemm_tn_args* args, int32_t n, vo
 }
 
 namespace mm {
-extern long g_block_bytes, g_split_bytes;                       // gemm_nt.hip (mmvae_set_tuning key 3)
 int launch_tn_wide(const mmvae_gemm_tn_args* a, hipStream_t st, int* nsplit_out);      // gemm_tn_wide.hip
 }
 extern "C" int mmvae_gemm_tn(const mmvae_gemm_tn_args* a, void* stream) {
     if (!a || !a->p || !a->q || !a->dw) return MMVAE_ERR_ARG;
     if (a->M <= 0 || a->N <= 0 || a->K <= 0) return MMVAE_ERR_ARG;
-    // The operand sources address P, Q and the prologue mask with 32-bit offsets from a scalar base.  Operands of 4 GiB or more
-    // (scaled omics widths) go through in row blocks: the batch rows are the reduction index and dW / db are accumulated.
+    // The operand sources address P, Q and the prologue mask with 32-bit offsets: operands of 4 GiB or more go through in row
+    // blocks -- the batch rows are the reduction index and dW / db are accumulated.
     const long p_row = (long)a->ldp * (a->p_dtype == MMVAE_BF16 ? 2 : 4), q_row = (long)a->ldq * (a->q_dtype == MMVAE_BF16 ? 2 : 4);
     const long py_row = a->p_prologue ? (long)a->ld_py * (a->prec == MMVAE_PREC_BF16 ? 2 : 4) : 0;
     long row_bytes = p_row > q_row ? p_row : q_row;
     if (py_row > row_bytes) row_bytes = py_row;
     if ((long)a->ld_pro_mask > row_bytes) row_bytes = a->ld_pro_mask;
-    if ((long)a->M * row_bytes >= mm::g_split_bytes) {
+    if (mm::needs_row_blocks(a->M, row_bytes)) {
         if (a->p_prologue != MMVAE_PRO_NONE && !a->p_coef) return MMVAE_ERR_ARG;      // every block would add dgamma / dbeta again: finalise separately
-        long rows = mm::g_block_bytes / row_bytes;          // block < split threshold: the recursion below ends after one level
-        if (rows <= 0) return MMVAE_ERR_ARG;
-        const long nblk = (a->M + rows - 1) / rows;         // equal blocks (see mmvae_gemm_nt)
-        long even = (a->M + nblk - 1) / nblk;
-        if (even >= 256) even = (even + 255) & ~255L;
-        if (even <= rows) rows = even;
-        else if (rows >= 256) rows &= ~255L;
-        for (long r0 = 0; r0 < a->M; r0 += rows) {
+        return mm::for_row_blocks(a->M, row_bytes, [&](long r0, int rows) {
             mmvae_gemm_tn_args s = *a;
-            s.M = (int32_t)((a->M - r0 < rows) ? a->M - r0 : rows);
+            s.M = rows;
             s.p = (const char*)a->p + r0 * p_row;
             s.q = (const char*)a->q + r0 * q_row;
             if (a->p_y) s.p_y = (const char*)a->p_y + r0 * py_row;
             if (a->pro_mask) s.pro_mask = a->pro_mask + r0 * a->ld_pro_mask;
-            const int rc = mmvae_gemm_tn(&s, stream);
-            if (rc) return rc;
-        }
-        return 0;
+            return mmvae_gemm_tn(&s, stream);
+        });
     }
     hipStream_t st = (hipStream_t)stream;
     {   // the large weight gradients (first encoder layers, last decoder layer): wide tiles, gemm_tn_wide.hip
         int ns = 0;
         const int rc = mm::launch_tn_wide(a, st, &ns);
-        if (rc != -100) return rc ? rc : mm::tn_reduce(a, ns, st);
+        if (rc != mm::NOT_TAKEN) return rc ? rc : mm::tn_reduce(a, ns, st);
     }
     if (a->prec == MMVAE_PREC_BF16) return mm::tn_dispatch_p<mm::bf16>(a, st);
     if (a->prec == MMVAE_PREC_F32) return mm::tn_dispatch_p<float>(a, st);

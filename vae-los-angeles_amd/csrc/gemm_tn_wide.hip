@@ -520,16 +520,8 @@ template <class C, int PMODE, typename QT, int NSTAGE>
 static int tnw_dma_launch(TnwArgs& w, hipStream_t st) {
     constexpr bool QF = sizeof(QT) == 4;
     constexpr int LDS = NSTAGE * (C::MT * C::PROW * (PMODE ? 2 : 1) + C::MT * (QF ? C::KT * 4 : C::QROW));
-    static bool attr = false;
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)gemm_tnw_dma_kernel<C, PMODE, QT, NSTAGE>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) return (int)e;
-        attr = true;
-    }
     const int grid = w.linear ? w.nsplit * w.ntiles : ((w.nsplit + 7) / 8) * 8 * w.ntiles;
-    hipLaunchKernelGGL((gemm_tnw_dma_kernel<C, PMODE, QT, NSTAGE>), dim3(grid), dim3(512), LDS, st, w);
-    MM_CHECK_LAUNCH();
-    return 0;
+    return launch_lds<gemm_tnw_dma_kernel<C, PMODE, QT, NSTAGE>>(dim3(grid), dim3(512), LDS, st, w);
 }
 
 typedef TnwCfg<4, 4, 2, 9> CfgA;        // 256 x 288
@@ -537,26 +529,15 @@ typedef TnwCfg<2, 4, 4, 7> CfgB;        // 128 x 448
 
 template <class C, int PMODE, typename QT, int QVEC>
 static int tnw_launch(TnwArgs& w, hipStream_t st) {
-    static bool attr = false;
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)gemm_tnw_kernel<C, PMODE, QT, QVEC>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-        if (e != hipSuccess) return (int)e;
-        attr = true;
-    }
     const int grid = w.linear ? w.nsplit * w.ntiles : ((w.nsplit + 7) / 8) * 8 * w.ntiles;
-    hipLaunchKernelGGL((gemm_tnw_kernel<C, PMODE, QT, QVEC>), dim3(grid), dim3(512), C::LDS, st, w);
-    MM_CHECK_LAUNCH();
-    return 0;
+    return launch_lds<gemm_tnw_kernel<C, PMODE, QT, QVEC>>(dim3(grid), dim3(512), C::LDS, st, w);
 }
 
-static int g_tn_wide_on = 1;
-void tn_wide_enable(int on) { g_tn_wide_on = on; }
-
 // Returns 0 after launching the GEMM (the caller then runs the slab reduce over *nsplit_out splits), > 0 on a launch error,
-// TN_WIDE_NA when the problem is not one of the wide kernel's.
+// NOT_TAKEN when the problem is not one of the wide kernel's.
 int launch_tn_wide(const mmvae_gemm_tn_args* a, hipStream_t st, int* nsplit_out) {
-    constexpr int NA = -100;
-    if (!g_tn_wide_on || a->prec != MMVAE_PREC_BF16 || a->p_dtype != MMVAE_BF16 || a->q_prologue != MMVAE_PRO_NONE || a->nsplit > 0) return NA;
+    constexpr int NA = NOT_TAKEN;
+    if (!g_tuning.tn_wide_on || a->prec != MMVAE_PREC_BF16 || a->p_dtype != MMVAE_BF16 || a->q_prologue != MMVAE_PRO_NONE || a->nsplit > 0) return NA;
     if (a->M < 8192 || !a->slab || a->N < 128 || a->K < 256) return NA;
     const int pmode = a->p_prologue == MMVAE_PRO_BN_BWD_APPLY ? 1 : 0;
     if (a->p_prologue != MMVAE_PRO_NONE && !pmode) return NA;
@@ -564,11 +545,9 @@ int launch_tn_wide(const mmvae_gemm_tn_args* a, hipStream_t st, int* nsplit_out)
     const bool fin = pmode && !a->p_coef;                 // mmvae_bn_bwd_finalize folded in
     if (pmode && (!a->p_y || !a->p_mean || !a->p_rstd || a->ld_py % 8 || ((uintptr_t)a->p_y & 15) || a->N % 8)) return NA;
     if (fin && (!a->p_sum_d || !a->p_sum_dx || !a->p_gamma || !a->p_dgamma || !a->p_dbeta)) return NA;
-    int qkind;                                             // 0 bf16, 4 / 2: fp32 in vectors of 4 / 2
+    int qkind;                                             // 0 bf16, 4 / 2: fp32 in vectors of 4 / 2 (no form reads single floats)
     if (a->q_dtype == MMVAE_BF16) { if (a->ldq % 8 || ((uintptr_t)a->q & 15)) return NA; qkind = 0; }
-    else if (a->ldq % 4 == 0 && a->K % 4 == 0 && ((uintptr_t)a->q & 15) == 0) qkind = 4;
-    else if (a->ldq % 2 == 0 && a->K % 2 == 0 && ((uintptr_t)a->q & 7) == 0) qkind = 2;
-    else return NA;
+    else { qkind = vec_width(a->ldq, a->K, a->q); if (qkind == 1) return NA; }
     // instantiated combinations: an fp32 Q (the input batch of the first encoder layers) with a BatchNorm-corrected bf16 P (the bench
     // widths) or a plain bf16 P (very wide inputs, where the engine applies the correction in a pass of its own: hundreds of K tiles would
     // each redo it).  Plain bf16 x bf16 problems (last decoder layers) were measured on this kernel too (3-stage ring): 57-59 us against
@@ -587,14 +566,8 @@ int launch_tn_wide(const mmvae_gemm_tn_args* a, hipStream_t st, int* nsplit_out)
     w.ntk = (a->K + KT - 1) / KT;
     w.ntiles = w.ntk * ((a->N + NT - 1) / NT);
     if (w.ntiles > (pmode ? 32 : 4096)) return NA;         // corrected P: every K tile redoes the correction -- the 128 x 128 kernel's case
-    int nsplit = 256 / w.ntiles;                           // one workgroup per CU
-    if (nsplit >= 8) nsplit &= ~7;                         // whole XCD rounds
-    const int max_split = (a->M + 4 * 32 - 1) / (4 * 32);
-    if (nsplit > max_split) nsplit = max_split;
-    if (nsplit < 1) nsplit = 1;
-    int rps = (a->M + nsplit - 1) / nsplit;
-    rps = (rps + 31) / 32 * 32;
-    nsplit = (a->M + rps - 1) / rps;
+    const SplitPlan sp = plan_splits(a->M, 32, 0, w.ntiles, 256);      // 256: one workgroup per CU
+    const int nsplit = sp.nsplit, rps = sp.rps;
     if ((long)nsplit * a->N * a->K > a->slab_elems) return NA;
     if (pmode && nsplit < 2) return NA;
     w.nsplit = nsplit; w.rps = rps; w.linear = nsplit < 8 ? 1 : 0;
