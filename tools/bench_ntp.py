@@ -3,8 +3,6 @@
 B = 65 536, interleaved rounds in one process, inputs rotated over buffers that exceed the Infinity Cache."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if os.environ.get("ABL"):        # timing-only ablation library (tools/abl_ntp.sh): wrong results by construction
-    os.environ["MMVAE_LIB_PATH"] = os.path.join(ROOT, "vae-los-angeles_amd", "mmvae", f"libmmvae_{os.environ['ABL']}.so")
 sys.path[:0] = [os.path.join(ROOT, "vae-los-angeles_amd")]
 import torch
 from mmvae import ops, _lib
@@ -37,11 +35,11 @@ for name, N, K in (("EncoderB.L0.fwd", 512, 572), ("EncoderA.L0.fwd", 128, 782))
     byts = M * K * 4 + M * N * 2 + N * K * 2
     res = {0: [], 1: []}
     for r in range(int(os.environ.get("ROUNDS", 5))):
-        for on in ((1,) if os.environ.get("ABL") else (0, 1)):
+        for on in (0, 1):
             lib.mmvae_set_tuning(8, on)
             fn(0); torch.cuda.synchronize()
             res[on].append(timeit(fn))
     lib.mmvae_set_tuning(8, 1)
-    for on in ((1,) if os.environ.get("ABL") else (0, 1)):
+    for on in (0, 1):
         t = sorted(res[on])
         print(f"{name} ntp={on}: median {t[len(t) // 2]:.1f} us  min {t[0]:.1f} us  -> {byts / t[len(t) // 2] / 1e6:.2f} TB/s of {byts / 1e6:.0f} MB", flush=True)

@@ -1,10 +1,8 @@
 #!/usr/bin/env python3
 """EncoderB's second Linear forward (bf16 A through the BatchNorm + ReLU + Dropout prologue, N = 256, K = 512, B = 65 536) in isolation;
-ABL=<name> selects an experimental library built by tools/abl_ntp.sh.  SHAPE=plain: DecoderB.L1.fwd (plain bf16 A, ReLU, N = 512, K = 256)."""
+SHAPE=plain: DecoderB.L1.fwd (plain bf16 A, ReLU, N = 512, K = 256).  MMVAE_LIB_PATH selects an experimental library (make VARIANT=name)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if os.environ.get("ABL"):
-    os.environ["MMVAE_LIB_PATH"] = os.path.join(ROOT, "vae-los-angeles_amd", "mmvae", f"libmmvae_{os.environ['ABL']}.so")
 sys.path[:0] = [os.path.join(ROOT, "vae-los-angeles_amd")]
 import torch
 from mmvae import ops
@@ -24,4 +22,4 @@ for r in range(3):
     s.record()
     for i in range(12): fn(i)
     e.record(); torch.cuda.synchronize()
-    print(f"{'DecoderB.L1.fwd' if PLAIN else 'EncoderB.L1.fwd'} {os.environ.get('ABL', 'product')}: {s.elapsed_time(e) / 12 * 1e3:.1f} us", flush=True)
+    print(f"{'DecoderB.L1.fwd' if PLAIN else 'EncoderB.L1.fwd'} {os.environ.get('MMVAE_LIB_PATH', 'product')}: {s.elapsed_time(e) / 12 * 1e3:.1f} us", flush=True)

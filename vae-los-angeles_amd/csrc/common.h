@@ -124,6 +124,79 @@ struct Philox {
 };
 
 // ------------------------------------------------------------------------------------------
+// Cycle stamps: the diagnostic library only (make STAMP=1 -> libmmvae_stamp.so, read with tools/stamp.py KERNEL).  A kernel sums
+// cycle deltas per wave in st_acc[] (slot i of st_acc is slot i of its buffer) and a sample of its waves adds them to the buffer
+// with stamp_flush; mmvae_debug_stamps(kernel, out, n, reset) copies a buffer out.  In the product build every piece below is empty.
+//
+// Kernel ids and slot layouts ("phases" are cycles summed over the sampled waves' steps; "steps" the number of such steps):
+//   STAMP_NT   gemm_nt_kernel (gemm_nt.hip), every 16th workgroup's wave 0:  0 reads(s1) + mma(s0) issue, 1 stage (vmcnt wait +
+//              ds_write + drain), 2 barrier wait, 3 fetch + reads(s0) + mma(s1) issue, 4 K steps, 5 waves, 6 whole kernel,
+//              7 of slot 1: wait for the global loads, 8 before the first K step, 9 after the last one
+//   STAMP_NT2  gemm_nt2_kernel (gemm_nt2.h), every 16th workgroup's wave 0:  0 wait for the own DMA, 1 barrier wait, 2 DMA issue of
+//              the next step, 3 fragment reads + MFMA, 4 K steps, 5 waves, 6 whole kernel, 9 epilogues (7, 8 unused)
+//   STAMP_NTP  gemm_ntp_kernel (gemm_ntp.h), every 16th workgroup:  consumer wave 0: 0 barrier wait, 1 fragment reads + MFMA,
+//              2 epilogues, 3 K steps, 4 tiles, 5 whole kernel, 6 workgroups; producer wave 0, per K step: 8 barrier wait,
+//              9 wait for the set's loads, 10 v_cvt_pk (fp32 -> bf16), 11 ds_write issue, 12 W DMA issue, 13 A load issue,
+//              14 wait for W of the next step
+//   STAMP_TN   gemm_tn_kernel's body (gemm_tn.hip), every 8th workgroup's wave 0:  0 fragment step 0, 1 stage (vmcnt wait +
+//              ds_write), 2 fragment step 1 + fetch issue + drain, 3 barrier wait, 4 batch steps, 5 waves, 6 whole kernel,
+//              7 of slot 1: wait for the global loads, 8 before the first batch step, 9 after the last one
+//   STAMP_TNW  gemm_tnw_dma_kernel (gemm_tn_wide.hip), every 8th workgroup's wave 0:  0 wait for the own DMA, 1 barrier, 2 DMA
+//              issue, 3 fragments + MFMA, 4 batch steps, 5 workgroups, 6 whole kernel, 7 epilogue
+// ------------------------------------------------------------------------------------------
+enum StampKernel { STAMP_NT = 0, STAMP_NT2 = 1, STAMP_NTP = 2, STAMP_TN = 3, STAMP_TNW = 4 };
+constexpr int STAMP_SLOTS = 16;
+
+#ifdef MM_STAMP
+#define STAMP_T(x) unsigned long long x = __builtin_readcyclecounter()      // a timestamp
+#define STAMP_ADD(i, d) st_acc[i] += (d)                                    // add a delta to slot i
+#define STAMP_ONLY(...) __VA_ARGS__                                         // a statement of the stamp build
+#define UNSTAMPED(...)                                                      // a statement of the product build
+// A kernel's buffer, in the object that holds the kernel, and its host-side reader
+#define STAMP_BUFFER(name) \
+    __device__ unsigned long long stamps_##name[STAMP_SLOTS]; \
+    int stamp_read_##name(uint64_t* out, int n, int reset) { return stamp_copy(HIP_SYMBOL(stamps_##name), out, n, reset); }
+// The extern "C" entry point, in one object of the library
+#define STAMP_ENTRY() \
+    extern "C" int mmvae_debug_stamps(int32_t kernel, uint64_t* out, int32_t n, int32_t reset) { \
+        switch (kernel) { \
+        case mm::STAMP_NT: return mm::stamp_read_nt(out, n, reset); \
+        case mm::STAMP_NT2: return mm::stamp_read_nt2(out, n, reset); \
+        case mm::STAMP_NTP: return mm::stamp_read_ntp(out, n, reset); \
+        case mm::STAMP_TN: return mm::stamp_read_tn(out, n, reset); \
+        case mm::STAMP_TNW: return mm::stamp_read_tnw(out, n, reset); \
+        } \
+        return MMVAE_ERR_ARG; \
+    }
+
+template <int N>
+__device__ __forceinline__ void stamp_flush(unsigned long long* slots, const unsigned long long (&acc)[N]) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) atomicAdd(&slots[i], acc[i]);
+}
+// the first n slots of a buffer -> out; then zeroes the buffer if reset
+inline int stamp_copy(const void* sym, uint64_t* out, int n, int reset) {
+    if (n < 0 || n > STAMP_SLOTS) return MMVAE_ERR_ARG;
+    hipError_t e = hipMemcpyFromSymbol(out, sym, n * sizeof(uint64_t));
+    if (e != hipSuccess || !reset) return (int)e;
+    const uint64_t z[STAMP_SLOTS] = {};
+    return (int)hipMemcpyToSymbol(sym, z, sizeof(z));
+}
+int stamp_read_nt(uint64_t*, int, int);
+int stamp_read_nt2(uint64_t*, int, int);
+int stamp_read_ntp(uint64_t*, int, int);
+int stamp_read_tn(uint64_t*, int, int);
+int stamp_read_tnw(uint64_t*, int, int);
+#else
+#define STAMP_T(x)
+#define STAMP_ADD(i, d)
+#define STAMP_ONLY(...)
+#define UNSTAMPED(...) __VA_ARGS__
+#define STAMP_BUFFER(name)
+#define STAMP_ENTRY()
+#endif
+
+// ------------------------------------------------------------------------------------------
 // Host-side dispatch plumbing shared by the GEMM entry points
 // ------------------------------------------------------------------------------------------
 

@@ -20,12 +20,11 @@
 #include "mmvae_hip.h"
 #include "gemm_src.h"
 #include "gemm_nt_epi.h"
-#ifdef MM_STAMP
-namespace mm { __device__ unsigned long long mm_stamps[12]; }
-#endif
 #include "gemm_nt2.h"
 
 namespace mm {
+
+STAMP_BUFFER(nt)
 
 // ------------------------------------------------------------------------------------------
 // kernel
@@ -42,17 +41,7 @@ template <int WN> struct NtLds {
 
 // WN = 2: 128x128 tile, 4 waves, 2 workgroups per CU.  WN = 4: 128x256 tile, 8 waves, 1 workgroup per CU -- the A tile is
 // fetched once for 256 output columns, which halves the L2->CU operand ingest of the N = 256 / 512 layers.
-#ifdef MM_STAMP
-// Diagnostic build only (make STAMP=1 -> libmmvae_stamp.so, tools/stamp_nt.py): s_memtime stamps at the points of a K step
-// where the wave has drained lgkmcnt anyway, summed per wave and added to mm_stamps[] = {reads + mma0 issue, stage (vmcnt
-// wait + ds_write), barrier wait, fetch + reads + mma1 issue, K steps, waves, whole-kernel cycles summed over waves}.
-#define MM_T(x) const unsigned long long x = __builtin_readcyclecounter()
-#define MM_ACC(i, d) st_acc[i] += (d)
-#else
-#define MM_T(x)
-#define MM_ACC(i, d)
-#endif
-
+// Cycle stamps (STAMP_NT, common.h) sit at the points of a K step where the wave has drained lgkmcnt anyway.
 template <typename CT, typename Src, typename Epi, int WN>
 __global__ __launch_bounds__(128 * WN, 2)
 void gemm_nt_kernel(Src src, const CT* __restrict__ W, long ldw, int M, int N, int K, int gx, int gy, Epi epi)
@@ -73,10 +62,7 @@ void gemm_nt_kernel(Src src, const CT* __restrict__ W, long ldw, int M, int N, i
     const int rt = (slot / gy) * 8 + (L & 7);
     if (rt >= gx) return;
     const int row0 = rt * TILE, col0 = ct * BN;
-#ifdef MM_STAMP
-    unsigned long long st_acc[6] = {0, 0, 0, 0, 0, 0}, t_first = 0, t_last = 0;
-    MM_T(t_begin);
-#endif
+    STAMP_ONLY(unsigned long long st_acc[10] = {}, t_last = 0; STAMP_T(t_begin);)
 
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int wr = wid / WN, wc = wid % WN;
@@ -160,39 +146,26 @@ void gemm_nt_kernel(Src src, const CT* __restrict__ W, long ldw, int M, int N, i
     // 1256 -> 999 cycles per 128x128x64 step and CU for this loop skeleton (no-traffic floor 700, MFMA floor 560).
     constexpr int NMEM = A_PER + 4;                          // loads / LDS writes per lane and K step
     auto kstep = [&](auto& ra_n, auto& rb_n, int kt, int buf, bool has_next, bool do_fetch, int fetch_kt) {
-        MM_T(t0);
+        STAMP_T(t0);
         rd(f1a, f1b, buf, 1);
         mma(f0a, f0b);
-        MM_T(t1);
-#ifdef MM_STAMP
-        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");      // steady state: the register set about to be staged has landed
-        MM_T(t1b);
-        MM_ACC(5, t1b - t1);
-#endif
+        STAMP_T(t1);
+        STAMP_ONLY(asm volatile("s_waitcnt vmcnt(8)" ::: "memory"));      // steady state: the register set about to be staged has landed
+        STAMP_T(t1b);
+        STAMP_ADD(7, t1b - t1);
         if (has_next) stage(ra_n, rb_n, kt + 1, buf ^ 1);
-#ifndef MM_STAMP
-#pragma unroll
-        for (int j = 0; j < NMEM; ++j) { __builtin_amdgcn_sched_group_barrier(0x008, 16 / NMEM, 0); __builtin_amdgcn_sched_group_barrier(0x200, 1, 0); }
-#endif
-#ifdef MM_STAMP
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
-        MM_T(t2);
+        UNSTAMPED(_Pragma("unroll") for (int j = 0; j < NMEM; ++j) { __builtin_amdgcn_sched_group_barrier(0x008, 16 / NMEM, 0); __builtin_amdgcn_sched_group_barrier(0x200, 1, 0); })
+        STAMP_ONLY(asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"));
+        STAMP_T(t2);
         __syncthreads();
-        MM_T(t3);
+        STAMP_T(t3);
         if (do_fetch) fetch(ra_n, rb_n, fetch_kt);
         if (has_next) rd(f0a, f0b, buf ^ 1, 0);
         mma(f1a, f1b);
-#ifndef MM_STAMP
-#pragma unroll
-        for (int j = 0; j < NMEM; ++j) { __builtin_amdgcn_sched_group_barrier(0x008, 16 / NMEM, 0); __builtin_amdgcn_sched_group_barrier(0x020, 1, 0); }
-#endif
-        MM_T(t4);
-#ifdef MM_STAMP
-        if (st_acc[4] == 0) t_first = t0;
-        t_last = t4;
-#endif
-        MM_ACC(0, t1 - t0); MM_ACC(1, t2 - t1); MM_ACC(2, t3 - t2); MM_ACC(3, t4 - t3); MM_ACC(4, 1);
+        UNSTAMPED(_Pragma("unroll") for (int j = 0; j < NMEM; ++j) { __builtin_amdgcn_sched_group_barrier(0x008, 16 / NMEM, 0); __builtin_amdgcn_sched_group_barrier(0x020, 1, 0); })
+        STAMP_T(t4);
+        STAMP_ONLY(if (st_acc[4] == 0) st_acc[8] = t0 - t_begin; t_last = t4;)
+        STAMP_ADD(0, t1 - t0); STAMP_ADD(1, t2 - t1); STAMP_ADD(2, t3 - t2); STAMP_ADD(3, t4 - t3); STAMP_ADD(4, 1);
     };
 
     EpiOperands<Epi> eops;
@@ -249,27 +222,11 @@ void gemm_nt_kernel(Src src, const CT* __restrict__ W, long ldw, int M, int N, i
     }
 
     nt_epilogue<CT, Epi, WN>(red, ecol, acc, epi, eops, row0, col0, M, N, tid, lane, wr, wc);
-#ifdef MM_STAMP
-    if (tid == 0 && (blockIdx.x & 15) == 3) {        // a sample of waves: same-address atomics from every wave cost more than the kernel
-        MM_T(t_end);
-        for (int i = 0; i < 5; ++i) atomicAdd(&mm_stamps[i], st_acc[i]);
-        atomicAdd(&mm_stamps[5], 1ull);
-        atomicAdd(&mm_stamps[6], t_end - t_begin);
-        atomicAdd(&mm_stamps[7], st_acc[5]);
-        atomicAdd(&mm_stamps[8], t_first - t_begin);
-        atomicAdd(&mm_stamps[9], t_end - t_last);
-    }
-#endif
+    STAMP_T(t_end);
+    STAMP_ADD(5, 1); STAMP_ADD(6, t_end - t_begin); STAMP_ADD(9, t_end - t_last);
+    // a sample of waves: same-address atomics from every wave cost more than the kernel
+    STAMP_ONLY(if (tid == 0 && (blockIdx.x & 15) == 3) stamp_flush(stamps_nt, st_acc));
 }
-
-#ifdef MM_STAMP
-extern "C" int mmvae_debug_stamps(unsigned long long* out8, int reset) {
-    hipError_t e = hipMemcpyFromSymbol(out8, HIP_SYMBOL(mm::mm_stamps), 12 * sizeof(unsigned long long));
-    if (e != hipSuccess) return (int)e;
-    if (reset) { unsigned long long z[12] = {0}; e = hipMemcpyToSymbol(HIP_SYMBOL(mm::mm_stamps), z, sizeof(z)); }
-    return (int)e;
-}
-#endif
 
 template <typename CT, typename Src, typename Epi, int WN>
 static int launch_nt_wn(const Src& src, const void* W, long ldw, int M, int N, int K, const Epi& epi, hipStream_t st) {
@@ -484,3 +441,5 @@ extern "C" int mmvae_gemm_nt(const mmvae_gemm_nt_args* a, void* stream) {
     if (a->prec == MMVAE_PREC_F32) return mm::dispatch_src<float>(a, st);
     return MMVAE_ERR_ARG;
 }
+
+STAMP_ENTRY()

@@ -1,7 +1,7 @@
 // NT GEMM, second generation (gfx950):  C[M,N] = epilogue( A[M,K] * W[N,K]^T )  for operands that need no arithmetic on their way
 // into the MFMA -- A already in the compute type (bf16 activations / gradients), W the prepared bf16 weights.
 //
-// What the first-generation kernel (gemm_nt.hip) spends its time on at B = 65 536 (tools/stamp_nt.py):
+// What the first-generation kernel (gemm_nt.hip) spends its time on at B = 65 536 (tools/stamp.py nt):
 //   * a tile's first loads are issued when the workgroup starts and its last stores when it ends; every workgroup of the launch
 //     runs the same program on the same amount of data, so the whole chip sits in its prologue (HBM saturated, MFMA idle), then
 //     in its main loops, then in its epilogues (HBM read path idle) together: 20-25 % of a workgroup's life on either side of
@@ -33,6 +33,8 @@ template <int WN> struct Nt2Lds {
     static constexpr int ECOL = RED + 4 * 64 * WN * 4;             // per-column constants of the epilogue: 8 * 64*WN floats
     static constexpr int TOTAL = ECOL + 8 * 64 * WN * 4;
 };
+
+STAMP_BUFFER(nt2)
 
 typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((address_space(1))) const void gbl_void;
@@ -324,15 +326,7 @@ void gemm_nt2_kernel(const bf16* __restrict__ A, long lda, const bf16* __restric
             for (int n = 0; n < 4; ++n) Mma<CT>::mma(acc[m][n], bf[n], af[m]);     // swapped operands: transposed accumulator (gemm_nt_epi.h)
     };
 
-#ifdef MM_STAMP
-    // diagnostic build (make STAMP=1): cycles per K step of {wait for the own DMA, barrier, DMA issue, fragment reads + MFMA},
-    // K steps, waves, whole kernel, epilogues -- into the first generation's mm_stamps[] (tools/stamp_nt.py NT2=1)
-    unsigned long long st_acc[6] = {0, 0, 0, 0, 0, 0};
-    const unsigned long long t_begin = __builtin_readcyclecounter();
-#define NT2_T(x) const unsigned long long x = __builtin_readcyclecounter()
-#else
-#define NT2_T(x)
-#endif
+    STAMP_ONLY(unsigned long long st_acc[10] = {}; STAMP_T(t_begin);)        // STAMP_NT2 (common.h)
     issue(T, 0, 0);
     int g = 0;                                                      // ring position: slot = g & 1, continuous across tiles
     for (;;) {
@@ -347,30 +341,26 @@ void gemm_nt2_kernel(const bf16* __restrict__ A, long lda, const bf16* __restric
         for (int kt = 0; kt < nk; ++kt, ++g) {
             // own DMA of this slot has landed (the only vector-memory operations in flight); after the barrier everybody's has,
             // and nobody still reads the other slot
-            NT2_T(t0);
+            STAMP_T(t0);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            NT2_T(t1);
+            STAMP_T(t1);
             __syncthreads();
-            NT2_T(t2);
+            STAMP_T(t2);
             if (kt == 0) nt_epilogue_fill_cols<Epi, WN>(ecol, epi, col0, N, tid);     // previous tile's epilogue is over; visible after the next barrier
             // DMA of the next step first, then this step's fragment reads and MFMAs.  (Interleaving the 8 DMA pieces with the 32 MFMAs
             // -- unconditional issue in one basic block + sched_group_barrier 4 : 1 -- was measured: no gain, 5 % slower at K = 1024.)
             if (kt + 1 < nk) issue(T, kt + 1, (g + 1) & 1);
             else if (Tn >= 0 && !Epi::LDS_STREAM) issue(Tn, 0, (g + 1) & 1);     // the next tile's first slot flies under this tile's epilogue
-            NT2_T(t3);
+            STAMP_T(t3);
             rd(f0a, f0b, g & 1, 0);
             rd(f1a, f1b, g & 1, 1);
             mma(f0a, f0b);
             mma(f1a, f1b);
-#ifdef MM_STAMP
-            asm volatile("s_nop 0" :: "v"(acc[0][0][0]), "v"(acc[3][3][3]));      // the MFMAs of this step are issued before the stamp
-            NT2_T(t4);
-            st_acc[0] += t1 - t0; st_acc[1] += t2 - t1; st_acc[2] += t3 - t2; st_acc[3] += t4 - t3; st_acc[4] += 1;
-#endif
+            STAMP_ONLY(asm volatile("s_nop 0" :: "v"(acc[0][0][0]), "v"(acc[3][3][3])));      // the MFMAs of this step are issued before the stamp
+            STAMP_T(t4);
+            STAMP_ADD(0, t1 - t0); STAMP_ADD(1, t2 - t1); STAMP_ADD(2, t3 - t2); STAMP_ADD(3, t4 - t3); STAMP_ADD(4, 1);
         }
-#ifdef MM_STAMP
-        NT2_T(te0);
-#endif
+        STAMP_T(te0);
         if (nk == 1) __syncthreads();                               // the column constants were written after this tile's only barrier
         // epilogue operands (saved activation, keep mask): fetched here, not a K step early as the first generation does -- 48
         // more live registers across the last MFMAs spilled, and the co-resident workgroup covers the latency
@@ -383,22 +373,14 @@ void gemm_nt2_kernel(const bf16* __restrict__ A, long lda, const bf16* __restric
             nt_epilogue_prefetch<Epi, 0>(eops, epi, row0, col0, M, N, BN, lane, wr, wc);
             nt_epilogue<CT, Epi, WN>(red, ecol, acc, epi, eops, row0, col0, M, N, tid, lane, wr, wc);
         }
-#ifdef MM_STAMP
-        NT2_T(te1);
-        st_acc[5] += te1 - te0;
-#endif
+        STAMP_T(te1);
+        STAMP_ADD(9, te1 - te0);
         if (Tn < 0) break;
         T = Tn;
     }
-#ifdef MM_STAMP
-    if (tid == 0 && (blockIdx.x & 15) == 3) {
-        const unsigned long long t_end = __builtin_readcyclecounter();
-        for (int i = 0; i < 5; ++i) atomicAdd(&mm_stamps[i], st_acc[i]);
-        atomicAdd(&mm_stamps[5], 1ull);
-        atomicAdd(&mm_stamps[6], t_end - t_begin);
-        atomicAdd(&mm_stamps[9], st_acc[5]);
-    }
-#endif
+    STAMP_T(t_end);
+    STAMP_ADD(5, 1); STAMP_ADD(6, t_end - t_begin);
+    STAMP_ONLY(if (tid == 0 && (blockIdx.x & 15) == 3) stamp_flush(stamps_nt2, st_acc));
 }
 
 // Persistent grid: every CU gets its residency's worth of workgroups (2 of 4 waves, or 1 of 8), a multiple of 8 so that a

@@ -12,7 +12,7 @@
 // again complete 64 contiguous bytes (8-byte pieces measured 35 % slower on the store-bound layers).
 // Every epilogue access is a per-lane 16-byte vector: operands are read and results stored straight from/to global
 // memory with no LDS transpose, no barrier and no idle waves.  The LDS-staged form this replaces cost as many cycles per
-// tile as an 8-step main loop (tools/stamp_nt.py: 12-14 k cycles per wave, 64 ds_write_b16 per lane).
+// tile as an 8-step main loop (tools/stamp.py nt: 12-14 k cycles per wave, 64 ds_write_b16 per lane).
 #pragma once
 #include "common.h"
 
@@ -452,7 +452,6 @@ __device__ __forceinline__ void nt_epilogue_body(const float* ecol, f32x4 (&acc)
                 *(uint4*)(epi.C + (long)(rbase + 8) * epi.ldc + cd) = uint4{st1[0], st1[1], st1[2], st1[3]};
             }
         }
-#ifndef MM_NO_STAT_REDUCE
         if (Epi::STATS && want_stats) {
             // Column sums of each group over the 16 lanes li of a lane group: reduce-scatter butterfly -- each step a lane
             // keeps the half of its values selected by one bit of li and adds the partner's copy of that half.
@@ -483,7 +482,6 @@ __device__ __forceinline__ void nt_epilogue_body(const float* ecol, f32x4 (&acc)
                 if (G == 8 || (li & 1) == 0) red[(wr * 2 + which) * BN + cw + e] = v[0];
             }
         }
-#endif
     }
 }
 
@@ -511,12 +509,10 @@ __device__ __forceinline__ void nt_epilogue(float* red, const float* ecol, f32x4
     }
     if (want_stats) {
         __syncthreads();
-#ifndef MM_NO_STAT_ATOMICS
         if (tid < BN && col0 + tid < N) {
             if (epi.stat1) unsafeAtomicAdd(epi.stat1 + col0 + tid, (double)(red[0 * BN + tid] + red[2 * BN + tid]));
             if (epi.stat2) unsafeAtomicAdd(epi.stat2 + col0 + tid, (double)(red[1 * BN + tid] + red[3 * BN + tid]));
         }
-#endif
     }
 }
 

@@ -19,7 +19,7 @@
 // (tile, K step) is one continuous sequence of steps across the workgroup's tiles: the producers run into the next tile while the
 // consumers are in the epilogue, which runs behind the barrier that frees the tile's last ring slot.  ONE s_barrier per K step,
 // executed by all waves: step g+2 is produced between barriers g and g+1 while step g is multiplied (rings of 3 slots).
-// Measured (tools/stamp_ntp.py, tools/abl_ntp.sh): the K steps run at the rate the CU's memory path takes
+// Measured (tools/stamp.py ntp and timing-only ablation builds): the K steps run at the rate the CU's memory path takes
 // 16-byte accesses in (21-25 bytes per clock and CU from L2; issue of a vector-memory instruction then blocks for 60-220 cycles),
 // which is what bounds this kernel, not HBM and not the MFMA pipe.
 // The LDS images are the first generation's (128-byte rows = one K step of 64 bf16, 16-byte chunks XOR-ed with row & 7), so are
@@ -33,24 +33,9 @@
 #include "gemm_nt_epi.h"
 #include "gemm_src.h"
 
-#ifndef NTP_PRO_WCONS
-#define NTP_PRO_WCONS 1
-#endif
-#ifndef NTP_ABL
-#define NTP_ABL 0              // timing-only ablations (tools/abl_ntp.sh): 1 = W DMA from one fixed K step, 2 = A loads from one fixed K step and row tile,
-#endif                         // 3 = no MFMA, 4 = no epilogue
-
 namespace mm {
 
-#ifdef MM_STAMP
-// diagnostic build only (make STAMP=1, tools/stamp_ntp.py): cycles per role, summed over a sample of workgroups
-__device__ unsigned long long mm_ntp_stamps[24];
-#define NTP_T(x) const unsigned long long x = __builtin_readcyclecounter()
-#define NTP_ACC(i, d) st_acc[i] += (d)
-#else
-#define NTP_T(x)
-#define NTP_ACC(i, d)
-#endif
+STAMP_BUFFER(ntp)          // cycles per role, summed over a sample of workgroups (STAMP_NTP, common.h)
 
 template <int V> struct IntC { static constexpr int value = V; };
 
@@ -207,7 +192,7 @@ void gemm_ntp_kernel(const AT* __restrict__ A, long lda, const bf16* __restrict_
     // W: the issuing waves' WPW pieces (8 LDS rows each) of the column tile per K step.  LDS row x of the tile's W block holds W row
     // (x & ~63) + EpiCols::wrow(x & 63) (the epilogue's column order), chunk (position ^ (x & 7)): a part per wave (scalar), a
     // compile-time part per piece (scalar multiply) and a lane part in ONE VGPR.  Issued by the consumer waves or by the producers (NtpCfg::WCONS).
-    constexpr bool WCONS = Cfg::WCONS || (Pro::ON && NTP_PRO_WCONS);   // with the operand prologue the producers are busier still (3 400 against 1 160 cycles per K step)
+    constexpr bool WCONS = Cfg::WCONS || Pro::ON;   // with the operand prologue the producers are busier still (3 400 against 1 160 cycles per K step)
     constexpr int WPW = BN / 8 / (WCONS ? Cfg::NCONS : Cfg::NPA);      // pieces per issuing wave and K step: 4 / 4 (consumers), 8 / 4 (producers)
     constexpr bool PAIRC = EC::G == 8;
     const int widx = WCONS ? wid : wid - Cfg::NCONS;                   // this wave's index among the issuing waves (the other role never issues)
@@ -219,7 +204,7 @@ void gemm_ntp_kernel(const AT* __restrict__ A, long lda, const bf16* __restrict_
     auto issue_w = [&]() __attribute__((always_inline)) {           // DMA of the next W step into its ring slot (past the last step: the last one again)
         const int ln = ntp_lane_id(), l3 = ln >> 3;
         const unsigned wlane = ((unsigned)(PAIRC ? 8 * (l3 >> 2) + (l3 & 3) : l3) * (unsigned)ldw + (unsigned)(((ln & 7) ^ l3) * 8)) * 2u;
-        const bf16* sb = W + ((long)(wcol0 + wrow_wave) * ldw + (NTP_ABL == 1 ? 0 : wkt * 64));
+        const bf16* sb = W + ((long)(wcol0 + wrow_wave) * ldw + wkt * 64);
         const unsigned ls = wlds0 + wslot * Cfg::W_SLOT;
 #pragma unroll
         for (int i = 0; i < WPW; ++i) ntp_dma16(sb + (long)wrow_piece(i) * ldw, wlane, ls, i * 1024);
@@ -255,10 +240,7 @@ void gemm_ntp_kernel(const AT* __restrict__ A, long lda, const bf16* __restrict_
 #pragma unroll
             for (int m = 0; m < 4; ++m)
 #pragma unroll
-                for (int n = 0; n < 4; ++n) {
-                    if (NTP_ABL == 3) asm volatile("" :: "v"(bf[n]), "v"(af[m]));
-                    else Mma<CT>::mma(acc[nb][m][n], bf[n], af[m]);      // swapped operands (gemm_nt_epi.h)
-                }
+                for (int n = 0; n < 4; ++n) Mma<CT>::mma(acc[nb][m][n], bf[n], af[m]);      // swapped operands (gemm_nt_epi.h)
         };
         float st_sum1 = 0.f, st_sum2 = 0.f;          // this lane's column (see the epilogue) over the tiles of the current column tile
         auto dump_stats = [&]() __attribute__((always_inline)) {           // -> the workgroup's sums; every (wr, column) entry has ONE owner lane
@@ -369,36 +351,28 @@ void gemm_ntp_kernel(const AT* __restrict__ A, long lda, const bf16* __restrict_
                     }
                 };
                 const int act = epi.act_code();
-                if (NTP_ABL == 4) { asm volatile("" :: "v"(acc[0][0][0]), "v"(acc[NH - 1][3][3])); }
-                else if (act == 0) fast(IntC<0>{}); else if (act == 1) fast(IntC<1>{}); else fast(IntC<2>{});
+                if (act == 0) fast(IntC<0>{}); else if (act == 1) fast(IntC<1>{}); else fast(IntC<2>{});
         };
         int T = T0, kt = 0, w3 = 0, a3 = 0, ct_prev = -1, ct_flush = -1, row0 = 0, col0 = 0, tpar = 0;
         int e_row0 = 0, e_col0 = 0; const float* e_ecol = ecol2; bool e_pend = false, e_dump = false;
-#ifdef MM_STAMP
-        unsigned long long st_acc[6] = {0, 0, 0, 0, 0, 0};
-        NTP_T(t_begin);
-#endif
+        STAMP_ONLY(unsigned long long st_acc[7] = {}; STAMP_T(t_begin);)
         if (WCONS) { issue_w(); issue_w(); }                  // W of steps 0 and 1
         for (int g = 0; g < G; ++g) {
-            NTP_T(tb0);
+            STAMP_T(tb0);
             // own share of W(g) has landed: everything but the WPW youngest operations (= W(g+1)); this also retires the stores of the
             // epilogue that ran one iteration ago
             if (WCONS) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(WPW) : "memory");
             ntp_bar();
-#ifdef MM_STAMP
-            unsigned long long tb1 = __builtin_readcyclecounter();
-#endif
-            NTP_ACC(0, tb1 - tb0); NTP_ACC(3, 1);
+            STAMP_T(tb1);
+            STAMP_ADD(0, tb1 - tb0); STAMP_ADD(3, 1);
             if (e_pend) {
-                NTP_T(te0);
+                STAMP_T(te0);
                 epilogue(e_row0, e_col0, e_ecol);
                 if (e_dump) dump_stats();
                 e_pend = false;
-#ifdef MM_STAMP
-                NTP_T(te1);
-                NTP_ACC(2, te1 - te0); NTP_ACC(4, 1);
-                tb1 = te1;
-#endif
+                STAMP_T(te1);
+                STAMP_ADD(2, te1 - te0); STAMP_ADD(4, 1);
+                STAMP_ONLY(tb1 = te1);
             }
             if (kt == 1 && ct_flush >= 0) { flush_stats(ct_flush); ct_flush = -1; }     // every consumer is past the old column tile's last epilogue
             if (kt == 0) {
@@ -453,11 +427,9 @@ void gemm_ntp_kernel(const AT* __restrict__ A, long lda, const bf16* __restrict_
                 for (int j = 0; j < 8; ++j) { __builtin_amdgcn_sched_group_barrier(0x008, 2, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); }
                 __builtin_amdgcn_sched_group_barrier(0x008, 16, 0);
             }
-#ifdef MM_STAMP
-            asm volatile("s_nop 0" :: "v"(acc[0][0][0][0]), "v"(acc[NH - 1][3][3][3]));      // the MFMAs of this step are issued before the stamp
-            NTP_T(tb2);
-            NTP_ACC(1, tb2 - tb1);
-#endif
+            STAMP_ONLY(asm volatile("s_nop 0" :: "v"(acc[0][0][0][0]), "v"(acc[NH - 1][3][3][3])));      // the MFMAs of this step are issued before the stamp
+            STAMP_T(tb2);
+            STAMP_ADD(1, tb2 - tb1);
             w3 = (w3 == Cfg::RW - 1) ? 0 : w3 + 1;
             a3 = (a3 == Cfg::RA - 1) ? 0 : a3 + 1;
             if (++kt == nk) {
@@ -471,25 +443,18 @@ void gemm_ntp_kernel(const AT* __restrict__ A, long lda, const bf16* __restrict_
         }
         ntp_bar();
         if (e_pend) {
-            NTP_T(te0);
+            STAMP_T(te0);
             epilogue(e_row0, e_col0, e_ecol);
             dump_stats();
-#ifdef MM_STAMP
-            NTP_T(te1);
-            NTP_ACC(2, te1 - te0); NTP_ACC(4, 1);
-#endif
+            STAMP_T(te1);
+            STAMP_ADD(2, te1 - te0); STAMP_ADD(4, 1);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the W pieces issued past the last step have landed: no DMA outlives the workgroup
         ntp_bar();                                   // every consumer has added its last tile's column sums
         flush_stats(ct_prev);
-#ifdef MM_STAMP
-        if (tid == 0 && (blockIdx.x & 15) == 3) {
-            NTP_T(t_end);
-            for (int i = 0; i < 5; ++i) atomicAdd(&mm_ntp_stamps[i], st_acc[i]);
-            atomicAdd(&mm_ntp_stamps[5], t_end - t_begin);
-            atomicAdd(&mm_ntp_stamps[6], 1ull);
-        }
-#endif
+        STAMP_T(t_end);
+        STAMP_ADD(5, t_end - t_begin); STAMP_ADD(6, 1);
+        STAMP_ONLY(if (tid == 0 && (blockIdx.x & 15) == 3) stamp_flush(stamps_ntp, st_acc));
     } else {
         // ---------------------------------------------------------------------------------- A producers
         constexpr int EL = 16 / (int)sizeof(AT);                    // A elements per lane and load (16 bytes)
@@ -532,8 +497,8 @@ void gemm_ntp_kernel(const AT* __restrict__ A, long lda, const bf16* __restrict_
             if (edge) set_voff();
         };
         auto load = [&](f32x4 (&s)[AI]) __attribute__((always_inline)) {
-            const unsigned ko = (unsigned)(min((NTP_ABL == 2 ? 0 : it.kt * 64) + q * EL, kmaxv) - q * EL) * (unsigned)sizeof(AT);
-            const char* sbase = (const char*)A + (size_t)(NTP_ABL == 2 ? (blockIdx.x & 7) * BM : it.row0) * (size_t)lda * sizeof(AT);
+            const unsigned ko = (unsigned)(min(it.kt * 64 + q * EL, kmaxv) - q * EL) * (unsigned)sizeof(AT);
+            const char* sbase = (const char*)A + (size_t)(unsigned)it.row0 * (size_t)lda * sizeof(AT);
 #pragma unroll
             for (int i = 0; i < AI; ++i) ntp_ld16(s[i], voff[i] + ko, sbase);
         };
@@ -544,9 +509,12 @@ void gemm_ntp_kernel(const AT* __restrict__ A, long lda, const bf16* __restrict_
                 for (int i = 0; i < AI; ++i) ntp_ld8(m[i], moff[i] + (unsigned)(kt_ * 64), mbase);
             }
         };
-#ifdef MM_STAMP
-        unsigned long long stmp[8] = {0, 0, 0, 0, 0, 0, 0, 0}, stprev[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
+        // stamps (STAMP_NTP, common.h): s_memtime at 8 points of an iteration, collected WITHOUT waiting (ntp_bar()'s lgkmcnt(0)
+        // retires them): a waiting stamp would serialise the LDS writes and the issue streams it is supposed to time
+        STAMP_ONLY(unsigned long long stmp[8] = {}, stprev[8] = {}, st_acc[7] = {};)
+#define NTP_ST(i) STAMP_ONLY(asm volatile("s_memtime %0" : "=s"(stmp[i]) :: "memory"))
+#define NTP_STACC() STAMP_ONLY(for (int i_ = 0; i_ < 7; ++i_) st_acc[i_] += stprev[i_ + 1] - stprev[i_])
+#define NTP_STEND() STAMP_ONLY(asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); for (int i_ = 0; i_ < 8; ++i_) stprev[i_] = stmp[i_])
         int skt = 0, sslot = 0, staged = 0;                          // K step (inside its tile) / ring slot / index of the step that is staged next
         int s_T = T0, s_row0, s_ct; { int rt_, ct_; tile_rc(T0, rt_, ct_); s_row0 = rt_ * BM; s_ct = ct_; }      // PRO + out: the tile that is being staged
         auto stage = [&](f32x4 (&s)[AI]) __attribute__((always_inline)) {
@@ -568,9 +536,7 @@ void gemm_ntp_kernel(const AT* __restrict__ A, long lda, const bf16* __restrict_
                     for (int e = 0; e < 4; ++e) o[i][e] = (bf16)v[e];
                 }
             }
-#ifdef MM_STAMP
-            asm volatile("s_memtime %0" : "=s"(stmp[3]) :: "memory");
-#endif
+            NTP_ST(3);
 #pragma unroll
             for (int i = 0; i < AI; ++i) {
                 const int r = prow0 + RPI * i + rsub;
@@ -621,18 +587,6 @@ void gemm_ntp_kernel(const AT* __restrict__ A, long lda, const bf16* __restrict_
         constexpr int LPS = AI * (PMASK ? 2 : 1);                     // loads per set: A pieces (+ keep-byte pieces)
         constexpr int N_SET = (SETS - 1) * LPS + 2 * PW;              // operations younger than the loads of the set that is staged next
         constexpr int N_W = 2 * LPS + PW;                             // operations younger than the W pieces of the next step
-#ifdef MM_STAMP
-        // s_memtime at 8 points of an iteration, collected WITHOUT waiting (ntp_bar()'s lgkmcnt(0) retires them): a waiting stamp would
-        // serialise the LDS writes and the issue streams it is supposed to time
-        unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define NTP_ST(i) asm volatile("s_memtime %0" : "=s"(stmp[i]) :: "memory")
-#define NTP_STACC() for (int i_ = 0; i_ < 7; ++i_) st_acc[i_] += stprev[i_ + 1] - stprev[i_]
-#define NTP_STEND() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); for (int i_ = 0; i_ < 8; ++i_) stprev[i_] = stmp[i_]
-#else
-#define NTP_ST(i)
-#define NTP_STACC()
-#define NTP_STEND()
-#endif
 #define NTP_WAITW(N) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory");
         int g = 0;
         bool done = false;
@@ -666,10 +620,7 @@ void gemm_ntp_kernel(const AT* __restrict__ A, long lda, const bf16* __restrict_
 #undef NTP_ST
 #undef NTP_STACC
 #undef NTP_STEND
-#undef NTP_ASTEP
-#ifdef MM_STAMP
-        if (lane == 0 && pw == 0 && (blockIdx.x & 15) == 3) for (int i = 0; i < 7; ++i) atomicAdd(&mm_ntp_stamps[8 + i], st_acc[i]);
-#endif
+        STAMP_ONLY(if (lane == 0 && pw == 0 && (blockIdx.x & 15) == 3) stamp_flush(stamps_ntp + 8, st_acc));
         ntp_bar();
         ntp_bar();                                   // the consumers' last epilogue / statistics flush
     }

@@ -48,12 +48,3 @@ int ntp_dispatch(const mmvae_gemm_nt_args* a, hipStream_t st) {
 }
 
 }  // namespace mm
-
-#ifdef MM_STAMP
-extern "C" int mmvae_debug_ntp_stamps(unsigned long long* out24, int reset) {
-    hipError_t e = hipMemcpyFromSymbol(out24, HIP_SYMBOL(mm::mm_ntp_stamps), 24 * sizeof(unsigned long long));
-    if (e != hipSuccess) return (int)e;
-    if (reset) { unsigned long long z[24] = {0}; e = hipMemcpyToSymbol(HIP_SYMBOL(mm::mm_ntp_stamps), z, sizeof(z)); }
-    return (int)e;
-}
-#endif

@@ -12,7 +12,7 @@
 // Q may carry the BN-normalise + ReLU + Dropout prologue (it is then the previous layer's
 // pre-BN output), so post-activation tensors are never materialised.
 // Pipeline: two global register sets (one for f32 sources), double-buffered LDS with one barrier per
-// batch step, steady-state loop without conditional fetches (see gemm_nt.hip for why).  tools/stamp_tn.py
+// batch step, steady-state loop without conditional fetches (see gemm_nt.hip for why).  tools/stamp.py tn
 // shows where a step goes: the global loads are never waited for; the registers -> LDS stage and the
 // transpose reads are what the MFMAs wait on.
 // The batch is split over `nsplit` workgroups per output tile; partial tiles are combined with
@@ -22,11 +22,9 @@
 #include "mmvae_hip.h"
 #include "gemm_src.h"
 
-#ifndef MM_REDUCE_U
-#define MM_REDUCE_U 16      // loads a reduce thread keeps in flight (step at B = 65 536: 4 -> +8 us, 8 -> +2.5, 32 -> +8.5 against 16)
-#endif
-
 namespace mm {
+
+constexpr int REDUCE_U = 16;      // loads a reduce thread keeps in flight (step at B = 65 536: 4 -> +8 us, 8 -> +2.5, 32 -> +8.5 against 16)
 
 template <typename CT> struct TnGeom;
 template <> struct TnGeom<bf16> {
@@ -66,21 +64,14 @@ __device__ __forceinline__ f32x4 tn_frag(const unsigned char* tile, int colbase,
     return v;
 }
 
-#ifdef MM_STAMP
-// Diagnostic build only (make STAMP=1, tools/stamp_tn.py): cycles per batch step of {fragment step 0, stage, fragment step 1
-// + fetch issue, barrier}, steps, waves, whole-kernel cycles, cycles before the loop, cycles after it.
-__device__ unsigned long long mm_stamps_tn[12];
-#define MT_T(x) const unsigned long long x = __builtin_readcyclecounter()
-#else
-#define MT_T(x)
-#endif
+STAMP_BUFFER(tn)           // cycles per batch step of tn_body (STAMP_TN, common.h)
 
 // One workgroup's share of a dW GEMM: output tile and batch split from its LOCAL block id L (0 .. grid of this problem), shared
 // by the one-problem kernel and the grouped kernel below.
 // DMA = true (both operands plain and already in the compute type, every batch step of every split a full MT rows): the tiles
 // are moved by LDS-DMA (global_load_lds_dwordx4, 4 rows x 256 B per wave-instruction, the chunk swizzle applied to the SOURCE
 // address) instead of global -> VGPR -> ds_write; the registers -> LDS pass was what the MFMAs of this kernel waited for
-// (tools/stamp_tn.py: stage 24 % of a step + the fragment step that follows it stalled on it).
+// (tools/stamp.py tn: stage 24 % of a step + the fragment step that follows it stalled on it).
 // NG = 2 (DMA form only): EIGHT waves in two groups of four; every wave still owns a 64x64 piece of the 128x128 tile, group g
 // multiplies rows [32 g, 32 g + 32) of every 64-row step and the two partial tiles are added through LDS before the slab
 // store -- twice the rows per workgroup at the same number of waves per CU, i.e. HALF the slab (its store + the reduce's
@@ -180,43 +171,27 @@ void tn_body(const PSrc& ps, const QSrc& qs, float* __restrict__ dW, long ldw, f
     };
     // one batch step: tile t is multiplied from LDS buffer `buf` while tile t+1 goes registers -> other buffer between the
     // two fragment steps and a later tile is fetched into the registers just freed; ONE barrier per step
-#ifdef MM_STAMP
-    unsigned long long st_acc[5] = {0, 0, 0, 0, 0}, t_first = 0, t_last = 0, st_acc5 = 0;
-    MT_T(t_begin);
-#endif
+    STAMP_ONLY(unsigned long long st_acc[10] = {}, t_last = 0; STAMP_T(t_begin);)
     // registers -> LDS writes and the global loads are spread between the MFMAs of the two fragment steps (see gemm_nt.hip)
     auto kstep = [&](auto& rp_n, auto& rq_n, int t, int buf, bool has_next, bool do_fetch, int fetch_t) {
-        MT_T(t0);
+        STAMP_T(t0);
         compute(buf, 0);
-        MT_T(t1);
-#ifdef MM_STAMP
-        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");      // steady state: the set about to be staged has landed
-        MT_T(t1b);
-        st_acc5 += t1b - t1;
-#endif
+        STAMP_T(t1);
+        STAMP_ONLY(asm volatile("s_waitcnt vmcnt(8)" ::: "memory"));      // steady state: the set about to be staged has landed
+        STAMP_T(t1b);
+        STAMP_ADD(7, t1b - t1);
         if (has_next) stage(rp_n, rq_n, t + 1, buf ^ 1);
-#ifndef MM_STAMP
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { __builtin_amdgcn_sched_group_barrier(0x008, 2, 0); __builtin_amdgcn_sched_group_barrier(0x200, 1, 0); }
-#endif
-        MT_T(t2);
+        UNSTAMPED(_Pragma("unroll") for (int j = 0; j < 8; ++j) { __builtin_amdgcn_sched_group_barrier(0x008, 2, 0); __builtin_amdgcn_sched_group_barrier(0x200, 1, 0); })
+        STAMP_T(t2);
         compute(buf, 1);
         if (do_fetch) fetch(rp_n, rq_n, fetch_t);               // into the registers just staged
-#ifndef MM_STAMP
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { __builtin_amdgcn_sched_group_barrier(0x008, 2, 0); __builtin_amdgcn_sched_group_barrier(0x020, 1, 0); }
-#endif
-#ifdef MM_STAMP
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
-        MT_T(t3);
+        UNSTAMPED(_Pragma("unroll") for (int j = 0; j < 8; ++j) { __builtin_amdgcn_sched_group_barrier(0x008, 2, 0); __builtin_amdgcn_sched_group_barrier(0x020, 1, 0); })
+        STAMP_ONLY(asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"));
+        STAMP_T(t3);
         __syncthreads();
-        MT_T(t4);
-#ifdef MM_STAMP
-        if (st_acc[4] == 0) t_first = t0;
-        t_last = t4;
-        st_acc[0] += t1 - t0; st_acc[1] += t2 - t1; st_acc[2] += t3 - t2; st_acc[3] += t4 - t3; st_acc[4] += 1;
-#endif
+        STAMP_T(t4);
+        STAMP_ONLY(if (st_acc[4] == 0) st_acc[8] = t0 - t_begin; t_last = t4;)
+        STAMP_ADD(0, t1 - t0); STAMP_ADD(1, t2 - t1); STAMP_ADD(2, t3 - t2); STAMP_ADD(3, t4 - t3); STAMP_ADD(4, 1);
     };
     // f32 sources hold 32 bytes per chunk in flight (two sets spill) and the BN-prologue source measured slower with two:
     // those run one register set, one step ahead
@@ -392,17 +367,9 @@ void tn_body(const PSrc& ps, const QSrc& qs, float* __restrict__ dW, long ldw, f
             if (lane < 16 && n < N) unsafeAtomicAdd(db + n, v);
         }
     }
-#ifdef MM_STAMP
-    if (tid == 0 && (blockIdx.x & 7) == 3) {
-        MT_T(t_end);
-        for (int i = 0; i < 5; ++i) atomicAdd(&mm_stamps_tn[i], st_acc[i]);
-        atomicAdd(&mm_stamps_tn[5], 1ull);
-        atomicAdd(&mm_stamps_tn[6], t_end - t_begin);
-        atomicAdd(&mm_stamps_tn[7], st_acc5);
-        atomicAdd(&mm_stamps_tn[8], t_first - t_begin);
-        atomicAdd(&mm_stamps_tn[9], t_end - t_last);
-    }
-#endif
+    STAMP_T(t_end);
+    STAMP_ADD(5, 1); STAMP_ADD(6, t_end - t_begin); STAMP_ADD(9, t_end - t_last);
+    STAMP_ONLY(if (tid == 0 && (blockIdx.x & 7) == 3) stamp_flush(stamps_tn, st_acc));
 }
 
 template <typename CT, typename PSrc, typename QSrc, bool DMA, int NG = 1>
@@ -465,7 +432,7 @@ void gemm_tn_group_kernel(const TnGroup g)
 }
 
 // sum_z p[z * stride], z = 0 .. n-1, added in that order; U loads are requested before the first is added (a thread of a reduce
-// launch has nothing else to do; MM_REDUCE_U = 16 measured best)
+// launch has nothing else to do; REDUCE_U = 16 measured best)
 template <int U>
 __device__ __forceinline__ float slab_sum(const float* __restrict__ p, long stride, int n) {
     float s = 0.f;
@@ -500,17 +467,8 @@ __global__ __launch_bounds__(256) void tn_group_reduce_kernel(const TnGroupReduc
     const int e = i - g.first[pi], nk = g.nk[pi], ns = g.nsplit[pi];
     const float* sl = g.slab[pi] + e;
     const float old = g.dW[pi][e];                       // requested with the first slab loads, not behind the sum (one round trip fewer)
-    g.dW[pi][e] = old + slab_sum<MM_REDUCE_U>(sl, nk, ns);                                   // lddw == K for these (contiguous gradient views)
+    g.dW[pi][e] = old + slab_sum<REDUCE_U>(sl, nk, ns);                                   // lddw == K for these (contiguous gradient views)
 }
-
-#ifdef MM_STAMP
-extern "C" int mmvae_debug_stamps_tn(unsigned long long* out12, int reset) {
-    hipError_t e = hipMemcpyFromSymbol(out12, HIP_SYMBOL(mm::mm_stamps_tn), 12 * sizeof(unsigned long long));
-    if (e != hipSuccess) return (int)e;
-    if (reset) { unsigned long long z[12] = {0}; e = hipMemcpyToSymbol(HIP_SYMBOL(mm::mm_stamps_tn), z, sizeof(z)); }
-    return (int)e;
-}
-#endif
 
 // dW[n][k] += sum_z slab[z][n][k].  Splits are summed in groups of TN_RG (blockIdx.y): ONE group (<= TN_RG splits, the large
 // weight matrices) is a fixed-order sum -> bitwise reproducible gradients; more groups (small matrices split hundreds of
@@ -523,7 +481,7 @@ __global__ __launch_bounds__(256) void tn_reduce_kernel(const float* __restrict_
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nk; i += (long)gridDim.x * blockDim.x) {
         const long n = i / K, k = i - n * K;
         const float old = single ? dW[n * ldw + k] : 0.f;   // requested with the first slab loads, not behind the sum (one round trip fewer)
-        const float s = slab_sum<MM_REDUCE_U>(slab + z0 * nk + i, nk, z1 - z0);
+        const float s = slab_sum<REDUCE_U>(slab + z0 * nk + i, nk, z1 - z0);
         if (single) dW[n * ldw + k] = old + s;
         else unsafeAtomicAdd(dW + n * ldw + k, s);
     }

@@ -83,14 +83,7 @@ __device__ __forceinline__ bf16x8 tnw_frag(const unsigned char* tile, int rowb, 
     return u.v;
 }
 
-#ifdef MM_STAMP
-// Diagnostic build only (make STAMP=1, tools/stamp_tnw.py): cycles of {own-DMA wait, barrier, DMA issue, fragments + MFMA}
-// summed over the steps of wave 0 of every 8th workgroup, steps, workgroups, whole-kernel cycles, epilogue cycles.
-__device__ unsigned long long mm_stamps_tnw[12];
-#define MW_T(x) const unsigned long long x = __builtin_readcyclecounter()
-#else
-#define MW_T(x)
-#endif
+STAMP_BUFFER(tnw)          // cycles per batch step of gemm_tnw_dma_kernel (STAMP_TNW, common.h)
 
 template <typename QT, int VEC> struct TnwQRaw;
 template <> struct TnwQRaw<bf16, 8> { bf16x8 v; };
@@ -437,10 +430,7 @@ void gemm_tnw_dma_kernel(const TnwArgs a)
     // order: step t has landed when at most the pieces of the NSTAGE - 2 later steps are outstanding.
     constexpr int NP_LO = (PMODE ? 2 : 1) * (PP / 8) + QP / 8;                 // pieces per step of a wave (waves < PP % 8 / QP % 8 issue one more)
     const int extra = ((PP % 8 != 0 && wv < PP % 8) ? (PMODE ? 2 : 1) : 0) + ((QP % 8 != 0 && wv < QP % 8) ? 1 : 0);
-#ifdef MM_STAMP
-    unsigned long long sa[4] = {0, 0, 0, 0};
-    MW_T(t_begin);
-#endif
+    STAMP_ONLY(unsigned long long st_acc[8] = {}; STAMP_T(t_begin);)
 #pragma unroll
     for (int s_ = 0; s_ < NSTAGE - 1; ++s_) if (s_ < nt) issue(s_, s_);
     // The ring is unrolled so that every stage address is a compile-time offset: with a run-time stage index hipcc cannot tell
@@ -451,28 +441,26 @@ void gemm_tnw_dma_kernel(const TnwArgs a)
         for (int u = 0; u < NSTAGE; ++u) {
             const int t = t0 + u;
             if (t >= nt) break;
-            MW_T(w0);
+            STAMP_T(w0);
             if (NSTAGE > 2 && t + NSTAGE - 2 < nt) {             // steady state: NSTAGE - 2 later steps may still be in flight
                 if (extra == 0) asm volatile("s_waitcnt vmcnt(%0)" :: "n"((NSTAGE - 2) * NP_LO) : "memory");
                 else if (extra == 1) asm volatile("s_waitcnt vmcnt(%0)" :: "n"((NSTAGE - 2) * (NP_LO + 1)) : "memory");
                 else if (extra == 2) asm volatile("s_waitcnt vmcnt(%0)" :: "n"((NSTAGE - 2) * (NP_LO + 2)) : "memory");
                 else asm volatile("s_waitcnt vmcnt(%0)" :: "n"((NSTAGE - 2) * (NP_LO + 3)) : "memory");
             } else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            MW_T(w1);
+            STAMP_T(w1);
             __builtin_amdgcn_s_barrier();                        // everybody's pieces of step t have landed; nobody still reads stage t - 1
             asm volatile("" ::: "memory");
-            MW_T(w2);
+            STAMP_T(w2);
             if (t + NSTAGE - 1 < nt) issue(t + NSTAGE - 1, (u + NSTAGE - 1) % NSTAGE);      // the stage step t - 1 was read from
-            MW_T(w3);
+            STAMP_T(w3);
             compute(u);
-#ifdef MM_STAMP
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            MW_T(w4);
-            sa[0] += w1 - w0; sa[1] += w2 - w1; sa[2] += w3 - w2; sa[3] += w4 - w3;
-#endif
+            STAMP_ONLY(asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"));
+            STAMP_T(w4);
+            STAMP_ADD(0, w1 - w0); STAMP_ADD(1, w2 - w1); STAMP_ADD(2, w3 - w2); STAMP_ADD(3, w4 - w3);
         }
     }
-    MW_T(t_loop_end);
+    STAMP_T(t_loop_end);
 
     float* sl = a.slab + (long)zz * N * K;
     const bool v4 = (K & 3) == 0, v2 = (K & 1) == 0;
@@ -504,16 +492,9 @@ void gemm_tnw_dma_kernel(const TnwArgs a)
             if (lane < 16 && n < N) unsafeAtomicAdd(a.db + n, v);
         }
     }
-#ifdef MM_STAMP
-    if (tid == 0 && (blockIdx.x & 7) == 3) {
-        MW_T(t_end);
-        for (int i = 0; i < 4; ++i) atomicAdd(&mm_stamps_tnw[i], sa[i]);
-        atomicAdd(&mm_stamps_tnw[4], (unsigned long long)nt);
-        atomicAdd(&mm_stamps_tnw[5], 1ull);
-        atomicAdd(&mm_stamps_tnw[6], t_end - t_begin);
-        atomicAdd(&mm_stamps_tnw[7], t_end - t_loop_end);
-    }
-#endif
+    STAMP_T(t_end);
+    STAMP_ADD(4, nt); STAMP_ADD(5, 1); STAMP_ADD(6, t_end - t_begin); STAMP_ADD(7, t_end - t_loop_end);
+    STAMP_ONLY(if (tid == 0 && (blockIdx.x & 7) == 3) stamp_flush(stamps_tnw, st_acc));
 }
 
 template <class C, int PMODE, typename QT, int NSTAGE>
@@ -585,12 +566,3 @@ int launch_tn_wide(const mmvae_gemm_tn_args* a, hipStream_t st, int* nsplit_out)
 }
 
 }  // namespace mm
-
-#ifdef MM_STAMP
-extern "C" int mmvae_debug_stamps_tnw(unsigned long long* out12, int reset) {
-    hipError_t e = hipMemcpyFromSymbol(out12, HIP_SYMBOL(mm::mm_stamps_tnw), 12 * sizeof(unsigned long long));
-    if (e != hipSuccess) return (int)e;
-    if (reset) { unsigned long long z[12] = {0}; e = hipMemcpyToSymbol(HIP_SYMBOL(mm::mm_stamps_tnw), z, sizeof(z)); }
-    return (int)e;
-}
-#endif
