@@ -212,6 +212,8 @@ int mmvae_bn_bwd_finalize_apply(int32_t dtype, int32_t M, int32_t N, void* d, in
  * EncoderC (encoders.py:57-61): Embedding + two heads == a per-class table
  *   T[S][2L] = emb[S][E] x [Wmu;Wlv]^T + [bmu;blv]      (fp32), gathered per sample later.
  * Backward: from dT[S][2L]: dEmb, dWmu, dWlv, dbmu, dblv (all accumulated).
+ *   Capacity: every workgroup of mmvae_embed_table_bwd keeps its three operands in LDS, so the call returns MMVAE_ERR_ARG (nothing
+ *   enqueued) when (S*2L + S*E + 2L*E) * 4 bytes exceed 64 KiB: 24 sites x latent 128 x embed 32 fit (59 KiB), 32 sites do not.
  * ------------------------------------------------------------------------------------------- */
 int mmvae_embed_table_fwd(int32_t S, int32_t E, int32_t L, const float* emb, const float* w_mu, const float* b_mu,
                           const float* w_lv, const float* b_lv, float* table, void* stream);
@@ -345,7 +347,7 @@ int mmvae_rows_to_bf16(const void* src, int32_t src_dtype, int64_t ld_src, void*
 
 /* ---------------------------------------------------------------------------------------------
  * AdamW (torch.optim.AdamW, constructed by the caller: optimize_hyperparameters.py:93-97,
- * train_dna2rna.py:185-189), all tensors in one launch per 64 tensors.  `items_host` is an array in HOST memory
+ * train_dna2rna.py:185-189), all tensors in one launch per 64 tensors (every record is checked before the first launch).  `items_host` is an array in HOST memory
  * (device pointers inside); it is copied into the kernel arguments, so nothing is uploaded and the call is graph-capturable:
  *   p *= 1-lr*wd ; m = b1*m+(1-b1)g ; v = b2*v+(1-b2)g^2 ; p -= lr/bc1 * m/(sqrt(v)/sqrt(bc2)+eps)
  * ------------------------------------------------------------------------------------------- */

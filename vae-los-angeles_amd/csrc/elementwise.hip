@@ -3,6 +3,7 @@
 // mean-fusion + reparameterisation, the fused loss, Philox noise and multi-tensor AdamW.
 // All of these are HBM- or latency-bound; they use 64-lane wave reductions, vector loads where
 // the caller's row alignment allows, and f64 only for the final cross-block accumulations.
+#include <vector>
 #include "common.h"
 #include "mmvae_hip.h"
 
@@ -1108,8 +1109,10 @@ extern "C" int mmvae_adamw_step(const mmvae_adamw_item* items_host, int32_t n_it
     if (!items_host || n_items <= 0 || (!step_dev && (bias_corr1 <= 0.f || bias_corr2 <= 0.f))) return MMVAE_ERR_ARG;
     if (advance && (!step_dev || n_items > 64)) return MMVAE_ERR_ARG;       // one launch = one tick of the counter
     if (step_dev) { bias_corr1 = 1.f; bias_corr2 = 1.f; }
+    // every item is checked and every chunk laid out BEFORE the first launch: a refused call has enqueued nothing (mmvae_hip.h)
+    std::vector<AdamWBatch> batches((n_items + 63) / 64);
     for (int base = 0; base < n_items; base += 64) {
-        AdamWBatch batch;
+        AdamWBatch& batch = batches[base / 64];
         const int n = n_items - base < 64 ? n_items - base : 64;
         batch.n = n; batch.first[0] = 0;
         for (int i = 0; i < n; ++i) {
@@ -1117,9 +1120,10 @@ extern "C" int mmvae_adamw_step(const mmvae_adamw_item* items_host, int32_t n_it
             if (!batch.items[i].p || !batch.items[i].g || !batch.items[i].m || !batch.items[i].v || batch.items[i].n <= 0) return MMVAE_ERR_ARG;
             batch.first[i + 1] = batch.first[i] + grid_for(batch.items[i].n, 256 * 4, 256);       // 4 elements per thread, <= 256 blocks per tensor
         }
-        const int gx = batch.first[n];
-        if (advance && gx > MMVAE_CTR_COPIES) return MMVAE_ERR_ARG;
-        hipLaunchKernelGGL(adamw_kernel, dim3(gx), dim3(256), 0, (hipStream_t)stream, batch, lr, beta1, beta2, eps,
+        if (advance && batch.first[n] > MMVAE_CTR_COPIES) return MMVAE_ERR_ARG;
+    }
+    for (const AdamWBatch& batch : batches) {
+        hipLaunchKernelGGL(adamw_kernel, dim3(batch.first[batch.n]), dim3(256), 0, (hipStream_t)stream, batch, lr, beta1, beta2, eps,
                            weight_decay, bias_corr1, 1.0f / sqrtf(bias_corr2), maximize, step_dev, advance ? 1 : 0, lr_dev);
         MM_CHECK_LAUNCH();
     }
