@@ -5,18 +5,26 @@ short sequence of launches into libmmvae_hip.so; no torch arithmetic is used on 
 Activations between GEMMs are stored in the *activation type* of the precision mode (bf16 or
 f32); BatchNorm statistics, loss sums, gradients of parameters and the optimiser are fp32.
 
-What is saved for backward per BN layer is only the PRE-BatchNorm GEMM output, the per-column
-(mean, rstd, scale, shift) and the dropout keep-mask: post-activation tensors are recomputed
-inside the consumer GEMM's operand prologue.
+What is saved for backward per BN layer (a `LayerSave`) is only the PRE-BatchNorm GEMM output, the
+per-column (mean, rstd, scale, shift) and the dropout keep-mask: post-activation tensors are
+recomputed inside the consumer GEMM's operand prologue (an `ops.Prologue`).
+
+What travels from the forward through the loss to the backward is one `StepState`: the layer saves
+of each encoder, the decoders' activations, eps / logvar, the step's zeroed buffers (`StepZeros`:
+ONE allocation, laid out by `VAEGraph.zero_pack`), and what the loss adds on the way -- the
+reconstruction losses computed inside the decoder GEMMs (`FusedRecon`) and the gradients the loss
+kernel left for the backward (`LossGrads`).
 """
 import os
+from dataclasses import dataclass
+from typing import NamedTuple, Optional
 
 import torch
 
 from . import ops
 from . import _lib as L_
-from .ops import (PREC_BF16, PREC_F32, ACT_NONE, ACT_RELU, ACT_SIGMOID, EPI_RELU_MASK, EPI_BN_BWD, TILE, DROP_P,
-                  ceil_to, act_dtype)
+from .ops import (PREC_BF16, PREC_F32, ACT_NONE, ACT_RELU, ACT_SIGMOID, EPI_RELU_MASK, EPI_BN_BWD, DROP_P,
+                  ceil_to, act_dtype, Prologue, BnBwdEpilogue, BnBwdFinalize, BnBwdApply)
 
 _PRECISIONS = {"bf16": PREC_BF16, "fp32": PREC_F32, "f32": PREC_F32}
 _default_precision = _PRECISIONS[os.environ.get("MMVAE_PRECISION", "bf16").lower()]
@@ -55,10 +63,11 @@ class NoiseSource:
 
     def _seed(self):
         seed = torch.initial_seed() & 0xFFFFFFFFFFFFFFFF
-        if self.stream_rank is not None:
-            seed = (seed + 0x9E3779B97F4A7C15 * (int(self.stream_rank) + 1)) & 0xFFFFFFFFFFFFFFFF
-        elif torch.distributed.is_available() and torch.distributed.is_initialized():
-            seed = (seed + 0x9E3779B97F4A7C15 * (torch.distributed.get_rank() + 1)) & 0xFFFFFFFFFFFFFFFF
+        rank = self.stream_rank
+        if rank is None and torch.distributed.is_available() and torch.distributed.is_initialized():
+            rank = torch.distributed.get_rank()
+        if rank is not None:
+            seed = (seed + 0x9E3779B97F4A7C15 * (int(rank) + 1)) & 0xFFFFFFFFFFFFFFFF
         return seed
 
     def offset_tensor(self, device):
@@ -142,12 +151,99 @@ def zeros_pack(device, specs):
 _ITEMSIZE = {torch.float32: 4, torch.float64: 8, torch.uint8: 1, torch.int64: 8}
 
 
+def carve_arena(flat, params):
+    """{param: view of its shape} tiling the flat fp32 gradient arena in the order of `params`."""
+    views, off = {}, 0
+    for p in params:
+        views[p] = flat[off:off + p.numel()].view(p.shape)
+        off += p.numel()
+    return views
+
+
+class PrepCache:
+    """The prepared (MFMA operand) weights of a module tree: rebuilt when the precision, the device or the storage of a parameter
+    changes, and refreshed from the fp32 masters by ONE launch on every call.  It holds no reference to its owner (an owner that
+    kept bound methods of itself here would be freed only by the cyclic GC, with its gradients and prepared weights in HBM)."""
+
+    def __init__(self):
+        self.key = self.prep = None
+
+    def ensure(self, prec, device, params, build):
+        """params: the parameters; build(prec, device) -> their PreparedLinears."""
+        key = (prec, str(device)) + tuple(p.data_ptr() for p in params)
+        if key != self.key:
+            pls = build(prec, device)
+            self.prep = ops.WeightPrep(pls, device) if pls else None
+            self.key = key
+        if self.prep is not None:
+            self.prep.run()
+
+
 class BNState:
     """Per-layer BatchNorm vectors: rows of one [4][N] fp32 buffer (mean, rstd, scale, shift)."""
 
     def __init__(self, N, device):
         self.buf = torch.empty(4, N, dtype=torch.float32, device=device)
         self.mean, self.rstd, self.scale, self.shift = self.buf[0], self.buf[1], self.buf[2], self.buf[3]
+
+
+class LayerSave(NamedTuple):
+    """What the backward needs of one [Linear -> BatchNorm -> ReLU -> Dropout] layer."""
+    q: torch.Tensor                     # the dW GEMM's Q operand: the layer's input as stored, or its kept post-activation form
+    q_prologue: Optional[Prologue]      # what turns the stored input into the layer's input on load (None: first layer, or kept)
+    y: torch.Tensor                     # the Linear's output, before BatchNorm
+    bn: BNState
+    y_prologue: Prologue                # what the consumer of y applies: this layer's BatchNorm + ReLU + Dropout
+
+
+class FusedRecon(NamedTuple):
+    """Reconstruction losses computed inside the decoders' last GEMMs (VAEGraph.fused_recon)."""
+    sums: torch.Tensor                  # float64[5] loss accumulators those GEMMs added to
+    out5: torch.Tensor                  # float32[5] that mmvae_loss_finalize fills from them
+    g: dict                             # decoder index -> gradient w.r.t. its pre-activation output
+    targets: dict                       # decoder index -> the target the forward was given
+
+
+@dataclass(slots=True, eq=False)
+class LossGrads:
+    """Gradients the fused loss left for the backward of the forward that produced its inputs (functional, "fused hand-off")."""
+    g_outs: list                        # per decoder: activation-typed gradient (w.r.t. the logits behind a Sigmoid) or None
+    g_mu: torch.Tensor
+    g_lv: torch.Tensor
+    unit_grad: bool                     # the caller promised loss.backward() with the default gradient of 1
+    scale: Optional[torch.Tensor] = None        # the gradient that arrived at the loss (device scalar), unless unit_grad
+    armed: bool = False                 # the loss's own backward ran
+
+
+@dataclass(slots=True, eq=False)
+class StepZeros:
+    """Everything one step needs zeroed, in the order of its regions inside ONE allocation (VAEGraph.zero_pack).  The forward half
+    is the first two fields (loss_ws only when a backward follows), the backward half the last three."""
+    fwd_stats: list                     # per BN layer: float64 (2, width) sums of the forward BatchNorm
+    loss_ws: Optional[tuple]            # (sums float64[5], out5 float32[5]) as ops.loss_workspace; None once the loss took it
+    arena: Optional[torch.Tensor]       # flat fp32 gradient arena (param_list() order)
+    bwd_stats: list                     # per BN layer: float64 (2, width) sums of the BatchNorm backward
+    d_table: Optional[torch.Tensor]     # (copies, sites, 2 * latent): the EncoderC table gradient, summed over the copies in its backward
+
+
+@dataclass(slots=True, eq=False)
+class StepState:
+    """One forward's state for the loss and the backward.  Parts that are absent (an encoder that did not run, no fused
+    reconstruction loss, no fused loss yet) are None."""
+    prec: int
+    B: int
+    train: bool
+    eps: Optional[torch.Tensor] = None
+    logvar: Optional[torch.Tensor] = None
+    n_mod: int = 0
+    enc_a: Optional[list] = None        # [LayerSave]
+    enc_b: Optional[list] = None
+    site: Optional[torch.Tensor] = None
+    dec: Optional[list] = None          # per decoder: (activations, output)
+    zeros: Optional[StepZeros] = None   # the forward's memset when a backward follows; dropped where the backward starts
+    fused: Optional[FusedRecon] = None
+    loss_grads: Optional[LossGrads] = None
+    consumed: bool = False              # the backward ran: buffers are not retained
 
 
 # --------------------------------------------------------------------------------------------
@@ -186,7 +282,7 @@ class EncoderMLP:
         stats_bufs: optional pre-zeroed float64 (2, N) accumulators, one per BN layer."""
         B, dev = x.shape[0], x.device
         adt = act_dtype(prec)
-        saved = []
+        layers = []
         h, pro = x, None
         fin = None            # the BatchNorm finalisation of the layer that produced h, still owed: it rides in the GEMM that consumes h
 
@@ -201,7 +297,7 @@ class EncoderMLP:
                 except L_.MMVAEArgError:
                     pass                                   # refused before anything was enqueued (argument check)
             if fin is not None:
-                ops.bn_finalize(0, 0, None, None, None, None, None, None, None, None, None, None, args=fin)
+                ops.bn_finalize_launch(fin)
                 fin = None
             try:
                 ops.gemm_nt(prec, h, w, N, K, out, bias=bias, prologue=pro, stats=stats, tag=tag, pro_out=pro_out)
@@ -222,48 +318,47 @@ class EncoderMLP:
             # layer's post-activation, 2 bytes per element), which lets this layer's dW GEMM run the plain LDS-DMA kernel instead of
             # redoing the prologue on its Q operand (EncoderB's second Linear: 52 -> 39 us for the dW GEMM)
             h_act = None
-            if want_bwd and pro is not None and ops.can_keep_pro_out(prec, B, N, K, h, y) and pro[2] is not None \
-                    and pro[2].stride(0) % 8 == 0 and pro[2].data_ptr() % 8 == 0:
+            if want_bwd and pro is not None and ops.can_keep_pro_out(prec, B, N, K, h, y) and pro.mask is not None \
+                    and pro.mask.stride(0) % 8 == 0 and pro.mask.data_ptr() % 8 == 0:
                 h_act = torch.empty(B, K, dtype=torch.bfloat16, device=dev)
             if train:
-                stats = stats_bufs[len(saved)] if stats_bufs is not None else torch.zeros(2, N, dtype=torch.float64, device=dev)
-                h_act = consume(N, K, y, pl.bias, pl.w, f"{self.name}.L{len(saved)}.fwd", stats=stats, pro_out=h_act)
+                stats = stats_bufs[len(layers)] if stats_bufs is not None else torch.zeros(2, N, dtype=torch.float64, device=dev)
+                h_act = consume(N, K, y, pl.bias, pl.w, f"{self.name}.L{len(layers)}.fwd", stats=stats, pro_out=h_act)
                 # the finalisation of THIS layer's statistics is owed to whoever reads y next (the next layer or the heads)
                 fin = ops.bn_finalize_args(B, N, stats, bn.weight, bn.bias, bn.running_mean, bn.running_var,
                                            bn.num_batches_tracked, st.mean, st.rstd, st.scale, st.shift, bn.eps,
                                            bn.momentum if bn.momentum is not None else 0.1)
-                mask = masks[len(saved)]
-                new_pro = (st.scale, st.shift, mask, 1.0 / (1.0 - DROP_P))
+                new_pro = Prologue(st.scale, st.shift, masks[len(layers)], 1.0 / (1.0 - DROP_P))
             else:
-                ops.gemm_nt(prec, h, pl.w, N, K, y, bias=pl.bias, prologue=pro, tag=f"{self.name}.L{len(saved)}.fwd")
+                ops.gemm_nt(prec, h, pl.w, N, K, y, bias=pl.bias, prologue=pro, tag=f"{self.name}.L{len(layers)}.fwd")
                 ops.bn_eval_coeffs(bn.weight, bn.bias, bn.running_mean, bn.running_var, st.scale, st.shift, bn.eps, st.mean, st.rstd)
-                new_pro = (st.scale, st.shift, None, 1.0)
-            saved.append((h, pro, y, st, new_pro) if h_act is None else (h_act, None, y, st, new_pro))      # backward's Q operand: plain when kept
+                new_pro = Prologue(st.scale, st.shift, None, 1.0)
+            layers.append(LayerSave(h, pro, y, st, new_pro) if h_act is None else LayerSave(h_act, None, y, st, new_pro))      # backward's Q operand: plain when kept
             h, pro = y, new_pro
         heads = torch.empty(B, 2 * self.latent, dtype=torch.float32, device=dev)
         consume(2 * self.latent, self.pl_heads.K, heads, self.pl_heads.bias, self.pl_heads.w, f"{self.name}.heads.fwd")
-        return heads, saved
+        return heads, layers
 
-    def backward(self, prec, saved, d_heads, grads, tn=ops.gemm_tn, stats_bufs=None, train=True, d_heads_lp=None):
+    def backward(self, prec, layers, d_heads, grads, tn=ops.gemm_tn, stats_bufs=None, train=True, d_heads_lp=None):
         """d_heads: [B][2L] fp32.  grads: dict param -> fp32 view (pre-zeroed, accumulated).
         train=False: the forward ran in eval mode (running statistics, no dropout) -- torch's
         batch_norm(training=False) backward: dy = gamma * rstd * d, no batch-statistics correction."""
         B, dev = d_heads.shape[0], d_heads.device
         adt = act_dtype(prec)
-        nt = (B + TILE - 1) // TILE
         L2 = 2 * self.latent
-        h_in, pro_in, y, st, pro = saved[-1]
         Kl = self.pl_heads.K
         gw = grads[self.fc_mu.weight]            # fc_logvar.weight follows immediately in the arena
         gb = grads[self.fc_mu.bias]
-        tn(prec, d_heads, y, _span(gw, L2 * Kl).view(L2, Kl), _span(gb, L2), L2, Kl, q_prologue=pro, tag=f"{self.name}.heads.dW")
+        tn(prec, d_heads, layers[-1].y, _span(gw, L2 * Kl).view(L2, Kl), _span(gb, L2), L2, Kl, q_prologue=layers[-1].y_prologue, tag=f"{self.name}.heads.dW")
         # gradient entering the last hidden layer: dX GEMM of the heads (A = d_heads, W = heads^T)
         src, src_wt, src_n, src_k = (d_heads_lp if d_heads_lp is not None else d_heads), self.pl_heads.wt, Kl, L2
         for i in reversed(range(len(self.linears))):
             lin, bn, pl = self.linears[i], self.bns[i], self.pl[i]
-            h_in, pro_in, y, st, pro = saved[i]
+            sv = layers[i]
+            y = sv.y
+            st = sv.bn
             N, K = pl.N, pl.K
-            bnargs = (st.scale, st.shift, st.mean, st.rstd, pro[2], pro[3])
+            bnargs = BnBwdEpilogue(st.scale, st.shift, st.mean, st.rstd, sv.y_prologue.mask, sv.y_prologue.inv_keep)
             # BatchNorm/ReLU/Dropout backward of layer i: ONE contraction that stores d = dX * keep * relu' and accumulates
             # (sum d, sum d*xhat); then the BN correction in place (mmvae_bn_bwd_apply) or on the dW GEMM's operand load.
             stats = stats_bufs[i] if stats_bufs is not None else torch.zeros(2, N, dtype=torch.float64, device=dev)
@@ -273,28 +368,28 @@ class EncoderMLP:
             # The finalisation of the backward sums (dgamma, dbeta, the three constants per column) rides in the launch that consumes
             # them -- the first layer's dW GEMM or the in-place correction pass -- instead of a 5 us launch of its own (round 3); the
             # library answers ERR_ARG where its kernels cannot do that (small batches, unusual widths): then the separate launch.
-            fin = (stats, bn.weight, grads[bn.weight], grads[bn.bias], not train)
+            fin = BnBwdFinalize(stats, bn.weight, grads[bn.weight], grads[bn.bias], not train)
             # (not for very wide inputs -- the scaled omics widths: the dW GEMM then has hundreds of K tiles and every one of them
             # would redo the correction of its P rows; one pass over d is cheaper)
             if i == 0 and K <= 4096:
                 # first layer: only the dW GEMM consumes dL/dy -> the correction rides on its operand load, no pass over d
                 if prec == PREC_BF16 and B >= 8192 and N >= 128 and K >= 256:
                     try:
-                        tn(prec, d, h_in, grads[lin.weight], grads[lin.bias], N, K, q_prologue=pro_in,
-                           p_prologue=(y, st.mean, st.rstd, None, fin), tag=f"{self.name}.L{i}.dW")
+                        tn(prec, d, sv.q, grads[lin.weight], grads[lin.bias], N, K, q_prologue=sv.q_prologue,
+                           p_prologue=BnBwdApply(y, st.mean, st.rstd, fin=fin), tag=f"{self.name}.L{i}.dW")
                         continue
                     except L_.MMVAEArgError:
                         pass                                   # refused before anything was enqueued
                 ops.bn_bwd_finalize(B, N, stats, bn.weight, st.rstd, grads[bn.weight], grads[bn.bias], coef, eval_mode=not train)
-                tn(prec, d, h_in, grads[lin.weight], grads[lin.bias], N, K, q_prologue=pro_in,
-                   p_prologue=(y, st.mean, st.rstd, coef), tag=f"{self.name}.L{i}.dW")
+                tn(prec, d, sv.q, grads[lin.weight], grads[lin.bias], N, K, q_prologue=sv.q_prologue,
+                   p_prologue=BnBwdApply(y, st.mean, st.rstd, coef), tag=f"{self.name}.L{i}.dW")
                 continue
             try:
                 ops.bn_bwd_finalize_apply(d, y, B, N, st.mean, st.rstd, *fin)
             except L_.MMVAEArgError:
                 ops.bn_bwd_finalize(B, N, stats, bn.weight, st.rstd, grads[bn.weight], grads[bn.bias], coef, eval_mode=not train)
                 ops.bn_bwd_apply(d, y, N, st.mean, st.rstd, coef)
-            tn(prec, d, h_in, grads[lin.weight], grads[lin.bias], N, K, q_prologue=pro_in, tag=f"{self.name}.L{i}.dW")
+            tn(prec, d, sv.q, grads[lin.weight], grads[lin.bias], N, K, q_prologue=sv.q_prologue, tag=f"{self.name}.L{i}.dW")
             src, src_wt, src_n, src_k = d, pl.wt, K, N
 
 
@@ -389,7 +484,7 @@ class DecoderMLP:
             h = out
         return h, acts
 
-    def backward(self, prec, acts, out, g_out, g_is_logit_grad, dz, accumulate_dz, grads, tn=ops.gemm_tn, d0_out=None):
+    def backward(self, prec, acts, out, g_out, g_is_logit_grad, dz, grads, tn=ops.gemm_tn, d0_out=None):
         """g_out: gradient w.r.t. the decoder output ([B][>=N], fp32 or activation type).  For a
         sigmoid decoder it is w.r.t. the pre-sigmoid logits iff g_is_logit_grad.
         d0_out: where the gradient w.r.t. layer 0's output goes (a column slice of the buffer VAEGraph multiplies with the merged
@@ -409,7 +504,7 @@ class DecoderMLP:
                 ops.gemm_nt(prec, d, pl.wt, pl.K, pl.N, d_prev, epilogue=EPI_RELU_MASK, h=acts[j], tag=f"{self.name}.L{j}.dX")
                 d = d_prev
             elif d0_out is None:
-                ops.gemm_nt(prec, d, pl.wt, pl.K, pl.N, dz, accumulate=accumulate_dz, tag=f"{self.name}.L{j}.dX")
+                ops.gemm_nt(prec, d, pl.wt, pl.K, pl.N, dz, tag=f"{self.name}.L{j}.dX")
 
 
 # --------------------------------------------------------------------------------------------
@@ -425,8 +520,7 @@ class VAEGraph:
         self.decoders = list(decoders)
         self.blocks = [b for b in (enc_a, enc_b, enc_c) if b is not None] + self.decoders
         self.latent = (enc_a or enc_b or enc_c).latent
-        self._prep = None
-        self._prep_key = None
+        self._prep = PrepCache()
         self.dec_stem = None
         self.noise = GLOBAL_NOISE
         self.grad_sync = None          # mmvae.parallel.GradAllReduce (early/final hooks) under data parallelism
@@ -466,30 +560,52 @@ class VAEGraph:
         """Index into the arena where the early all-reduce bucket starts."""
         return sum(p.numel() for b in self.blocks if b not in self.decoders for p in b.params()) + sum(p.numel() for p in self._late_decoder_params())
 
-    def _ensure_prepared(self, prec, device):
-        key = (prec, str(device)) + tuple(p.data_ptr() for p in self.param_list())
-        if self._prep is None or self._prep_key != key:
-            pls = []
-            for b in self.blocks:
-                pls += b.prepare(prec, device)
-            # The first layers of all decoders read the same z (K = latent: one K step): ONE GEMM with their weights concatenated
-            # along N instead of one latency-bound launch per decoder, and ONE dX GEMM (K = sum of their widths) for dL/dz in
-            # backward.  Each decoder continues from / writes into its column slice (widths must keep the slices 16-byte aligned).
-            self.dec_stem = None
-            decs = self.decoders
-            if (len(decs) >= 2 and all(isinstance(d, DecoderMLP) and len(d.linears) >= 2 for d in decs)
-                    and all(d.linears[0].in_features == decs[0].linears[0].in_features and d.linears[0].out_features % 8 == 0 for d in decs)):
-                self.dec_stem = ops.PreparedLinear([d.linears[0].weight for d in decs], [d.linears[0].bias for d in decs], prec, device)
-                pls.append(self.dec_stem)
-            self._prep = ops.WeightPrep(pls, device)
-            self._prep_key = key
-        self._prep.run()
+    def _prepare(self, prec, device):
+        """The PreparedLinears of every block (+ the merged first layers of the decoders): what the preparation cache refreshes."""
+        pls = []
+        for b in self.blocks:
+            pls += b.prepare(prec, device)
+        # The first layers of all decoders read the same z (K = latent: one K step): ONE GEMM with their weights concatenated
+        # along N instead of one latency-bound launch per decoder, and ONE dX GEMM (K = sum of their widths) for dL/dz in
+        # backward.  Each decoder continues from / writes into its column slice (widths must keep the slices 16-byte aligned).
+        self.dec_stem = None
+        decs = self.decoders
+        if (len(decs) >= 2 and all(isinstance(d, DecoderMLP) and len(d.linears) >= 2 for d in decs)
+                and all(d.linears[0].in_features == decs[0].linears[0].in_features and d.linears[0].out_features % 8 == 0 for d in decs)):
+            self.dec_stem = ops.PreparedLinear([d.linears[0].weight for d in decs], [d.linears[0].bias for d in decs], prec, device)
+            pls.append(self.dec_stem)
+        return pls
+
+    def zero_pack(self, device, has_a, has_b, has_site, fwd, bwd):
+        """ONE memset for what a step with these modalities needs zeroed -> StepZeros.  fwd: the forward BatchNorm sums (training);
+        bwd: the flat gradient arena, the backward's BatchNorm sums and the embedding-table gradient; both: the loss accumulators
+        too (three fills before).  The half that was not asked for is empty / None."""
+        widths = (self.enc_a.widths() if has_a else []) + (self.enc_b.widths() if has_b else [])
+        n_sums = 2 * sum(widths)                       # every layer's (2, width) float64 sums are a multiple of 16 bytes: no gaps
+        n_sites = self.enc_c.embedding.weight.shape[0] if has_site else 0
+        n_tab = n_sites * 2 * self.latent * L_.TABLE_COPIES
+        both = fwd and bwd
+        fwd_sums, loss_sums, loss_out5, arena, bwd_sums, d_table = zeros_pack(device, [
+            (n_sums if fwd else 0, torch.float64),
+            (5 if both else 0, torch.float64),
+            (5 if both else 0, torch.float32),
+            (sum(p.numel() for p in self.param_list()) if bwd else 0, torch.float32),
+            (n_sums if bwd else 0, torch.float64),
+            (max(n_tab, 1) if bwd else 0, torch.float32)])
+
+        def per_layer(sums):
+            return [t.view(2, -1) for t in sums.split([2 * w for w in widths])]
+        return StepZeros(fwd_stats=per_layer(fwd_sums) if fwd else [],
+                         loss_ws=(loss_sums, loss_out5) if both else None,
+                         arena=arena if bwd else None,
+                         bwd_stats=per_layer(bwd_sums) if bwd else [],
+                         d_table=d_table[:n_tab].view(-1, n_sites, 2 * self.latent) if bwd and has_site else None)
 
     def forward(self, prec, xa, xb, site, train, want_bwd=False):
-        """Returns (outs(list, fp32), mu, logvar, saved).  want_bwd: a backward will follow (training only) -- decided by the caller
+        """Returns (outs(list, fp32), mu, logvar, state).  want_bwd: a backward will follow (training only) -- decided by the caller
         (functional.run_graph) BEFORE it enters the autograd.Function, inside which grad mode is always off."""
         ref = xa if xa is not None else (xb if xb is not None else site)
-        if not ref.is_cuda:
+        if not ref.is_cuda or any(p.device != ref.device for p in self.param_list()):
             raise RuntimeError(f"the MI355X path needs inputs and parameters on one CUDA/HIP device (input on {ref.device}); "
                                "there is no CPU fallback")
         with ops.pinned_stream():
@@ -498,52 +614,43 @@ class VAEGraph:
     def _forward(self, prec, xa, xb, site, train, want_bwd):
         ref = xa if xa is not None else (xb if xb is not None else site)
         dev, B = ref.device, ref.shape[0]
-        if not ref.is_cuda or any(p.device != dev for p in self.param_list()):
-            raise RuntimeError(f"the MI355X path needs inputs and parameters on one CUDA/HIP device (input on {dev}); "
-                               "there is no CPU fallback")
-        self._ensure_prepared(prec, dev)
-        saved = {"prec": prec, "B": B, "train": train}
+        self._prep.ensure(prec, dev, self.param_list(), self._prepare)
+        state = StepState(prec, B, train)
         heads_a = heads_b = table = None
         Ld = self.latent
         widths_a = self.enc_a.widths() if (train and xa is not None) else []
         widths_b = self.enc_b.widths() if (train and xb is not None) else []
+        n_a = len(widths_a)
         masks, eps = self.noise.draw(B, widths_a + widths_b, Ld, dev)       # eps is sampled in eval mode too (vae.py:73)
         # ONE memset for everything this step needs zeroed: forward BatchNorm sums, the loss accumulators, and -- when a backward will
         # follow -- the flat gradient arena with the backward's BatchNorm sums and embedding-table gradient (three fills before)
-        st_all = []
-        if train:
-            specs = [(2 * w, torch.float64) for w in widths_a + widths_b]
-            nst = len(specs)
-            if want_bwd:
-                specs += [(5, torch.float64), (5, torch.float32)] + self._grad_specs(xa is not None, xb is not None, site is not None)
-            packed = zeros_pack(dev, specs)
-            st_all = [t.view(2, -1) for t in packed[:nst]]
-            if want_bwd:
-                saved["loss_ws"] = (packed[nst], packed[nst + 1])
-                saved["grad_pack"] = packed[nst + 2:]
+        zeros = self.zero_pack(dev, xa is not None, xb is not None, site is not None, fwd=True, bwd=want_bwd) if train else None
+        if want_bwd:
+            state.zeros = zeros
         if xa is not None:
             xa = _check_input(xa, "a", self.enc_a.in_dim, prec)
-            heads_a, saved["enc_a"] = self.enc_a.forward(prec, xa, train, masks[:len(widths_a)] if train else None,
-                                                         st_all[:len(widths_a)] if train else None, want_bwd=want_bwd)
+            heads_a, state.enc_a = self.enc_a.forward(prec, xa, train, masks[:n_a] if train else None,
+                                                      zeros.fwd_stats[:n_a] if train else None, want_bwd=want_bwd)
         if xb is not None:
             xb = _check_input(xb.reshape(xb.shape[0], -1), "b", self.enc_b.in_dim, prec)     # encoders.py:44 view
-            heads_b, saved["enc_b"] = self.enc_b.forward(prec, xb, train, masks[len(widths_a):] if train else None,
-                                                         st_all[len(widths_a):] if train else None, want_bwd=want_bwd)
+            heads_b, state.enc_b = self.enc_b.forward(prec, xb, train, masks[n_a:] if train else None,
+                                                      zeros.fwd_stats[n_a:] if train else None, want_bwd=want_bwd)
         if site is not None:
             if site.dtype != torch.int64:
                 site = site.long()
             site = site.contiguous()
             table = self.enc_c.table()
-            saved["site"] = site
+            state.site = site
         mu = torch.empty(B, Ld, dtype=torch.float32, device=dev)
         logvar = torch.empty(B, Ld, dtype=torch.float32, device=dev)
         z = torch.empty(B, ceil_to(Ld, 8), dtype=act_dtype(prec), device=dev)
         ops.fuse_reparam_fwd(B, Ld, heads_a, heads_b, table, site, eps, mu, logvar, z)
         # .detach(): aliases of the RETURNED tensors, so the saved state holds no reference to objects that own the
-        # autograd node (tensor -> grad_fn -> ctx -> saved -> tensor would be a cycle only the cyclic GC frees,
+        # autograd node (tensor -> grad_fn -> ctx -> state -> tensor would be a cycle only the cyclic GC frees,
         # i.e. every step's activations would pile up in HBM until it runs)
-        saved.update(eps=eps, logvar=logvar.detach(), n_mod=(heads_a is not None) + (heads_b is not None) + (table is not None))
-        outs, saved["dec"] = [None] * len(self.decoders), [None] * len(self.decoders)
+        state.eps, state.logvar = eps, logvar.detach()
+        state.n_mod = (heads_a is not None) + (heads_b is not None) + (table is not None)
+        outs, state.dec = [None] * len(self.decoders), [None] * len(self.decoders)
         order = sorted(range(len(self.decoders)), key=lambda i: -sum(l.weight.numel() for l in self.decoders[i].linears))
         stem = self.dec_stem
         firsts = [None] * len(self.decoders)
@@ -557,61 +664,38 @@ class VAEGraph:
         fused = None
         want = self.fused_recon
         if want is not None and any(t is not None and self.decoders[i].can_fuse_loss(prec) for i, t in enumerate(want)):
-            sums, out5 = saved["loss_ws"] if "loss_ws" in saved else ops.loss_workspace(dev)
-            fused = saved["fused_recon"] = {"sums": sums, "out5": out5, "g": {}, "targets": {}}
+            fused = state.fused = FusedRecon(*(zeros.loss_ws if want_bwd else ops.loss_workspace(dev)), {}, {})
         for i in order:                                 # largest decoder first
             dec = self.decoders[i]
             tgt = want[i] if (fused is not None and want[i] is not None and dec.can_fuse_loss(prec)) else None
             if tgt is not None:
                 k = 1 if dec.final_sigmoid else 0                     # sums[0] = MSE, sums[1] = BCE (mmvae_vae_loss)
-                g, acts = dec.forward(prec, z, fused_loss=(tgt, fused["sums"][k:k + 1]), first=firsts[i])
-                fused["g"][i], fused["targets"][i] = g, tgt
+                g, acts = dec.forward(prec, z, fused_loss=(tgt, fused.sums[k:k + 1]), first=firsts[i])
+                fused.g[i], fused.targets[i] = g, tgt
                 o = torch.empty(1, dtype=torch.float32, device=dev).expand(B, dec.out_dim)     # placeholder: no storage behind it
             else:
                 o, acts = dec.forward(prec, z, first=firsts[i])
             outs[i] = o
-            saved["dec"][i] = (acts, o.detach())
-        return outs, mu, logvar, saved
+            state.dec[i] = (acts, o.detach())
+        return outs, mu, logvar, state
 
-    def _grad_specs(self, has_a, has_b, has_site):
-        """zeros_pack specs of what a backward needs zeroed: [flat gradient arena, BatchNorm-backward sums per BN layer, table gradient]."""
-        wa = self.enc_a.widths() if (has_a and self.enc_a is not None) else []
-        wb = self.enc_b.widths() if (has_b and self.enc_b is not None) else []
-        n_tab = self.enc_c.embedding.weight.shape[0] * 2 * self.latent * L_.TABLE_COPIES if has_site else 0
-        total = sum(p.numel() for p in self.param_list())
-        return [(total, torch.float32)] + [(2 * w, torch.float64) for w in wa + wb] + [(max(n_tab, 1), torch.float32)]
-
-    def alloc_grads(self, device, extra=(), packed=None):
-        """Flat zeroed gradient arena + views per parameter (+ extra zeroed tensors from the same memset; `packed`: tensors the
-        forward already zeroed with _grad_specs)."""
-        params = self.param_list()
-        total = sum(p.numel() for p in params)
-        if packed is None:
-            packed = zeros_pack(device, [(total, torch.float32)] + list(extra))
-        flat = packed[0]
-        views, off = {}, 0
-        for p in params:
-            views[p] = flat[off:off + p.numel()].view(p.shape)
-            off += p.numel()
-        return flat, views, packed[1:]
-
-    def backward(self, saved, g_outs, g_logit_flags, g_mu, g_lv):
+    def backward(self, state, g_outs, g_logit_flags, g_mu, g_lv):
         with ops.pinned_stream():
-            return self._backward(saved, g_outs, g_logit_flags, g_mu, g_lv)
+            return self._backward(state, g_outs, g_logit_flags, g_mu, g_lv)
 
-    def _backward(self, saved, g_outs, g_logit_flags, g_mu, g_lv):
+    def _backward(self, state, g_outs, g_logit_flags, g_mu, g_lv):
         """g_outs[i]: gradient w.r.t. decoder i's output or None; g_mu/g_lv fp32 [B][L] or None.
         Returns (flat_arena, {param: grad view})."""
-        prec, B = saved["prec"], saved["B"]
-        dev = saved["eps"].device
+        prec, B = state.prec, state.B
+        site = state.site
+        dev = state.eps.device
         Ld = self.latent
-        wa = self.enc_a.widths() if "enc_a" in saved else []
-        wb = self.enc_b.widths() if "enc_b" in saved else []
-        site = saved.get("site")
-        n_tab = self.enc_c.embedding.weight.shape[0] * 2 * Ld * L_.TABLE_COPIES if site is not None else 0
-        flat, grads, extra = self.alloc_grads(dev, [(2 * w, torch.float64) for w in wa + wb] + [(max(n_tab, 1), torch.float32)],
-                                              packed=saved.pop("grad_pack", None))
-        st_bwd = [t.view(2, -1) for t in extra[:-1]]
+        zeros, state.zeros = state.zeros, None         # zeroed by the forward's one memset; else (eval-mode forward, no want_bwd) here
+        if zeros is None:
+            zeros = self.zero_pack(dev, state.enc_a is not None, state.enc_b is not None, site is not None, fwd=False, bwd=True)
+        flat = zeros.arena
+        grads = carve_arena(flat, self.param_list())
+        n_a = len(state.enc_a) if state.enc_a is not None else 0
         dzs = []                                       # one dL/dz per decoder; summed in mmvae_fuse_reparam_bwd
         # slab workspace for the split-batch dW GEMMs (<= 64 splits of the largest weight matrix); launches that use it
         # run one after another on one stream, so a single buffer serves them all
@@ -638,16 +722,16 @@ class VAEGraph:
         D0, off = None, 0
         if stem is not None:
             D0 = torch.empty(B, stem.N, dtype=act_dtype(prec), device=dev)
-        for dec, (acts, out), g, is_logit in zip(self.decoders, saved["dec"], g_outs, g_logit_flags):
+        for dec, (acts, out), g, is_logit in zip(self.decoders, state.dec, g_outs, g_logit_flags):
             if g is None:
                 continue
             if stem is not None:
                 n0 = dec.linears[0].out_features
-                dec.backward(prec, acts, out, g, is_logit, None, False, grads, tn, d0_out=D0[:, off:off + n0])
+                dec.backward(prec, acts, out, g, is_logit, None, grads, tn, d0_out=D0[:, off:off + n0])
                 off += n0
                 continue
             dz = torch.empty(B, Ld, dtype=torch.float32, device=dev)
-            dec.backward(prec, acts, out, g, is_logit, dz, False, grads, tn)
+            dec.backward(prec, acts, out, g, is_logit, dz, grads, tn)
             dzs.append(dz)
         if stem is not None:
             dz = torch.empty(B, Ld, dtype=torch.float32, device=dev)
@@ -660,18 +744,16 @@ class VAEGraph:
             # small-output tensors sit in front of the cut: their grouped dW launch stays ONE launch at the end of backward, as on one GPU
             # (round 3; before, data parallelism flushed that launch here: an extra grouped GEMM + reduce per step).
             self.grad_sync.early(flat, self.early_cut())
-        n_mod = saved["n_mod"]
         d_heads = torch.empty(B, 2 * Ld, dtype=torch.float32, device=dev)
-        d_table = extra[-1][:n_tab].view(L_.TABLE_COPIES, -1, 2 * Ld) if site is not None else None
         # bf16 mode: a bf16 copy of d_heads for the heads' dX GEMMs (they round it on load anyway; plain bf16 A -> LDS-DMA kernel)
         d_heads_lp = torch.empty(B, ceil_to(2 * Ld, 8), dtype=torch.bfloat16, device=dev) if prec == PREC_BF16 else None
-        ops.fuse_reparam_bwd(B, Ld, n_mod, g_mu, g_lv, dzs, saved["eps"], saved["logvar"], d_heads, d_table, site, d_heads_lp=d_heads_lp)
-        if "enc_a" in saved:
-            self.enc_a.backward(prec, saved["enc_a"], d_heads, grads, tn, st_bwd[:len(wa)], train=saved["train"], d_heads_lp=d_heads_lp)
-        if "enc_b" in saved:
-            self.enc_b.backward(prec, saved["enc_b"], d_heads, grads, tn, st_bwd[len(wa):], train=saved["train"], d_heads_lp=d_heads_lp)
+        ops.fuse_reparam_bwd(B, Ld, state.n_mod, g_mu, g_lv, dzs, state.eps, state.logvar, d_heads, zeros.d_table, site, d_heads_lp=d_heads_lp)
+        if state.enc_a is not None:
+            self.enc_a.backward(prec, state.enc_a, d_heads, grads, tn, zeros.bwd_stats[:n_a], train=state.train, d_heads_lp=d_heads_lp)
+        if state.enc_b is not None:
+            self.enc_b.backward(prec, state.enc_b, d_heads, grads, tn, zeros.bwd_stats[n_a:], train=state.train, d_heads_lp=d_heads_lp)
         if site is not None:
-            self.enc_c.backward(d_table, grads)
+            self.enc_c.backward(zeros.d_table, grads)
         flush_tiny("tiny_dW.heads")
         if self.grad_sync is not None:
             self.grad_sync.final(flat)

@@ -7,14 +7,19 @@ Two gradient hand-offs exist between the loss and the model:
     autograd and are consumed directly by the backward GEMMs (converted on the fly).
   * fused (what `src.utils.losses.vae_loss` uses when it is given the outputs of one forward
     of our own model): the loss kernel already writes activation-typed gradients
-    (w.r.t. the pre-sigmoid logits for DecoderB) into buffers owned by that forward's saved
-    state; autograd then only carries `None`s plus the scalar grad_output, and no fp32
-    gradient of the size of the reconstructions is ever materialised.
+    (w.r.t. the pre-sigmoid logits for DecoderB) into buffers owned by that forward's
+    `engine.StepState` (its `loss_grads`, an `engine.LossGrads`); autograd then only carries
+    `None`s plus the scalar grad_output, and no fp32 gradient of the size of the
+    reconstructions is ever materialised.
+
+The loss finds the forward through the `OutTag` that `run_graph` leaves on every tensor it returns.
 """
+from typing import NamedTuple
+
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import ops
+from . import engine, ops
 from .ops import ceil_to, act_dtype
 
 
@@ -22,44 +27,39 @@ class VAEGraphFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, graph, prec, train, want_bwd, xa, xb, site, *params):
         ctx.set_materialize_grads(False)
-        outs, mu, logvar, saved = graph.forward(prec, xa, xb, site, train, want_bwd)
-        ctx.graph, ctx.saved, ctx.n_out = graph, saved, len(outs)
-        ctx.param_ids = [id(p) for p in graph.param_list()]
-        graph._last_saved = saved
+        outs, mu, logvar, state = graph.forward(prec, xa, xb, site, train, want_bwd)
+        ctx.graph, ctx.saved, ctx.n_out = graph, state, len(outs)
+        graph._last_saved = state
         return (*outs, mu, logvar)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, *gs):
-        graph, saved, n_out = ctx.graph, ctx.saved, ctx.n_out
-        if saved.get("consumed"):
+        graph, state, n_out = ctx.graph, ctx.saved, ctx.n_out
+        if state.consumed:
             raise RuntimeError("backward through this forward was already run (buffers are not retained)")
         g_outs = [None if g is None else _as_rows(g) for g in gs[:n_out]]
         g_mu = None if gs[n_out] is None else gs[n_out].contiguous().float()
         g_lv = None if gs[n_out + 1] is None else gs[n_out + 1].contiguous().float()
         flags = [False] * n_out
-        stash = saved.get("loss_grads")
-        if stash is not None and stash.get("armed"):                 # the loss handle's backward ran: its gradients are the stash
-            if stash.get("scale") is not None:                       # None: unit_grad promised by the caller (fused_loss)
-                ops.scale_many(list(stash["g_outs"]) + [stash["g_mu"], stash["g_lv"]], stash["scale"])       # one launch, not five
-            for i in range(n_out):
-                sg = stash["g_outs"][i]
+        lg = state.loss_grads
+        if lg is not None and lg.armed:                              # the loss handle's backward ran: its gradients are the ones to use
+            if lg.scale is not None:                                 # None: unit_grad promised by the caller (fused_loss)
+                ops.scale_many(list(lg.g_outs) + [lg.g_mu, lg.g_lv], lg.scale)       # one launch, not five
+            for i, sg in enumerate(lg.g_outs):
                 if sg is None:
                     continue
                 if g_outs[i] is not None:            # rare: another loss term also touched this output
-                    sg[:, :g_outs[i].shape[1]] += _to_stash_space(g_outs[i], saved["dec"][i][1], graph.decoders[i], sg.dtype)
+                    sg[:, :g_outs[i].shape[1]] += _to_stash_space(g_outs[i], state.dec[i][1], graph.decoders[i], sg.dtype)
                 g_outs[i], flags[i] = sg, graph.decoders[i].final_sigmoid
-            for key, cur in (("g_mu", g_mu), ("g_lv", g_lv)):
-                sg = stash[key]
+            for sg, cur in ((lg.g_mu, g_mu), (lg.g_lv, g_lv)):
                 if cur is not None:
                     sg += cur
-            g_mu, g_lv = stash["g_mu"], stash["g_lv"]
-        flat, grads = graph.backward(saved, g_outs, flags, g_mu, g_lv)
-        saved["consumed"] = True
-        used = _participating(graph, saved, g_outs)
-        out = []
-        for p in graph.param_list():
-            out.append(grads[p] if id(p) in used else None)
+            g_mu, g_lv = lg.g_mu, lg.g_lv
+        flat, grads = graph.backward(state, g_outs, flags, g_mu, g_lv)
+        state.consumed = True
+        used = _participating(graph, state, g_outs)
+        out = [grads[p] if id(p) in used else None for p in graph.param_list()]
         del grads                                     # keep the views unique so autograd can adopt them
         return (None, None, None, None, None, None, None, *out)
 
@@ -78,21 +78,18 @@ def _to_stash_space(g, out, dec, dtype):
     return g.to(dtype)
 
 
-def _participating(graph, saved, g_outs):
-    used = set()
-    blocks = []
-    if "enc_a" in saved:
-        blocks.append(graph.enc_a)
-    if "enc_b" in saved:
-        blocks.append(graph.enc_b)
-    if "site" in saved:
-        blocks.append(graph.enc_c)
-    for dec, g in zip(graph.decoders, g_outs):
-        if g is not None:
-            blocks.append(dec)
-    for b in blocks:
-        used.update(id(p) for p in b.params())
-    return used
+def _participating(graph, state, g_outs):
+    """ids of the parameters of the blocks that took part: the encoders that ran and the decoders a gradient arrived for."""
+    blocks = [b for b, ran in ((graph.enc_a, state.enc_a), (graph.enc_b, state.enc_b), (graph.enc_c, state.site)) if ran is not None]
+    blocks += [dec for dec, g in zip(graph.decoders, g_outs) if g is not None]
+    return {id(p) for b in blocks for p in b.params()}
+
+
+class OutTag(NamedTuple):
+    """Marks a tensor that run_graph returned (`t._mmvae`): the forward that made it and which of its outputs it is."""
+    state: engine.StepState
+    kind: str                       # "out" (a decoder's output) | "mu" | "logvar"
+    index: int                      # the decoder, for "out"
 
 
 def run_graph(graph, prec, train, xa, xb, site):
@@ -104,14 +101,13 @@ def run_graph(graph, prec, train, xa, xb, site):
     res = VAEGraphFn.apply(graph, prec, train, want_bwd, xa, xb, site, *params)
     n = len(graph.decoders)
     outs, mu, logvar = list(res[:n]), res[n], res[n + 1]
-    saved = graph._last_saved
+    state = graph._last_saved
     graph._last_saved = None
     if torch.is_grad_enabled() and any(p.requires_grad for p in params):
-        tag = {"saved": saved, "inputs": (xa, xb, site)}
         for i, o in enumerate(outs):
-            o._mmvae = (tag, "out", i)
-        mu._mmvae = (tag, "mu", 0)
-        logvar._mmvae = (tag, "logvar", 0)
+            o._mmvae = OutTag(state, "out", i)
+        mu._mmvae = OutTag(state, "mu", 0)
+        logvar._mmvae = OutTag(state, "logvar", 0)
     return outs, mu, logvar
 
 
@@ -120,20 +116,21 @@ def run_graph(graph, prec, train, xa, xb, site):
 # --------------------------------------------------------------------------------------------
 class _LossHandleFn(torch.autograd.Function):
     """Connects the fused loss value to the model's autograd node; gradients travel through the
-    stash (see module docstring), autograd only delivers grad_output."""
+    forward's LossGrads (see module docstring), autograd only delivers grad_output."""
 
     @staticmethod
-    def forward(ctx, total, stash, *model_outputs):
-        ctx.stash = stash
+    def forward(ctx, total, loss_grads, *model_outputs):
+        ctx.loss_grads = loss_grads
+        ctx.n_outputs = len(model_outputs)
         return total.view(())            # a view of the kernel's output buffer (not of an input that requires grad): no copy launch
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        if not ctx.stash.get("unit_grad"):
-            ctx.stash["scale"] = g.reshape(1).float().contiguous()
-        ctx.stash["armed"] = True
-        return (None, None) + (None,) * 16
+        if not ctx.loss_grads.unit_grad:
+            ctx.loss_grads.scale = g.reshape(1).float().contiguous()
+        ctx.loss_grads.armed = True
+        return (None,) * (2 + ctx.n_outputs)
 
 
 class _LossGeneralFn(torch.autograd.Function):
@@ -157,11 +154,6 @@ class _LossGeneralFn(torch.autograd.Function):
                 ops.scale_if_needed(t, scale)
             out.append(t)
         return (None, *out)
-
-
-def engine_noise():
-    from . import engine
-    return engine.GLOBAL_NOISE
 
 
 def _tag_of(t):
@@ -207,8 +199,6 @@ def _fused_loss(terms, beta, gamma, class_weights=None, unit_grad=False, beta_ga
     Returns (total (0-dim tensor, differentiable), out5 (device fp32 [total, recon, class, kld, labels out of range]))."""
     any_t = next(v[0] for v in terms.values() if v is not None)
     dev, B = any_t.device, any_t.shape[0]
-    if not any_t.is_cuda:
-        raise RuntimeError("the MI355X loss kernel needs CUDA/HIP tensors; there is no CPU fallback")
     ra, a = terms.get("a") or (None, None)
     rb, b = terms.get("b") or (None, None)
     lg, site = terms.get("c") or (None, None)
@@ -224,19 +214,21 @@ def _fused_loss(terms, beta, gamma, class_weights=None, unit_grad=False, beta_ga
     # reconstruction terms whose loss already ran inside the decoder's last GEMM (engine.VAEGraph.fused_recon): the "reconstruction"
     # is a placeholder, its loss sum sits in the forward's accumulators and its gradient in the forward's saved state
     fused, fused_idx = None, {}
+    placeholders = []                                  # the tensors that stand in for those reconstructions
     for key, (r, t) in (("a", (ra, a)), ("b", (rb, b))):
-        tg = _tag_of(r) if r is not None else None
-        fr = tg[0]["saved"].get("fused_recon") if tg is not None else None
-        if fr is not None and tg[1] == "out" and tg[2] in fr["g"]:
-            if fr["targets"][tg[2]].data_ptr() != t.data_ptr() or tuple(fr["targets"][tg[2]].shape) != tuple(t.shape):
+        tg = _tag_of(r)
+        fr = tg.state.fused if tg is not None else None
+        if fr is not None and tg.kind == "out" and tg.index in fr.g:
+            if fr.targets[tg.index].data_ptr() != t.data_ptr() or tuple(fr.targets[tg.index].shape) != tuple(t.shape):
                 raise RuntimeError("fused reconstruction loss: the target passed to the loss is not the tensor the forward was given")
-            fused, fused_idx[key] = fr, tg[2]
+            fused, fused_idx[key] = fr, tg.index
+            placeholders.append(r)
     if fused is not None and not (torch.is_grad_enabled()):
         raise RuntimeError("fused reconstruction loss needs the training step (gradients enabled)")
     if "a" in fused_idx:
-        ra_keep, ra = ra, None
+        ra = None
     if "b" in fused_idx:
-        rb_keep, rb = rb, None
+        rb = None
 
     def prep(x):
         return None if x is None else (x if (x.dtype == torch.float32 and x.stride(-1) == 1) else x.float().contiguous())
@@ -247,50 +239,46 @@ def _fused_loss(terms, beta, gamma, class_weights=None, unit_grad=False, beta_ga
     if mu_ is not None:
         mu_, lv_ = mu_.contiguous(), lv_.contiguous()
     if fused is not None:
-        sums, out4 = fused["sums"], fused["out5"]         # the decoders' GEMMs have already added their terms
+        sums, out4 = fused.sums, fused.out5               # the decoders' GEMMs have already added their terms
     else:
         sums = out4 = None                                 # out4: [total, recon, class, kld, labels out of range]
 
     # ---- fused hand-off: all differentiable inputs are outputs of ONE forward of our model --------------------
     tags = [_tag_of(t) for t in (ra, rb, lg, mu, lv) if t is not None and t.requires_grad]
-    tag = tags[0][0] if tags and all(t is not None and t[0] is tags[0][0] for t in tags) else None
-    if need_grad and tag is not None and not tag["saved"].get("consumed") and "loss_grads" not in tag["saved"]:
-        saved = tag["saved"]
+    state = tags[0].state if tags and all(t is not None and t.state is tags[0].state for t in tags) else None
+    if need_grad and state is not None and not state.consumed and state.loss_grads is None:
         if sums is None:
-            sums, out4 = saved.pop("loss_ws", None) or ops.loss_workspace(dev)     # zeroed by the forward's one memset
-        adt = act_dtype(saved["prec"])
-        n_dec = len(saved["dec"])
-        g_outs = [None] * n_dec
+            zeros = state.zeros
+            if zeros is not None and zeros.loss_ws is not None:                    # zeroed by the forward's one memset; taken once
+                (sums, out4), zeros.loss_ws = zeros.loss_ws, None
+            else:
+                sums, out4 = ops.loss_workspace(dev)
+        adt = act_dtype(state.prec)
+        g_outs = [None] * len(state.dec)
         for key, i in fused_idx.items():
-            g_outs[i] = fused["g"][i]
+            g_outs[i] = fused.g[i]
         ga = gb = gc = None
         if ra is not None and ra.requires_grad:
             ga = torch.empty(B, ceil_to(ra.shape[1], 8), dtype=adt, device=dev)
-            g_outs[_tag_of(ra)[2]] = ga
+            g_outs[_tag_of(ra).index] = ga
         if rb is not None and rb.requires_grad:
             gb = torch.empty(B, ceil_to(rb.shape[1], 8), dtype=adt, device=dev)
-            g_outs[_tag_of(rb)[2]] = gb
+            g_outs[_tag_of(rb).index] = gb
         if lg is not None and lg.requires_grad:
             gc = torch.empty(B, lg.shape[1], dtype=torch.float32, device=dev)
-            g_outs[_tag_of(lg)[2]] = gc
+            g_outs[_tag_of(lg).index] = gc
         g_mu = torch.empty(B, mu.shape[1], dtype=torch.float32, device=dev) if mu is not None else None
         g_lv = torch.empty_like(g_mu) if mu is not None else None
         ops.vae_loss(B, recon_a=ra_, a=a_, recon_b=rb_, b=b_, logits=lg_, site=site, class_weights=cw, mu=mu_, logvar=lv_,
                      beta=beta, gamma=gamma, sums=sums, g_a=ga, g_b=gb, grad_b_wrt_logit=True, g_c=gc, g_mu=g_mu, g_lv=g_lv,
                      beta_gamma_dev=beta_gamma_dev)
         ops.loss_finalize(sums, beta, gamma, out4, beta_gamma_dev)
-        stash = {"g_outs": g_outs, "g_mu": g_mu, "g_lv": g_lv, "scale": None, "unit_grad": bool(unit_grad)}
         if g_mu is None:                       # KL term absent: nothing flows into mu/logvar from this loss
-            stash["g_mu"] = torch.zeros(B, saved["logvar"].shape[1], dtype=torch.float32, device=dev)
-            stash["g_lv"] = torch.zeros_like(stash["g_mu"])
-        saved["loss_grads"] = stash
-        pads = [t for t in (ra, rb, lg, mu, lv) if t is not None]
-        if "a" in fused_idx:
-            pads.append(ra_keep)
-        if "b" in fused_idx:
-            pads.append(rb_keep)
-        pads += [None] * (16 - len(pads))
-        total = _LossHandleFn.apply(out4[0], stash, *pads)
+            g_mu = torch.zeros(B, state.logvar.shape[1], dtype=torch.float32, device=dev)
+            g_lv = torch.zeros_like(g_mu)
+        state.loss_grads = engine.LossGrads(g_outs=g_outs, g_mu=g_mu, g_lv=g_lv, unit_grad=bool(unit_grad))
+        pads = [t for t in (ra, rb, lg, mu, lv) if t is not None] + placeholders
+        total = _LossHandleFn.apply(out4[0], state.loss_grads, *pads)
         return total, out4
 
     if fused is not None:
@@ -342,7 +330,7 @@ class ReparamFn(torch.autograd.Function):
             raise RuntimeError(f"reparameterize: expected two (B, L) tensors, got {tuple(mu.shape)} and {tuple(logvar.shape)}")
         B, Ld = mu.shape
         heads = torch.cat([mu.detach().float(), logvar.detach().float()], dim=1).contiguous()
-        eps = engine_noise().draw(B, [], Ld, mu.device)[1]
+        eps = engine.GLOBAL_NOISE.draw(B, [], Ld, mu.device)[1]
         mu_o, lv_o = torch.empty_like(heads[:, :Ld]).contiguous(), torch.empty_like(heads[:, :Ld]).contiguous()
         z = torch.empty(B, Ld, dtype=torch.float32, device=mu.device)
         with ops.pinned_stream():
@@ -363,42 +351,32 @@ class ReparamFn(torch.autograd.Function):
 # --------------------------------------------------------------------------------------------
 # stand-alone blocks (EncoderA/B/C and DecoderA/B/C used on their own)
 # --------------------------------------------------------------------------------------------
-class BlockRuntime:
+class BlockRuntime(engine.PrepCache):
     """Weight preparation cache for one block used outside a VAEGraph."""
 
     def __init__(self, block):
-        self.block, self._prep, self._key = block, None, None
+        super().__init__()
+        self.block = block
 
     def ensure(self, prec, device):
-        key = (prec, str(device)) + tuple(p.data_ptr() for p in self.block.params())
-        if self._prep is None or key != self._key:
-            pls = self.block.prepare(prec, device)
-            self._prep = ops.WeightPrep(pls, device) if pls else None
-            self._key = key
-        if self._prep is not None:
-            self._prep.run()
+        super().ensure(prec, device, self.block.params(), self.block.prepare)
 
 
-def _alloc_block_grads(block, device):
+def _zero_grads(block, device):
+    """{param: zeroed fp32 gradient view}: the block's own flat arena (one fill launch)."""
     params = block.params()
-    flat = torch.zeros(sum(p.numel() for p in params), dtype=torch.float32, device=device)
-    views, off = {}, 0
-    for p in params:
-        views[p] = flat[off:off + p.numel()].view(p.shape)
-        off += p.numel()
-    return views
+    return engine.carve_arena(torch.zeros(sum(p.numel() for p in params), dtype=torch.float32, device=device), params)
 
 
 class EncoderMLPFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, rt, prec, train, noise, x, *params):
-        from .engine import _check_input
         ctx.set_materialize_grads(False)
-        x = _check_input(x.reshape(x.shape[0], -1), "x", rt.block.in_dim, prec)
+        x = engine._check_input(x.reshape(x.shape[0], -1), "x", rt.block.in_dim, prec)
         rt.ensure(prec, x.device)
         masks = noise.draw(x.shape[0], rt.block.widths(), None, x.device)[0] if train else None
-        heads, saved = rt.block.forward(prec, x, train, masks)
-        ctx.rt, ctx.prec, ctx.saved, ctx.train = rt, prec, saved, train
+        heads, layers = rt.block.forward(prec, x, train, masks)
+        ctx.rt, ctx.prec, ctx.layers, ctx.train = rt, prec, layers, train
         Ld = rt.block.latent
         return heads[:, :Ld], heads[:, Ld:]
 
@@ -407,14 +385,14 @@ class EncoderMLPFn(torch.autograd.Function):
     def backward(ctx, g_mu, g_lv):
         blk = ctx.rt.block
         Ld = blk.latent
-        y = ctx.saved[-1][2]
+        y = ctx.layers[-1].y
         d_heads = torch.zeros(y.shape[0], 2 * Ld, dtype=torch.float32, device=y.device)
         if g_mu is not None:
             d_heads[:, :Ld].copy_(g_mu)
         if g_lv is not None:
             d_heads[:, Ld:].copy_(g_lv)
-        grads = _alloc_block_grads(blk, y.device)
-        blk.backward(ctx.prec, ctx.saved, d_heads, grads, train=ctx.train)
+        grads = _zero_grads(blk, y.device)
+        blk.backward(ctx.prec, ctx.layers, d_heads, grads, train=ctx.train)
         out = [grads[p] for p in blk.params()]
         del grads
         return (None, None, None, None, None, *out)
@@ -449,7 +427,7 @@ class EmbedEncoderFn(torch.autograd.Function):
         d_table = torch.zeros(blk.embedding.weight.shape[0], 2 * Ld, dtype=torch.float32, device=dev)
         # dz = 0 and eps = 0: the kernel reduces to the scatter-add of (g_mu | g_lv) by class
         ops.fuse_reparam_bwd(B, Ld, 1, g_mu, g_lv, [zeros], zeros, zeros, d_heads, d_table, site)
-        grads = _alloc_block_grads(blk, dev)
+        grads = _zero_grads(blk, dev)
         blk.backward(d_table, grads)
         out = [grads[p] for p in blk.params()]
         del grads
@@ -480,8 +458,8 @@ class DecoderFn(torch.autograd.Function):
             return (None,) * (3 + len(blk.params()))
         g = _as_rows(g)
         dz = torch.zeros(g.shape[0], ctx.Ld, dtype=torch.float32, device=g.device)
-        grads = _alloc_block_grads(blk, g.device)
-        blk.backward(ctx.prec, ctx.acts, ctx.out, g, False, dz, False, grads)
+        grads = _zero_grads(blk, g.device)
+        blk.backward(ctx.prec, ctx.acts, ctx.out, g, False, dz, grads)
         out = [grads[p] for p in blk.params()]
         del grads
         return (None, None, dz if ctx.z_needs else None, *out)

@@ -21,8 +21,8 @@ step is cut into graphs at the points where a collective is issued eagerly on th
   * overlap=False: TWO graphs -- [forward, loss, backward] | [AdamW] -- with ONE all-reduce of the whole arena in between."""
 import torch
 
+from . import engine, ops
 from . import functional as F_
-from . import ops
 
 
 class GraphedTrainStep:
@@ -115,16 +115,14 @@ class GraphedTrainStep:
         return self._step()
 
     def _step(self):
-        total, out4 = self._forward_loss()
-        self.optimizer.zero_grad(set_to_none=True)
-        total.backward(self._one)                               # static ones: no fill launch, no gradient-scaling launch
+        out4 = self._fwd_bwd()
         self.optimizer.step()
         return out4
 
     def _fwd_bwd(self):
         total, out4 = self._forward_loss()
         self.optimizer.zero_grad(set_to_none=True)
-        total.backward(self._one)
+        total.backward(self._one)                               # static ones: no fill launch, no gradient-scaling launch
         return out4
 
     def _flat_grads(self):
@@ -149,7 +147,7 @@ class GraphedTrainStep:
                     raise ValueError("preserve_state needs at least one (undone) warm-up step")
                 dev = self.a.device
                 snap = ({k: v.clone() for k, v in self.model.state_dict().items()}, self.optimizer.snapshot(),
-                        F_.engine_noise().state_dict(dev))
+                        engine.GLOBAL_NOISE.state_dict(dev))
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):                        # eager warm-up: builds weight / optimiser tables, allocator pools
@@ -168,7 +166,7 @@ class GraphedTrainStep:
                     for k, v in snap[0].items():
                         cur[k].copy_(v)
                 self.optimizer.restore(snap[1])
-                F_.engine_noise().load_state_dict(snap[2], self.a.device)
+                engine.GLOBAL_NOISE.load_state_dict(snap[2], self.a.device)
                 torch.cuda.synchronize()
             self.graph = torch.cuda.CUDAGraph()
             self.graph_mid = None

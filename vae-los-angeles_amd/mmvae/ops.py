@@ -1,7 +1,7 @@
 """Tensor-level wrappers over the C ABI (include/mmvae_hip.h).  PyTorch is used here only as
 the owner of device memory and streams; all arithmetic happens in libmmvae_hip.so."""
 import ctypes as C
-
+from collections import namedtuple
 
 import torch
 
@@ -47,21 +47,28 @@ PROBE = None
 
 
 class probe_span:
-    """`with probe_span(tag, bytes)`: brackets a non-GEMM launch with events when a KernelProbe is installed (bench.py's
-    survey of the step); `nbytes` = algorithmic HBM bytes of the launch (operands read once + results written once)."""
+    """`with probe_span(tag, meta)`: brackets a launch with events when a KernelProbe is installed (bench.py's survey of the step);
+    `meta` is the record's dict or a callable producing it (called only when the span is timed).  A launch the library refused
+    (it enqueued nothing) leaves no record."""
 
-    def __init__(self, tag, nbytes):
-        self.tag, self.nbytes, self.t0 = tag, nbytes, None
+    def __init__(self, tag, meta):
+        self.tag, self.meta, self.t0 = tag, meta, None
 
     def __enter__(self):
         if PROBE is not None and PROBE.wants(self.tag):
             self.t0 = PROBE.begin()
         return self
 
-    def __exit__(self, *exc):
-        if self.t0 is not None:
-            PROBE.end(self.tag, self.t0, dict(kind="stream", bytes=int(self.nbytes() if callable(self.nbytes) else self.nbytes)))
+    def __exit__(self, exc_type, *exc):
+        if self.t0 is not None and exc_type is None:
+            PROBE.end(self.tag, self.t0, self.meta() if callable(self.meta) else self.meta)
         return False
+
+
+def stream_span(tag, nbytes):
+    """probe_span of a non-GEMM launch; `nbytes` = its algorithmic HBM bytes (operands read once + results written once), or a
+    callable producing them."""
+    return probe_span(tag, lambda: dict(kind="stream", bytes=int(nbytes() if callable(nbytes) else nbytes)))
 
 
 def ceil_to(x, m):
@@ -141,7 +148,7 @@ def rows_to_bf16(src, dst):
     ld = _ld(dst)
     if dst.untyped_storage().nbytes() < dst.storage_offset() * 2 + B * ld * 2:
         raise ValueError("rows_to_bf16: dst must own whole padded rows (B x ld elements)")
-    with probe_span("rows_to_bf16", B * F * src.element_size() + B * ld * 2):
+    with stream_span("rows_to_bf16", B * F * src.element_size() + B * ld * 2):
         L.check(L.load().mmvae_rows_to_bf16(src.data_ptr(), _dt(src), _ld(src), dst.data_ptr(), ld, B, F, _stream()), "mmvae_rows_to_bf16")
     return dst
 
@@ -229,16 +236,9 @@ class WeightPrep:
         arr = (L.PrepItem * self.n)(*items)
         host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
         self.table = host.to(device)
-        self._keys = self._current_keys()
-
-    def _current_keys(self):
-        return tuple(w.data_ptr() for pl in self.linears for w in pl.srcs + pl.bias_srcs)
-
-    def stale(self):
-        return self._keys != self._current_keys()
 
     def run(self):
-        with probe_span("prep_weights", lambda: sum(6 * w.numel() for pl in self.linears for w in pl.srcs)):
+        with stream_span("prep_weights", lambda: sum(6 * w.numel() for pl in self.linears for w in pl.srcs)):
             L.check(L.load().mmvae_prep_weights(self.table.data_ptr(), self.n, _stream()), "mmvae_prep_weights")
 
 
@@ -254,11 +254,32 @@ def can_keep_pro_out(prec, M, N, K, a, out):
             and a.data_ptr() % 16 == 0 and out.data_ptr() % 128 == 0)
 
 
+# The operand records of the GEMMs.  The wrappers below unpack them by position, so a plain tuple of the same fields serves too.
+# Prologue: BatchNorm + ReLU + Dropout applied to an operand on load, relu(x * scale + shift) * mask * inv_keep (mask None: no dropout).
+Prologue = namedtuple("Prologue", "scale shift mask inv_keep")
+# BnBwdEpilogue: the `bn=` operand of EPI_BN_BWD -- the layer's BatchNorm vectors and the dropout mask its output went through.
+BnBwdEpilogue = namedtuple("BnBwdEpilogue", "scale shift mean rstd mask inv_keep")
+# BnBwdFinalize: operands of mmvae_bn_bwd_finalize folded into the launch that consumes the backward sums (stats: float64 [2][N]).
+BnBwdFinalize = namedtuple("BnBwdFinalize", "stats gamma dgamma dbeta eval_mode")
+# BnBwdApply: `p_prologue` of a dW GEMM -- the BatchNorm-backward correction applied on the load of p, from the three constants per
+# column (`coef`) or, with the finalisation folded into the GEMM, from the sums themselves (`fin`, a BnBwdFinalize).
+BnBwdApply = namedtuple("BnBwdApply", "y mean rstd coef fin", defaults=(None, None))
+
+
+def _fill_prologue(g, prologue):
+    """The BN+ReLU+Dropout prologue fields that GemmNtArgs and GemmTnArgs share; -> the prologue code."""
+    sc, sh, mask, inv_keep = prologue
+    g.pro_scale, g.pro_shift, g.pro_mask = sc.data_ptr(), sh.data_ptr(), _p(mask)
+    g.ld_pro_mask = _ld(mask) if mask is not None else 0
+    g.pro_inv_keep = inv_keep
+    return PRO_BN_RELU_DROP
+
+
 def gemm_nt(prec, a, w_lp, N, K, out, *, bias=None, act=ACT_NONE, accumulate=False, prologue=None,
             epilogue=EPI_STORE, h=None, bn=None, bn_coef=None, bn_phase=None, stats=None, loss_sum=None, tag=None, pro_out=None,
             pro_finalize=None):
-    """out[M,N] = epi( pro(a)[M,K] @ W[N,K]^T ).  prologue = (scale, shift, mask|None, inv_keep);
-    bn = (scale, shift, mean, rstd, mask|None, inv_keep) for EPI_BN_BWD (out=None, stats given:
+    """out[M,N] = epi( pro(a)[M,K] @ W[N,K]^T ).  prologue = Prologue / (scale, shift, mask|None, inv_keep);
+    bn = BnBwdEpilogue / (scale, shift, mean, rstd, mask|None, inv_keep) for EPI_BN_BWD (out=None, stats given:
     statistics phase; out and bn_coef given: apply phase).  stats: zeroed float64 [2][N] accumulator.
     EPI_LOSS_MSE / EPI_LOSS_BCE_LOGIT: h = fp32 or bf16 target (rows 2-byte aligned; padded bf16 rows give the widest loads),
     out = bf16 gradient, loss_sum = one-element float64 view that is added to."""
@@ -270,11 +291,7 @@ def gemm_nt(prec, a, w_lp, N, K, out, *, bias=None, act=ACT_NONE, accumulate=Fal
     g.prec, g.M, g.N, g.K = prec, M, N, K
     g.a, g.a_dtype, g.lda = a.data_ptr(), _dt(a), _ld(a)
     if prologue is not None:
-        sc, sh, mask, inv_keep = prologue
-        g.prologue = PRO_BN_RELU_DROP
-        g.pro_scale, g.pro_shift, g.pro_mask = sc.data_ptr(), sh.data_ptr(), _p(mask)
-        g.ld_pro_mask = _ld(mask) if mask is not None else 0
-        g.pro_inv_keep = inv_keep
+        g.prologue = _fill_prologue(g, prologue)
         if pro_out is not None:                 # the operand after the prologue (bf16 [M][>= K]); see can_keep_pro_out()
             g.pro_out, g.ld_pro_out = pro_out.data_ptr(), _ld(pro_out)
         if pro_finalize is not None:            # BnFinalizeArgs of the layer that produced `a` (bn_finalize_args()): finalised inside this launch
@@ -298,13 +315,11 @@ def gemm_nt(prec, a, w_lp, N, K, out, *, bias=None, act=ACT_NONE, accumulate=Fal
     if loss_sum is not None:
         assert loss_sum.dtype == torch.float64 and h is not None and h.dtype in (torch.float32, torch.bfloat16)
         g.stat1, g.h_dtype = loss_sum.data_ptr(), _dt(h)
-    t0 = PROBE.begin() if (PROBE is not None and PROBE.wants(tag)) else None
-    L.check(L.load().mmvae_gemm_nt(C.byref(g), _stream()), "mmvae_gemm_nt")
-    if t0 is not None:
-        PROBE.end(tag, t0, dict(kind="nt", M=M, N=N, K=K, a_bytes=a.element_size(),
-                                c_bytes=0 if out is None else out.element_size(),
-                                pro=prologue is not None, pro_mask=prologue is not None and prologue[2] is not None,
-                                epi=epilogue, epi_mask=bn is not None and bn[4] is not None, act_bytes=2 if prec == PREC_BF16 else 4))
+    with probe_span(tag, lambda: dict(kind="nt", M=M, N=N, K=K, a_bytes=a.element_size(),
+                                      c_bytes=0 if out is None else out.element_size(),
+                                      pro=prologue is not None, pro_mask=g.pro_mask is not None,
+                                      epi=epilogue, epi_mask=g.epi_mask is not None, act_bytes=2 if prec == PREC_BF16 else 4)):
+        L.check(L.load().mmvae_gemm_nt(C.byref(g), _stream()), "mmvae_gemm_nt")
     return out
 
 
@@ -315,13 +330,9 @@ def _tn_args(prec, p, q, dw, db, N, K, q_prologue, p_prologue, nsplit, slab):
     g.p, g.p_dtype, g.ldp = p.data_ptr(), _dt(p), _ld(p)
     g.q, g.q_dtype, g.ldq = q.data_ptr(), _dt(q), _ld(q)
     if q_prologue is not None:
-        sc, sh, mask, inv_keep = q_prologue
-        g.q_prologue = PRO_BN_RELU_DROP
-        g.pro_scale, g.pro_shift, g.pro_mask = sc.data_ptr(), sh.data_ptr(), _p(mask)
-        g.ld_pro_mask = _ld(mask) if mask is not None else 0
-        g.pro_inv_keep = inv_keep
+        g.q_prologue = _fill_prologue(g, q_prologue)
     if p_prologue is not None:
-        py, mean, rstd, coef = p_prologue[:4]
+        py, mean, rstd, coef, *fin = p_prologue             # (y, mean, rstd, coef), or a BnBwdApply with its fifth field
         _mat(py, "p_y")
         g.p_prologue = PRO_BN_BWD_APPLY
         g.p_y, g.ld_py, g.p_mean, g.p_rstd = py.data_ptr(), _ld(py), mean.data_ptr(), rstd.data_ptr()
@@ -329,8 +340,7 @@ def _tn_args(prec, p, q, dw, db, N, K, q_prologue, p_prologue, nsplit, slab):
             assert py.dtype == p.dtype and coef.shape[0] == 3 and coef.shape[1] == N and coef.is_contiguous()
             g.p_coef = coef.data_ptr()
         else:
-            # mmvae_bn_bwd_finalize folded into the GEMM: p_prologue = (y, mean, rstd, None, (stats f64 [2][N], gamma, dgamma, dbeta, eval_mode))
-            stats, gamma, dgamma, dbeta, eval_mode = p_prologue[4]
+            stats, gamma, dgamma, dbeta, eval_mode = fin[0]   # BnBwdFinalize: mmvae_bn_bwd_finalize folded into the GEMM
             assert py.dtype == p.dtype and stats.dtype == torch.float64 and stats.shape[0] == 2 and stats.stride(1) == 1
             g.p_sum_d, g.p_sum_dx, g.p_gamma = stats[0].data_ptr(), stats[1].data_ptr(), gamma.data_ptr()
             g.p_dgamma, g.p_dbeta, g.p_eval_mode = dgamma.data_ptr(), dbeta.data_ptr(), int(eval_mode)
@@ -360,7 +370,7 @@ def gemm_tn_group(prec, problems, slab, tag="tiny_dW.group"):
             arr[j] = _tn_args(prec, pr["p"], pr["q"], pr["dw"], pr["db"], pr["N"], pr["K"], pr.get("q_prologue"), None, 0, slab[off:off + need])
             off += need
             nbytes += pr["p"].shape[0] * (pr["N"] * pr["p"].element_size() + pr["K"] * pr["q"].element_size()) + 4 * pr["N"] * pr["K"]
-        with probe_span(tag if i == 0 else f"{tag}.{i}", nbytes):
+        with stream_span(tag if i == 0 else f"{tag}.{i}", nbytes):
             status = lib.mmvae_gemm_tn_group(C.cast(arr, C.c_void_p), len(chunk), _stream())
             if status == -1:
                 # a problem outside the grouped kernel's operand combinations (odd widths / alignments): the entry point checks
@@ -373,13 +383,11 @@ def gemm_tn_group(prec, problems, slab, tag="tiny_dW.group"):
 
 def gemm_tn(prec, p, q, dw, db, N, K, *, q_prologue=None, p_prologue=None, nsplit=0, slab=None, tag=None):
     """dw[N,K] += pro_p(p)[M,N]^T @ pro(q)[M,K] ; db[N] += colsum(pro_p(p)).  dw/db fp32, pre-zeroed.
-    p_prologue = (y, mean, rstd, coef): the BatchNorm-backward correction of mmvae_bn_bwd_apply applied on the load of p."""
+    q_prologue: as gemm_nt's prologue.  p_prologue = BnBwdApply / (y, mean, rstd, coef): the BatchNorm-backward correction of mmvae_bn_bwd_apply applied on the load of p."""
     g = _tn_args(prec, p, q, dw, db, N, K, q_prologue, p_prologue, nsplit, slab)
-    t0 = PROBE.begin() if (PROBE is not None and PROBE.wants(tag)) else None
-    L.check(L.load().mmvae_gemm_tn(C.byref(g), _stream()), "mmvae_gemm_tn")
-    if t0 is not None:
-        PROBE.end(tag, t0, dict(kind="tn", M=p.shape[0], N=N, K=K, p_bytes=p.element_size() * (2 if p_prologue is not None else 1),
-                                q_bytes=q.element_size(), pro_mask=q_prologue is not None and q_prologue[2] is not None))
+    with probe_span(tag, lambda: dict(kind="tn", M=p.shape[0], N=N, K=K, p_bytes=p.element_size() * (2 if p_prologue is not None else 1),
+                                      q_bytes=q.element_size(), pro_mask=g.pro_mask is not None)):
+        L.check(L.load().mmvae_gemm_tn(C.byref(g), _stream()), "mmvae_gemm_tn")
 
 
 # --------------------------------------------------------------------------------------------
@@ -396,10 +404,14 @@ def bn_finalize_args(M, N, stats, gamma, beta, running_mean, running_var, nbt, m
                             mean.data_ptr(), rstd.data_ptr(), scale.data_ptr(), shift.data_ptr())
 
 
+def bn_finalize_launch(args):
+    """mmvae_bn_finalize on a prebuilt BnFinalizeArgs (bn_finalize_args())."""
+    L.check(L.load().mmvae_bn_finalize(C.byref(args), _stream()), "mmvae_bn_finalize")
+
+
 def bn_finalize(M, N, stats, gamma, beta, running_mean, running_var, nbt, mean, rstd, scale, shift,
-                eps=BN_EPS, momentum=BN_MOMENTUM, args=None):
-    a = args if args is not None else bn_finalize_args(M, N, stats, gamma, beta, running_mean, running_var, nbt, mean, rstd, scale, shift, eps, momentum)
-    L.check(L.load().mmvae_bn_finalize(C.byref(a), _stream()), "mmvae_bn_finalize")
+                eps=BN_EPS, momentum=BN_MOMENTUM):
+    bn_finalize_launch(bn_finalize_args(M, N, stats, gamma, beta, running_mean, running_var, nbt, mean, rstd, scale, shift, eps, momentum))
 
 
 def bn_eval_coeffs(gamma, beta, running_mean, running_var, scale, shift, eps=BN_EPS, mean=None, rstd=None):
@@ -416,14 +428,14 @@ def bn_bwd_finalize(M, N, stats, gamma, rstd, dgamma, dbeta, coef, eval_mode=Fal
 
 def bn_bwd_finalize_apply(d, y, M, N, mean, rstd, stats, gamma, dgamma, dbeta, eval_mode=False):
     """mmvae_bn_bwd_finalize + mmvae_bn_bwd_apply in one launch (the hidden widths of the model; raises for others)."""
-    with probe_span(f"bn_bwd_apply.N{N}", 3 * d.shape[0] * N * d.element_size()):
+    with stream_span(f"bn_bwd_apply.N{N}", 3 * d.shape[0] * N * d.element_size()):
         L.check(L.load().mmvae_bn_bwd_finalize_apply(_dt(d), M, N, d.data_ptr(), _ld(d), y.data_ptr(), _ld(y), mean.data_ptr(), rstd.data_ptr(),
                                                      stats[0].data_ptr(), stats[1].data_ptr(), gamma.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
                                                      int(eval_mode), _stream()), "mmvae_bn_bwd_finalize_apply")
 
 
 def bn_bwd_apply(d, y, N, mean, rstd, coef):
-    with probe_span(f"bn_bwd_apply.N{N}", 3 * d.shape[0] * N * d.element_size()):
+    with stream_span(f"bn_bwd_apply.N{N}", 3 * d.shape[0] * N * d.element_size()):
         L.check(L.load().mmvae_bn_bwd_apply(_dt(d), d.shape[0], N, d.data_ptr(), _ld(d), y.data_ptr(), _ld(y),
                                             mean.data_ptr(), rstd.data_ptr(), coef.data_ptr(), _stream()), "mmvae_bn_bwd_apply")
 
@@ -452,7 +464,7 @@ def fuse_reparam_fwd(B, Ld, heads_a, heads_b, table, site, eps, mu, logvar, z):
     a = L.FuseFwdArgs(B, Ld, n_mod, _p(heads_a), _p(heads_b), _ld(hd) if hd is not None else 0,
                       _p(table), _p(site), table.shape[0] if table is not None else 0,
                       eps.data_ptr(), mu.data_ptr(), logvar.data_ptr(), z.data_ptr(), _dt(z), _ld(z))
-    with probe_span("fuse_reparam_fwd", B * (8 * Ld * (n_mod - (table is not None)) + 8 * (table is not None) + 12 * Ld + z.element_size() * _ld(z))):
+    with stream_span("fuse_reparam_fwd", B * (8 * Ld * (n_mod - (table is not None)) + 8 * (table is not None) + 12 * Ld + z.element_size() * _ld(z))):
         L.check(L.load().mmvae_fuse_reparam_fwd(C.byref(a), _stream()), "mmvae_fuse_reparam_fwd")
 
 
@@ -465,7 +477,7 @@ def fuse_reparam_bwd(B, Ld, n_mod, g_mu, g_lv, dzs, eps, logvar, d_heads, d_tabl
                       d_heads.data_ptr(), _ld(d_heads), _p(d_table), _p(site), d_table.shape[-2] if d_table is not None else 0,
                       _p(d_heads_lp), _ld(d_heads_lp) if d_heads_lp is not None else 0, copies)
     n_dz = sum(1 for d in dzs if d is not None)
-    with probe_span("fuse_reparam_bwd", B * Ld * 4 * (n_dz + (g_mu is not None) + (g_lv is not None) + 2 + 2)):
+    with stream_span("fuse_reparam_bwd", B * Ld * 4 * (n_dz + (g_mu is not None) + (g_lv is not None) + 2 + 2)):
         L.check(L.load().mmvae_fuse_reparam_bwd(C.byref(a), _stream()), "mmvae_fuse_reparam_bwd")
 
 
@@ -509,7 +521,7 @@ def vae_loss(B, *, recon_a=None, a=None, recon_b=None, b=None, logits=None, site
         if mu is not None:
             n += B * mu.shape[1] * 4 * (2 + (g_mu is not None) + (g_lv is not None))
         return n
-    with probe_span("vae_loss", nbytes):
+    with stream_span("vae_loss", nbytes):
         L.check(L.load().mmvae_vae_loss(C.byref(x), _stream()), "mmvae_vae_loss")
 
 
@@ -544,7 +556,7 @@ def noise(mask, eps, keep_prob, seed, offset, offset_dev=None, advance=False):
     n_eps = 0 if eps is None else eps.numel()
     if advance:
         assert offset_dev is not None and offset_dev.numel() == L.CTR_COPIES and offset_dev.dtype == torch.int64
-    with probe_span("noise", n_mask + 4 * n_eps):
+    with stream_span("noise", n_mask + 4 * n_eps):
         L.check(L.load().mmvae_noise(_p(mask), n_mask, keep_prob, _p(eps), n_eps, seed, offset, _p(offset_dev), int(advance), _stream()), "mmvae_noise")
     return (n_mask + 15) // 16 * 4 + (n_eps + 3) // 4
 
@@ -593,7 +605,7 @@ def gather_rows(pairs, idx, src_rows):
         nbytes += 2 * B * row
     if idx.dtype != torch.int64 or not idx.is_cuda or not idx.is_contiguous():
         raise ValueError("gather_rows: idx must be a contiguous int64 device tensor")
-    with probe_span("gather_rows", nbytes):
+    with stream_span("gather_rows", nbytes):
         L.check(L.load().mmvae_gather_rows(C.cast(items, C.c_void_p), len(pairs), idx.data_ptr(), B, src_rows, _stream()), "mmvae_gather_rows")
 
 
@@ -604,7 +616,7 @@ def adamw_step(items, lr, b1, b2, eps, wd, bc1, bc2, maximize=False, step_dev=No
     tick = step_dev is not None and len(items) <= 64
     if step_dev is not None:
         assert step_dev.numel() == L.CTR_COPIES and step_dev.dtype == torch.int64
-    with probe_span("adamw", lambda: 28 * sum(it.n for it in items)):
+    with stream_span("adamw", lambda: 28 * sum(it.n for it in items)):
         L.check(L.load().mmvae_adamw_step(C.cast(items, C.c_void_p), len(items), lr, b1, b2, eps, wd, bc1, bc2, int(maximize),
                                           _p(step_dev), int(tick), _p(lr_dev), _stream()), "mmvae_adamw_step")
     if step_dev is not None and not tick:
