@@ -46,7 +46,8 @@ int mmvae_abi_version(void);    /* bumped on any struct change; the ctypes bindi
  * at the scaled omics widths) is processed in row blocks of at most half that threshold inside the entry point, and key 3 lowers it so
  * that tests reach that path at moderate sizes; key 4 = wide-tile kernel for the large weight gradients (gemm_tn_wide.hip) on/off;
  * key 6 / key 7 = row-coalesced LDS form of the BatchNorm-backward / ReLU-mask dX epilogue on/off; key 8 = wave-specialised NT kernel
- * (gemm_ntp.h: producer / consumer waves) on/off, key 9 = its minimum M (default 16384).  Other keys: MMVAE_ERR_ARG. */
+ * (gemm_ntp.h: producer / consumer waves) on/off, key 9 = its minimum M (default 16384); key 10 = the fused latent launch
+ * (mmvae_latent_fwd) on/off: off, it returns MMVAE_ERR_ARG and the caller issues the launches it replaces.  Other keys: MMVAE_ERR_ARG. */
 int mmvae_set_tuning(int32_t key, int32_t value);
 
 /* ---------------------------------------------------------------------------------------------
@@ -255,6 +256,55 @@ typedef struct {
 } mmvae_fuse_bwd_args;
 #define MMVAE_TABLE_COPIES 8
 int mmvae_fuse_reparam_bwd(const mmvae_fuse_bwd_args* args, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The latent path of the forward in ONE launch (latent.hip): from the encoders' last PRE-BatchNorm outputs to the decoders' first
+ * hidden activation, per 16-row slab without leaving the CU --
+ *   per encoder present:  heads = bf16(relu(y * scale + shift) * keep * inv_keep) x Wheads^T + bias   (the arithmetic of
+ *                         mmvae_gemm_nt with MMVAE_PRO_BN_RELU_DROP, K ascending; fp32, NOT stored)
+ *   mean fusion + reparameterisation exactly as mmvae_fuse_reparam_fwd (sum in the order a, b, table row of site[b]; a label outside
+ *                         [0, S) poisons its own row with NaN and touches nothing outside the table): mu, logvar (fp32) and z (bf16,
+ *                         pad columns zeroed) are written
+ *   stems:                h0 = bf16(relu(z x Wstem^T + bias_stem))   (mmvae_gemm_nt with MMVAE_ACT_RELU on the merged first layers)
+ * i.e. what vae.py:65-73 and the first Linear + ReLU of every decoder (decoders.py:13-14,27-28,44-45) compute, bit for bit what the
+ * four launches it replaces (two heads GEMMs, mmvae_fuse_reparam_fwd, the stem GEMM) write.
+ *   enc_x.y == NULL: that encoder is absent.  enc_x.finalize: `const mmvae_bn_finalize_args*` (host memory, read during the call) as
+ *   mmvae_gemm_nt's pro_finalize: every workgroup forms scale / shift from the f64 column sums, workgroup 0 writes mean / rstd /
+ *   scale / shift, the running statistics and num_batches_tracked; NULL: scale / shift are read (eval mode, or finalised before).
+ *   mask: uint8 keep mask [B][ld_mask] or NULL.  w: prepared heads weight ([>= 48][ldw] bf16, rows >= 2L zero), bias fp32 [2L].
+ *   n_mod must equal the number of modalities present (>= 1), as mmvae_fuse_reparam_fwd checks.
+ * Limits (anything else: MMVAE_ERR_ARG / MMVAE_ERR_DTYPE before anything is enqueued; the caller then issues the four launches):
+ *   prec == MMVAE_PREC_BF16 (MMVAE_ERR_DTYPE otherwise); B >= 1, 1 <= L <= 24 (2L <= 48 head columns: three MFMA tiles; the scaled
+ *   config's latent 128 does not fit) and B * L < 2^31; eps, mu, logvar, z, w_stem and h0 given;
+ *   per encoder: K % 32 == 0 and 32 <= K <= 256; ldy % 8 == 0, ldy >= K and y 16-byte aligned; ld_mask % 8 == 0, ld_mask >= K and
+ *   mask 8-byte aligned; w given, 16-byte aligned, ldw % 64 == 0 and ldw >= K; scale and shift given unless finalize is; finalize->N
+ *   == K, finalize->M == B >= 2 and its sums, gamma, beta, mean, rstd, scale, shift given;
+ *   ldz % 8 == 0, L <= ldz <= 32, z 16-byte aligned; N_stem % 64 == 0 and 64 <= N_stem <= 448; w_stem 16-byte aligned,
+ *   ldw_stem % 64 == 0 and ldw_stem >= 32; h0 rows are whole 128-byte lines (ldh0 % 64 == 0, ldh0 >= N_stem, 128-byte aligned base);
+ *   site given and 1 <= S, S * 2L <= 1024 when the table is; every row operand (y, mask, h0) below 4 GiB; tuning key 10 on
+ *   (mmvae_set_tuning).
+ * Not checked, the caller's contract: eps, mu and logvar are CONTIGUOUS [B][L] fp32; the head weights have at least 48 readable rows
+ *   (rows 2L..47 zero) and the stem weights 32 readable columns (columns L..31 zero) -- what mmvae_prep_weights writes into a
+ *   [ceil128(N)][ceil64(K)] operand; the table is [S][2L] fp32, site int64 [B].
+ * ------------------------------------------------------------------------------------------- */
+typedef struct {
+    const void* y; int64_t ldy; int32_t K;          /* last hidden layer's pre-BatchNorm output, bf16 [B][ldy] */
+    const float* scale; const float* shift;         /* [K]; ignored when finalize is given */
+    const uint8_t* mask; int64_t ld_mask; float inv_keep;
+    const void* finalize;
+    const void* w; int64_t ldw; const float* bias;
+} mmvae_latent_enc;
+typedef struct {
+    int32_t prec, B, L, n_mod;
+    mmvae_latent_enc enc_a, enc_b;
+    const float* table; const int64_t* site; int32_t S;
+    const float* eps;
+    float* mu; float* logvar;
+    void* z; int64_t ldz;
+    const void* w_stem; int64_t ldw_stem; const float* bias_stem; int32_t N_stem;
+    void* h0; int64_t ldh0;
+} mmvae_latent_fwd_args;
+int mmvae_latent_fwd(const mmvae_latent_fwd_args* args, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * vae_loss (src/utils/losses.py:8-46) and the directional losses

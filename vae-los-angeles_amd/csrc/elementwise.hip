@@ -6,6 +6,7 @@
 #include <vector>
 #include "common.h"
 #include "mmvae_hip.h"
+#include "fuse_math.h"
 
 namespace mm {
 
@@ -262,9 +263,9 @@ __global__ __launch_bounds__(256) void fuse_fwd_kernel(mmvae_fuse_fwd_args a) {
             const float bad = ok ? 0.f : __builtin_nanf("");
             mu += a.table[sc * 2 * a.L + l] + bad; lv += a.table[sc * 2 * a.L + a.L + l] + bad;
         }
-        if (a.n_mod > 1) { mu *= inv_n; lv *= inv_n; }
+        const float zf = fuse_reparam_elem(mu, lv, a.n_mod, inv_n, a.eps[(long)b * a.L + l]);
         a.mu[(long)b * a.L + l] = mu; a.logvar[(long)b * a.L + l] = lv;
-        *zp = from_f32<ZT>(mu + a.eps[(long)b * a.L + l] * expf(0.5f * lv));
+        *zp = from_f32<ZT>(zf);
     }
 }
 

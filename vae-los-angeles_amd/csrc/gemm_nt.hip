@@ -348,13 +348,7 @@ static int dispatch_epi(const mmvae_gemm_nt_args* a, const Src& src, hipStream_t
 
 // the folded mmvae_bn_finalize of the operand's producer (mmvae_gemm_nt_args::pro_finalize), or "off"
 BnFin bn_fin_of(const mmvae_gemm_nt_args* a) {
-    BnFin f;
-    if (!a->pro_finalize) return f;
-    const mmvae_bn_finalize_args* b = (const mmvae_bn_finalize_args*)a->pro_finalize;
-    f.sum = b->sum; f.sumsq = b->sumsq; f.gamma = b->gamma; f.beta = b->beta; f.eps = b->eps; f.momentum = b->momentum;
-    f.running_mean = b->running_mean; f.running_var = b->running_var; f.nbt = (long long*)b->num_batches_tracked;
-    f.mean = b->mean; f.rstd = b->rstd; f.scale = b->scale; f.shift = b->shift; f.M = b->M;
-    return f;
+    return bn_fin_from((const mmvae_bn_finalize_args*)a->pro_finalize);
 }
 static bool bn_fin_ok(const mmvae_gemm_nt_args* a) {
     if (!a->pro_finalize) return true;
@@ -401,6 +395,7 @@ extern "C" int mmvae_set_tuning(int32_t key, int32_t value) {
     case 7: t.relu_stream = value; return 0;
     case 8: t.ntp_on = value; return 0;
     case 9: t.ntp_min_m = value; return 0;
+    case 10: t.latent_on = value; return 0;
     }
     return MMVAE_ERR_ARG;
 }

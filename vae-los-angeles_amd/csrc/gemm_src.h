@@ -131,6 +131,16 @@ struct BnFin {
     }
 };
 
+// the folded finalisation described by an mmvae_bn_finalize_args in host memory, or "off" (nullptr)
+inline BnFin bn_fin_from(const mmvae_bn_finalize_args* b) {
+    BnFin f;
+    if (!b) return f;
+    f.sum = b->sum; f.sumsq = b->sumsq; f.gamma = b->gamma; f.beta = b->beta; f.eps = b->eps; f.momentum = b->momentum;
+    f.running_mean = b->running_mean; f.running_var = b->running_var; f.nbt = (long long*)b->num_batches_tracked;
+    f.mean = b->mean; f.rstd = b->rstd; f.scale = b->scale; f.shift = b->shift; f.M = b->M;
+    return f;
+}
+
 template <typename CT>
 struct SrcBnReluDrop {
     static constexpr int EPC = Mma<CT>::EPC;

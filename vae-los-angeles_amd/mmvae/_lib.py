@@ -82,6 +82,22 @@ class FuseFwdArgs(C.Structure):
                 ("z", vp), ("z_dtype", i32), ("ldz", i64)]
 
 
+class LatentEnc(C.Structure):
+    _fields_ = [("y", vp), ("ldy", i64), ("K", i32), ("scale", vp), ("shift", vp),
+                ("mask", vp), ("ld_mask", i64), ("inv_keep", f32), ("finalize", vp),
+                ("w", vp), ("ldw", i64), ("bias", vp)]
+
+
+class LatentFwdArgs(C.Structure):
+    _fields_ = [("prec", i32), ("B", i32), ("L", i32), ("n_mod", i32),
+                ("enc_a", LatentEnc), ("enc_b", LatentEnc),
+                ("table", vp), ("site", vp), ("S", i32),
+                ("eps", vp), ("mu", vp), ("logvar", vp),
+                ("z", vp), ("ldz", i64),
+                ("w_stem", vp), ("ldw_stem", i64), ("bias_stem", vp), ("N_stem", i32),
+                ("h0", vp), ("ldh0", i64)]
+
+
 class FuseBwdArgs(C.Structure):
     _fields_ = [("B", i32), ("L", i32), ("n_mod", i32),
                 ("g_mu", vp), ("g_lv", vp), ("dz", vp), ("dz2", vp), ("dz3", vp), ("lddz", i64),
@@ -128,6 +144,7 @@ _SIGNATURES = {
     "mmvae_embed_table_bwd": [i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp],
     "mmvae_fuse_reparam_fwd": [C.POINTER(FuseFwdArgs), vp],
     "mmvae_fuse_reparam_bwd": [C.POINTER(FuseBwdArgs), vp],
+    "mmvae_latent_fwd": [C.POINTER(LatentFwdArgs), vp],
     "mmvae_vae_loss": [C.POINTER(LossArgs), vp],
     "mmvae_loss_finalize": [vp, f32, f32, vp, vp, vp],
     "mmvae_gather_rows": [vp, i32, vp, i32, i64, vp],

@@ -277,39 +277,37 @@ class EncoderMLP:
     def widths(self):
         return [l.out_features for l in self.linears]
 
-    def forward(self, prec, x, train, masks, stats_bufs=None, want_bwd=False):
+    def _consume(self, prec, h, pro, fin, N, K, out, bias, w, tag, stats=None, pro_out=None):
+        """GEMM on (h, pro) that also finalises h's BatchNorm statistics (`fin`, owed by the layer that produced h) when the library
+        can fold that in; else the launch of its own.  Returns pro_out if the launch wrote it, else None."""
+        if fin is not None:
+            try:
+                ops.gemm_nt(prec, h, w, N, K, out, bias=bias, prologue=pro, stats=stats, tag=tag, pro_out=pro_out, pro_finalize=fin)
+                return pro_out
+            except L_.MMVAEArgError:
+                pass                                   # refused before anything was enqueued (argument check)
+            ops.bn_finalize_launch(fin)
+        try:
+            ops.gemm_nt(prec, h, w, N, K, out, bias=bias, prologue=pro, stats=stats, tag=tag, pro_out=pro_out)
+            return pro_out
+        except L_.MMVAEArgError:
+            if pro_out is None:
+                raise
+            # the library did not take the problem on the kernel that writes pro_out: the ordinary call, and the backward redoes
+            # the prologue on its operand load
+            ops.gemm_nt(prec, h, w, N, K, out, bias=bias, prologue=pro, stats=stats, tag=tag)
+            return None
+
+    def forward(self, prec, x, train, masks, stats_bufs=None, want_bwd=False, heads=True):
         """masks: one uint8 (B, width) keep-mask per BN layer (training) or None (eval).
-        stats_bufs: optional pre-zeroed float64 (2, N) accumulators, one per BN layer."""
+        stats_bufs: optional pre-zeroed float64 (2, N) accumulators, one per BN layer.
+        heads=False: stop before the heads -- returns (ops.LatentEncoder, layers): the last layer's output with its prologue and the
+        finalisation still owed, for VAEGraph's fused latent launch (or run_heads() when the library does not take it)."""
         B, dev = x.shape[0], x.device
         adt = act_dtype(prec)
         layers = []
         h, pro = x, None
         fin = None            # the BatchNorm finalisation of the layer that produced h, still owed: it rides in the GEMM that consumes h
-
-        def consume(N, K, out, bias, w, tag, stats=None, pro_out=None):
-            """GEMM on (h, pro) that also finalises h's BatchNorm statistics when the library can fold that in; else the launch of its own."""
-            nonlocal fin
-            if fin is not None:
-                try:
-                    ops.gemm_nt(prec, h, w, N, K, out, bias=bias, prologue=pro, stats=stats, tag=tag, pro_out=pro_out, pro_finalize=fin)
-                    fin = None
-                    return pro_out
-                except L_.MMVAEArgError:
-                    pass                                   # refused before anything was enqueued (argument check)
-            if fin is not None:
-                ops.bn_finalize_launch(fin)
-                fin = None
-            try:
-                ops.gemm_nt(prec, h, w, N, K, out, bias=bias, prologue=pro, stats=stats, tag=tag, pro_out=pro_out)
-                return pro_out
-            except L_.MMVAEArgError:
-                if pro_out is None:
-                    raise
-                # the library did not take the problem on the kernel that writes pro_out: the ordinary call, and the backward redoes
-                # the prologue on its operand load
-                ops.gemm_nt(prec, h, w, N, K, out, bias=bias, prologue=pro, stats=stats, tag=tag)
-                return None
-
         for lin, bn, pl in zip(self.linears, self.bns, self.pl):
             N, K = pl.N, pl.K
             y = torch.empty(B, ceil_to(N, 8), dtype=adt, device=dev)
@@ -323,7 +321,7 @@ class EncoderMLP:
                 h_act = torch.empty(B, K, dtype=torch.bfloat16, device=dev)
             if train:
                 stats = stats_bufs[len(layers)] if stats_bufs is not None else torch.zeros(2, N, dtype=torch.float64, device=dev)
-                h_act = consume(N, K, y, pl.bias, pl.w, f"{self.name}.L{len(layers)}.fwd", stats=stats, pro_out=h_act)
+                h_act = self._consume(prec, h, pro, fin, N, K, y, pl.bias, pl.w, f"{self.name}.L{len(layers)}.fwd", stats=stats, pro_out=h_act)
                 # the finalisation of THIS layer's statistics is owed to whoever reads y next (the next layer or the heads)
                 fin = ops.bn_finalize_args(B, N, stats, bn.weight, bn.bias, bn.running_mean, bn.running_var,
                                            bn.num_batches_tracked, st.mean, st.rstd, st.scale, st.shift, bn.eps,
@@ -335,9 +333,15 @@ class EncoderMLP:
                 new_pro = Prologue(st.scale, st.shift, None, 1.0)
             layers.append(LayerSave(h, pro, y, st, new_pro) if h_act is None else LayerSave(h_act, None, y, st, new_pro))      # backward's Q operand: plain when kept
             h, pro = y, new_pro
-        heads = torch.empty(B, 2 * self.latent, dtype=torch.float32, device=dev)
-        consume(2 * self.latent, self.pl_heads.K, heads, self.pl_heads.bias, self.pl_heads.w, f"{self.name}.heads.fwd")
-        return heads, layers
+        owed = ops.LatentEncoder(h, pro, fin, self.pl_heads)
+        return (self.run_heads(prec, owed) if heads else owed), layers
+
+    def run_heads(self, prec, owed):
+        """The fc_mu | fc_logvar heads as a GEMM of their own -> fp32 (B, 2 * latent)."""
+        heads = torch.empty(owed.y.shape[0], 2 * self.latent, dtype=torch.float32, device=owed.y.device)
+        self._consume(prec, owed.y, owed.prologue, owed.fin, 2 * self.latent, self.pl_heads.K, heads, self.pl_heads.bias, self.pl_heads.w,
+                      f"{self.name}.heads.fwd")
+        return heads
 
     def backward(self, prec, layers, d_heads, grads, tn=ops.gemm_tn, stats_bufs=None, train=True, d_heads_lp=None):
         """d_heads: [B][2L] fp32.  grads: dict param -> fp32 view (pre-zeroed, accumulated).
@@ -627,14 +631,21 @@ class VAEGraph:
         zeros = self.zero_pack(dev, xa is not None, xb is not None, site is not None, fwd=True, bwd=want_bwd) if train else None
         if want_bwd:
             state.zeros = zeros
+        # With merged decoder first layers in bf16 mode the encoders stop before their heads: heads, fusion, reparameterisation and the
+        # stems are ONE launch (mmvae_latent_fwd); where the library does not take it, the launches it replaces run below.  The refusal
+        # is only known once both encoders have run, so that fallback issues [A layers, B layers, A heads, B heads, fusion, stems]
+        # where graphs without a stem (and every graph before the fused launch) issue [A layers, A heads, B layers, B heads, ...]: the
+        # same launches on the same operands with the same results, EncoderA's last pre-BatchNorm output is simply read later.
+        stem = self.dec_stem
+        fuse_latent = stem is not None and prec == PREC_BF16
         if xa is not None:
             xa = _check_input(xa, "a", self.enc_a.in_dim, prec)
             heads_a, state.enc_a = self.enc_a.forward(prec, xa, train, masks[:n_a] if train else None,
-                                                      zeros.fwd_stats[:n_a] if train else None, want_bwd=want_bwd)
+                                                      zeros.fwd_stats[:n_a] if train else None, want_bwd=want_bwd, heads=not fuse_latent)
         if xb is not None:
             xb = _check_input(xb.reshape(xb.shape[0], -1), "b", self.enc_b.in_dim, prec)     # encoders.py:44 view
             heads_b, state.enc_b = self.enc_b.forward(prec, xb, train, masks[n_a:] if train else None,
-                                                      zeros.fwd_stats[n_a:] if train else None, want_bwd=want_bwd)
+                                                      zeros.fwd_stats[n_a:] if train else None, want_bwd=want_bwd, heads=not fuse_latent)
         if site is not None:
             if site.dtype != torch.int64:
                 site = site.long()
@@ -644,7 +655,16 @@ class VAEGraph:
         mu = torch.empty(B, Ld, dtype=torch.float32, device=dev)
         logvar = torch.empty(B, Ld, dtype=torch.float32, device=dev)
         z = torch.empty(B, ceil_to(Ld, 8), dtype=act_dtype(prec), device=dev)
-        ops.fuse_reparam_fwd(B, Ld, heads_a, heads_b, table, site, eps, mu, logvar, z)
+        H0 = torch.empty(B, stem.N, dtype=act_dtype(prec), device=dev) if stem is not None else None
+        if fuse_latent:
+            try:
+                ops.latent_fwd(prec, B, Ld, heads_a, heads_b, table, site, eps, mu, logvar, z, stem, H0)
+            except L_.MMVAEArgError:                   # refused before anything was enqueued
+                fuse_latent = False
+                heads_a = self.enc_a.run_heads(prec, heads_a) if heads_a is not None else None
+                heads_b = self.enc_b.run_heads(prec, heads_b) if heads_b is not None else None
+        if not fuse_latent:
+            ops.fuse_reparam_fwd(B, Ld, heads_a, heads_b, table, site, eps, mu, logvar, z)
         # .detach(): aliases of the RETURNED tensors, so the saved state holds no reference to objects that own the
         # autograd node (tensor -> grad_fn -> ctx -> state -> tensor would be a cycle only the cyclic GC frees,
         # i.e. every step's activations would pile up in HBM until it runs)
@@ -652,11 +672,10 @@ class VAEGraph:
         state.n_mod = (heads_a is not None) + (heads_b is not None) + (table is not None)
         outs, state.dec = [None] * len(self.decoders), [None] * len(self.decoders)
         order = sorted(range(len(self.decoders)), key=lambda i: -sum(l.weight.numel() for l in self.decoders[i].linears))
-        stem = self.dec_stem
         firsts = [None] * len(self.decoders)
         if stem is not None:
-            H0 = torch.empty(B, stem.N, dtype=act_dtype(prec), device=dev)
-            ops.gemm_nt(prec, z, stem.w, stem.N, stem.K, H0, bias=stem.bias, act=ACT_RELU, tag="Decoders.L0.fwd")
+            if not fuse_latent:
+                ops.gemm_nt(prec, z, stem.w, stem.N, stem.K, H0, bias=stem.bias, act=ACT_RELU, tag="Decoders.L0.fwd")
             off = 0
             for i, d in enumerate(self.decoders):
                 firsts[i] = H0[:, off:off + d.linears[0].out_features]

@@ -468,6 +468,53 @@ def fuse_reparam_fwd(B, Ld, heads_a, heads_b, table, site, eps, mu, logvar, z):
         L.check(L.load().mmvae_fuse_reparam_fwd(C.byref(a), _stream()), "mmvae_fuse_reparam_fwd")
 
 
+# LatentEncoder: what an encoder hands to the fused latent launch instead of running its heads -- its last hidden layer's pre-BatchNorm
+# output `y`, that layer's Prologue, the BatchNorm finalisation still owed (BnFinalizeArgs or None) and the heads' PreparedLinear.
+LatentEncoder = namedtuple("LatentEncoder", "y prologue fin heads")
+
+
+def _latent_enc(e, enc):
+    sc, sh, mask, inv_keep = enc.prologue
+    e.y, e.ldy, e.K = _mat(enc.y, "y").data_ptr(), _ld(enc.y), enc.heads.K
+    e.scale, e.shift, e.mask, e.ld_mask, e.inv_keep = sc.data_ptr(), sh.data_ptr(), _p(mask), (_ld(mask) if mask is not None else 0), inv_keep
+    if enc.fin is not None:
+        e.finalize = C.addressof(enc.fin)
+    e.w, e.ldw, e.bias = enc.heads.w.data_ptr(), enc.heads.w.stride(0), _p(enc.heads.bias)
+
+
+def latent_fwd_args(prec, B, Ld, enc_a, enc_b, table, site, eps, mu, logvar, z, stem, h0):
+    """-> (LatentFwdArgs of mmvae_latent_fwd, its algorithmic HBM bytes).  The struct holds addresses only: the tensors and the
+    encoders' BnFinalizeArgs must outlive the call."""
+    a = L.LatentFwdArgs()
+    a.prec, a.B, a.L = prec, B, Ld
+    a.n_mod = (enc_a is not None) + (enc_b is not None) + (table is not None)
+    nbytes = 12 * Ld + z.element_size() * _ld(z) + h0.element_size() * stem.N + 8 * (table is not None)
+    for e, enc in ((a.enc_a, enc_a), (a.enc_b, enc_b)):
+        if enc is not None:
+            _latent_enc(e, enc)
+            nbytes += enc.heads.K * (enc.y.element_size() + (enc.prologue[2] is not None))
+    if table is not None:
+        a.table, a.site, a.S = table.data_ptr(), _p(site), table.shape[0]
+    a.eps, a.mu, a.logvar = eps.data_ptr(), mu.data_ptr(), logvar.data_ptr()
+    a.z, a.ldz = z.data_ptr(), _ld(z)
+    a.w_stem, a.ldw_stem, a.bias_stem, a.N_stem = stem.w.data_ptr(), stem.w.stride(0), _p(stem.bias), stem.N
+    a.h0, a.ldh0 = h0.data_ptr(), _ld(h0)
+    return a, B * nbytes
+
+
+def latent_fwd(prec, B, Ld, enc_a, enc_b, table, site, eps, mu, logvar, z, stem, h0):
+    """mmvae_latent_fwd: heads of the encoders present (LatentEncoder or None), mean fusion + reparameterisation and the decoders'
+    merged first layers (`stem`, a PreparedLinear; h0 = relu(z @ stem^T + b)) in ONE launch.  eps, mu and logvar are contiguous
+    (B, Ld).  Raises MMVAEArgError, with nothing enqueued, for what the kernel does not take: the caller then issues the launches it
+    replaces."""
+    for t in (eps, mu, logvar):
+        if tuple(t.shape) != (B, Ld) or not t.is_contiguous():
+            raise ValueError(f"latent_fwd: eps / mu / logvar must be contiguous ({B}, {Ld}), got {tuple(t.shape)} / {t.stride()}")
+    a, nbytes = latent_fwd_args(prec, B, Ld, enc_a, enc_b, table, site, eps, mu, logvar, z, stem, h0)
+    with stream_span("latent.fwd", nbytes):
+        L.check(L.load().mmvae_latent_fwd(C.byref(a), _stream()), "mmvae_latent_fwd")
+
+
 def fuse_reparam_bwd(B, Ld, n_mod, g_mu, g_lv, dzs, eps, logvar, d_heads, d_table, site, d_heads_lp=None):
     """dzs: 1..3 fp32 (B, Ld) tensors with one leading dimension (dL/dz of each decoder); they are summed.
     d_table: zeroed [S][2L] or [copies][S][2L] (workgroups spread their scatter-adds over the copies)."""
