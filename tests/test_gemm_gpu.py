@@ -10,6 +10,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import gemm_bounds as G  # noqa: E402
 from mmvae import ops  # noqa: E402
 from mmvae.ops import PREC_BF16, PREC_F32  # noqa: E402
 
@@ -24,6 +25,15 @@ def _prep(W, b, prec):
     pl = ops.PreparedLinear([W], [b], prec, DEV)
     ops.WeightPrep([pl], DEV).run()
     return pl
+
+
+def _stats_inside(st, stored):
+    """Column (sum, sum of squares) of a tile kernel against the float64 sums of the values it stored, inside the derived statistics
+    bound of tests/gemm_bounds.py (fp32 partial sums over one 128-row tile, then f64 atomics).  tests/test_gemm_bounds_cpu.py shows
+    that on these inputs the bound is below the rtol = 1e-4, atol = 1e-2 it replaces, column by column."""
+    c = stored.numpy()
+    err, tol = np.abs(st.cpu().numpy() - G.stats_ref(c)), G.stats_tol(c, G.ROWS_TILE)
+    assert (err <= tol).all(), f"column statistics outside the derived bound: worst err / bound {np.max(err / np.maximum(tol, 1e-300)):.3f}"
 
 
 def _tol(K, scale, out_bf16=False):
@@ -62,8 +72,7 @@ def test_nt_store(prec, M, N, K, a_bf16):
             tol = _tol(K, float(r.abs().max()), out_dt == torch.bfloat16)
             assert float((got - r).abs().max()) <= tol, (act, out_dt)
             assert torch.all((out[:, N:].float() == 7.0) | (out[:, N:].float() == 0.0))   # pad columns: untouched or zeroed
-            np.testing.assert_allclose(st[0].cpu(), got.sum(0), rtol=1e-4, atol=1e-2)
-            np.testing.assert_allclose(st[1].cpu(), (got ** 2).sum(0), rtol=1e-4, atol=1e-2)
+            _stats_inside(st, got)
     # accumulate
     out = torch.ones(M, N, device=DEV)
     ops.gemm_nt(prec, Ad, pl.w, N, K, out, bias=pl.bias, accumulate=True)
@@ -214,7 +223,7 @@ def test_nt_wide_tiles(N, K):
                 r = ref.clamp_min(0)
                 got = out.float().cpu().double()
                 assert float((got - r).abs().max()) <= _tol(K, float(r.abs().max()), out_dt == torch.bfloat16)
-                np.testing.assert_allclose(st[0].cpu(), got.sum(0), rtol=1e-4, atol=1e-2)
+                _stats_inside(st, got)
         # backward epilogues on the wide kernel: ReLU mask and both BatchNorm forms (output width N, reduction K)
         adt = torch.bfloat16
         dY = _round(torch.randn(M, K, generator=g), prec)
