@@ -396,6 +396,37 @@ int mmvae_rows_to_bf16(const void* src, int32_t src_dtype, int64_t ld_src, void*
                        void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Imputation metrics of a reconstruction against its target in ONE streaming pass (metrics.hip): what compute_metrics
+ * (compare_directional_imputation.py:167-210) and calculate_metrics (vae_cross_modality_cv.py:71-108) take from an N x N
+ * cosine_similarity matrix and a Python loop of scipy.stats.pearsonr over host copies.  y = target, p = prediction, [M][N]:
+ *   row_pearson[i] = Pearson r of (y_i, p_i), clamped to [-1, 1]; NaN when every element of y_i, or every element of p_i, compares
+ *                    equal to that row's first element (scipy's constant-input rule, decided on the values)
+ *   row_cosine[i]  = sum y p / (|y_i| |p_i|), a zero norm replaced by 1 (sklearn's normalize: a zero row gives 0)
+ *   col_acc[0][j] += sum_i (y_ij - c_j)      col_acc[1][j] += sum_i (y_ij - c_j)^2      c = col_shift, NULL = 0
+ *   col_acc[2][j] += sum_i (p_ij - y_ij)^2   col_acc[3][j] += sum_i |p_ij - y_ij|
+ * col_acc is double[4][N] and ACCUMULATED (f64 atomics; zero it once per evaluation, as `sums` of mmvae_vae_loss): MAE / MSE / RMSE
+ * and the flat and per-feature R^2 follow from it on the host, additive over batches; col_shift (one fixed vector per evaluation,
+ * e.g. the first target row) keeps the column moments well conditioned and is undone there.  row_* are fp32 [M], written.
+ * Values are widened to f64 on load and every sum is f64; Pearson uses the moments of the row shifted by its own first element.
+ * Non-finite inputs give non-finite outputs.  Results are not bit-reproducible between runs (order of the atomics).
+ *   pred / target: MMVAE_F32 or MMVAE_BF16, row-major, leading dimension in elements, any row stride >= N (padded bf16 rows, see
+ *   mmvae_rows_to_bf16, included; loads are as wide as base and stride allow; pad columns are never read).  ld_pred == 0: ONE prediction row for every sample (the
+ *   mean-imputation baseline, compare_directional_imputation.py:213-232, without its np.tile).  1 <= M, N < 2^31; row offsets are
+ *   64-bit, there is no operand size limit.
+ * MMVAE_ERR_ARG (nothing enqueued): a null struct or null pred / target / col_acc / row_pearson / row_cosine, M < 1, N < 1, a leading
+ *   dimension below N (other than ld_pred == 0), a dtype that is neither, a pointer not aligned to its element size.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t M, N;
+    const void* pred; int32_t pred_dtype; int64_t ld_pred;
+    const void* target; int32_t target_dtype; int64_t ld_target;
+    const float* col_shift;
+    double* col_acc;
+    float* row_pearson; float* row_cosine;
+} mmvae_metrics_args;
+int mmvae_recon_metrics(const mmvae_metrics_args* args, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * AdamW (torch.optim.AdamW, constructed by the caller: optimize_hyperparameters.py:93-97,
  * train_dna2rna.py:185-189), all tensors in one launch per 64 tensors (every record is checked before the first launch).  `items_host` is an array in HOST memory
  * (device pointers inside); it is copied into the kernel arguments, so nothing is uploaded and the call is graph-capturable:

@@ -1,0 +1,158 @@
+#!/usr/bin/env python3
+"""Imputation quality of a trained model on the trainers' validation split: the last stage of the reference's pipeline
+(prepare -> train.py -> evaluate.py; its README and run_pipeline.sh name the script, the snapshot does not contain it).
+
+    python evaluate.py --kind rna2dna                         # checkpoint of the latest train_rna2dna.py run
+    python evaluate.py --kind multimodal --checkpoint checkpoints/best_multivae_<run id>.pt --out results.json
+
+One table row per (route, target modality) with the columns of compute_metrics (compare_directional_imputation.py:167-210), and
+beside every target modality the mean-imputation baseline (training-set column means, compare_directional_imputation.py:213-232).
+Routes: the directional models' one route; MultiModalVAE: a -> b, b -> a and the full (a, b, site) reconstruction.  The metrics
+are computed on the device (mmvae.metrics: one streaming launch per batch and route), nothing but 32 bytes per feature and the
+per-row vectors' aggregates reaches the host.  Evaluation runs in eval mode under no_grad; eps is still sampled (vae.py:73), so
+--seed selects the Philox stream.  Single process; the accumulators are additive, a multi-rank form is one all-reduce away."""
+import argparse
+import json
+import os
+import sys
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+if HERE not in sys.path:
+    sys.path.insert(0, HERE)
+
+import torch  # noqa: E402
+
+from mmvae.metrics import ImputationMetrics  # noqa: E402
+from src.config import Config  # noqa: E402
+from trainer import KINDS, load_pickled_dataset, make_model, split_indices, synthetic_dataset  # noqa: E402
+
+COLUMNS = ("MAE", "MSE", "RMSE", "R2", "MeanR2", "CosineSimilarity", "PearsonMean", "PearsonStd", "PearsonValid")
+
+
+def build_parser(kind):
+    ap = argparse.ArgumentParser(description=f"{KINDS[kind]['title']} imputation metrics on MI355X")
+    ap.add_argument("--data", default=None, help="processed_data.pkl produced by the reference's prepare scripts (default: synthetic)")
+    ap.add_argument("--samples", type=int, default=262144, help="synthetic dataset size")
+    ap.add_argument("--input-dim-a", type=int, default=int(os.getenv("INPUT_DIM_A", 782)))
+    ap.add_argument("--input-dim-b", type=int, default=int(os.getenv("INPUT_DIM_B", 572)))
+    ap.add_argument("--n-sites", type=int, default=24)
+    ap.add_argument("--latent-dim", type=int, default=int(os.getenv("LATENT_DIM", Config.LATENT_DIM)))
+    ap.add_argument("--batch-size", type=int, default=4096)
+    ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32"])
+    ap.add_argument("--input-dtype", default="fp32", choices=["fp32", "bf16"], help="storage of the device-resident RNA / DNA matrices")
+    ap.add_argument("--checkpoint", default=None, help="state_dict as the trainers save it (default: the run named by latest_<tag>_run_id.txt)")
+    ap.add_argument("--checkpoint-dir", default=Config.CHECKPOINT_DIR)
+    ap.add_argument("--seed", type=int, default=Config.RANDOM_SEED, help="Philox stream of eps")
+    ap.add_argument("--out", default=None, help="write the table rows as JSON here")
+    return ap
+
+
+def routes(kind):
+    """[(route name, forward kwargs over the batch (a, b, s), [(index into the forward's outputs, target 'a' | 'b')])]"""
+    if kind == "rna2dna":
+        return [("rna+site->dna", lambda a, b, s: dict(rna=a, site=s), [(0, "b")])]
+    if kind == "dna2rna":
+        return [("dna+site->rna", lambda a, b, s: dict(dna=b, site=s), [(0, "a")])]
+    return [("a->b", lambda a, b, s: dict(a=a), [(1, "b")]),
+            ("b->a", lambda a, b, s: dict(b=b), [(0, "a")]),
+            ("a+b+site->a,b", lambda a, b, s: dict(a=a, b=b, site=s), [(0, "a"), (1, "b")])]
+
+
+def _row(route, modality, model_name, result):
+    row = {"Route": route, "Modality": modality, "Model": model_name}
+    row.update({k: result[k] for k in COLUMNS})
+    return row
+
+
+def print_table(rows):
+    head = f"{'Route':<16}{'Modality':<9}{'Model':<16}" + "".join(f"{c:>17}" for c in COLUMNS)
+    print(head)
+    print("-" * len(head))
+    for r in rows:
+        print(f"{r['Route']:<16}{r['Modality']:<9}{r['Model']:<16}"
+              + "".join(f"{r[c]:>17d}" if c == "PearsonValid" else f"{r[c]:>17.6f}" for c in COLUMNS))
+
+
+def run(kind, argv=None):
+    args = build_parser(kind).parse_args(argv)
+    tag, title = KINDS[kind]["tag"], KINDS[kind]["title"]
+    if not torch.cuda.is_available():
+        raise SystemExit("evaluate.py needs an MI355X: the product path has no CPU fallback")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    if args.data:
+        tpm, beta_v, site = load_pickled_dataset(args.data)
+        args.input_dim_a, args.input_dim_b = tpm.shape[1], beta_v.shape[1]
+        args.n_sites = int(site.max()) + 1
+    else:
+        tpm, beta_v, site = synthetic_dataset(args.samples, args.input_dim_a, args.input_dim_b, args.n_sites, Config.RANDOM_SEED)
+    lo_, hi_ = int(site.min()), int(site.max())
+    if lo_ < 0 or hi_ >= args.n_sites:                       # the trainer's check: the site encoder's Embedding has no row for them
+        raise SystemExit(f"site labels must lie in [0, {args.n_sites}); found [{lo_}, {hi_}]")
+    val_idx, train_idx = split_indices(tpm.shape[0])
+    if val_idx.numel() == 0:
+        raise SystemExit(f"{tpm.shape[0]} samples leave no validation rows")
+    va = [t[val_idx].to(dev).contiguous() for t in (tpm, beta_v, site)]
+    # mean imputation: the column means of the TRAINING rows, one row for every validation sample
+    means = {"a": tpm[train_idx].double().mean(dim=0).float().to(dev), "b": beta_v[train_idx].double().mean(dim=0).float().to(dev)}
+    if args.input_dtype == "bf16":
+        from mmvae import to_bf16_rows
+        va[:2] = [to_bf16_rows(t) for t in va[:2]]
+
+    path = args.checkpoint
+    if path is None:
+        id_file = f"latest_{tag}_run_id.txt"
+        if not os.path.exists(id_file):
+            raise SystemExit(f"no --checkpoint given and {id_file} (written by the trainer) is not here")
+        with open(id_file) as f:
+            path = os.path.join(args.checkpoint_dir, f"best_{tag}_{f.read().strip()}.pt")
+    if not os.path.exists(path):
+        raise SystemExit(f"checkpoint {path} not found")
+    model = make_model(kind, args)
+    state = torch.load(path, map_location="cpu")
+    own = model.state_dict()
+    bad = [f"{k}: checkpoint {tuple(state[k].shape)}, model {tuple(v.shape)}" for k, v in own.items()
+           if k in state and tuple(state[k].shape) != tuple(v.shape)]
+    missing = [k for k in own if k not in state]
+    if bad or missing:
+        raise SystemExit(f"{path} is not a {title} of RNA {args.input_dim_a} / DNA {args.input_dim_b} / {args.n_sites} sites / latent "
+                         f"{args.latent_dim}: " + "; ".join(bad[:4] + [f"missing {k}" for k in missing[:4]]))
+    model.load_state_dict(state)
+    model.to(dev).set_precision(args.precision).eval()
+    torch.manual_seed(args.seed)
+
+    dims = {"a": args.input_dim_a, "b": args.input_dim_b}
+    names = {"a": "RNA", "b": "DNA"}
+    plan = routes(kind)
+    acc = {(name, tgt): ImputationMetrics(dims[tgt], dev) for name, _, outs in plan for _, tgt in outs}
+    targets = sorted({tgt for _, _, outs in plan for _, tgt in outs})
+    base = {tgt: ImputationMetrics(dims[tgt], dev) for tgt in targets}
+    B, n_val = args.batch_size, va[0].shape[0]
+    with torch.no_grad():
+        for i in range(0, n_val, B):
+            a, b, s = va[0][i:i + B], va[1][i:i + B], va[2][i:i + B]
+            truth = {"a": a, "b": b}
+            for name, kwargs, outs in plan:
+                res = model(**kwargs(a, b, s))
+                for j, tgt in outs:
+                    acc[(name, tgt)].update(truth[tgt], res[j])
+            for tgt in targets:
+                base[tgt].update(truth[tgt], means[tgt])
+    rows = []
+    for name, _, outs in plan:
+        for _, tgt in outs:
+            rows.append(_row(name, names[tgt], title, acc[(name, tgt)].compute()))
+    for tgt in targets:
+        rows.append(_row("train mean", names[tgt], "MeanImputation", base[tgt].compute()))
+    print(f"{title}: {path}  ({n_val} validation rows, batch {B}, {args.precision}, {args.input_dtype} inputs)")
+    print_table(rows)
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(rows, f, indent=1)
+    return rows
+
+
+if __name__ == "__main__":
+    pre = argparse.ArgumentParser(add_help=False)
+    pre.add_argument("--kind", default="multimodal", choices=sorted(KINDS))
+    known, rest = pre.parse_known_args()
+    run(known.kind, rest)

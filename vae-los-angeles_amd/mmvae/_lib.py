@@ -120,6 +120,13 @@ class LossArgs(C.Structure):
                 ("g_mu", vp), ("g_lv", vp), ("beta_gamma_dev", vp), ("a_dtype", i32), ("b_dtype", i32)]
 
 
+class MetricsArgs(C.Structure):
+    _fields_ = [("M", i32), ("N", i32),
+                ("pred", vp), ("pred_dtype", i32), ("ld_pred", i64),
+                ("target", vp), ("target_dtype", i32), ("ld_target", i64),
+                ("col_shift", vp), ("col_acc", vp), ("row_pearson", vp), ("row_cosine", vp)]
+
+
 class GatherItem(C.Structure):
     _fields_ = [("src", vp), ("dst", vp), ("src_row_stride", i64), ("dst_row_stride", i64), ("row_bytes", i32), ("pad_", i32)]
 
@@ -147,6 +154,7 @@ _SIGNATURES = {
     "mmvae_latent_fwd": [C.POINTER(LatentFwdArgs), vp],
     "mmvae_vae_loss": [C.POINTER(LossArgs), vp],
     "mmvae_loss_finalize": [vp, f32, f32, vp, vp, vp],
+    "mmvae_recon_metrics": [C.POINTER(MetricsArgs), vp],
     "mmvae_gather_rows": [vp, i32, vp, i32, i64, vp],
     "mmvae_rows_to_bf16": [vp, i32, i64, vp, i64, i32, i32, vp],
     "mmvae_sigmoid_bwd": [i32, i32, vp, i64, vp, i64, vp, i32, i64, vp],

@@ -656,6 +656,48 @@ def gather_rows(pairs, idx, src_rows):
         L.check(L.load().mmvae_gather_rows(C.cast(items, C.c_void_p), len(pairs), idx.data_ptr(), B, src_rows, _stream()), "mmvae_gather_rows")
 
 
+def _metrics_operand(t, name, N):
+    """(pointer, dtype, leading dimension) of a metrics operand: (M, N) with unit inner stride and any row stride >= N, fp32 or bf16."""
+    _mat(t, name)
+    if t.shape[1] != N or (t.shape[0] > 1 and t.stride(0) < N):
+        raise ValueError(f"recon_metrics: {name} is {tuple(t.shape)} / {t.stride()}, need (M, {N}) rows that do not overlap")
+    return t.data_ptr(), _dt(t), _ld(t)
+
+
+def recon_metrics(pred, target, col_shift, col_acc, row_pearson, row_cosine):
+    """One streaming pass over (prediction, target) (mmvae_recon_metrics): row_pearson / row_cosine (fp32 (M,)) are written,
+    col_acc (float64 (4, N): sum (y - c), sum (y - c)^2, sum (p - y)^2, sum |p - y| per column, c = col_shift or 0) is ACCUMULATED
+    into -- zero it once per evaluation.  target: (M, N) fp32 or bf16, unit inner stride, any row stride (padded bf16 rows included);
+    pred: the same, or a 1-D (N,) tensor = one prediction row for every sample."""
+    _mat(target, "target")
+    M, N = target.shape
+    if M < 1 or N < 1:
+        raise ValueError(f"recon_metrics: empty target {tuple(target.shape)}")
+    t_ptr, t_dt, t_ld = _metrics_operand(target, "target", N)
+    if pred.dim() == 1:
+        if not pred.is_cuda or pred.shape[0] != N or pred.stride(0) != 1:
+            raise ValueError(f"recon_metrics: a broadcast prediction must be a contiguous ({N},) device tensor, got {tuple(pred.shape)}")
+        p_ptr, p_dt, p_ld, p_rows = pred.data_ptr(), _dt(pred), 0, 1
+    else:
+        if pred.shape[0] != M:
+            raise ValueError(f"recon_metrics: prediction {tuple(pred.shape)} against target {tuple(target.shape)}")
+        p_ptr, p_dt, p_ld = _metrics_operand(pred, "pred", N)
+        p_rows = M
+    for t, name, dt, shape in ((col_shift, "col_shift", torch.float32, (N,)), (col_acc, "col_acc", torch.float64, (4, N)),
+                               (row_pearson, "row_pearson", torch.float32, (M,)), (row_cosine, "row_cosine", torch.float32, (M,))):
+        if t is None and name == "col_shift":
+            continue
+        if not t.is_cuda or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"recon_metrics: {name} must be a contiguous {dt} device tensor of shape {shape}")
+    if len({t.device for t in (pred, target, col_acc, row_pearson, row_cosine)} | ({col_shift.device} if col_shift is not None else set())) != 1:
+        raise ValueError("recon_metrics: all operands must live on one device")
+    a = L.MetricsArgs(M, N, p_ptr, p_dt, p_ld, t_ptr, t_dt, t_ld, _p(col_shift), col_acc.data_ptr(), row_pearson.data_ptr(),
+                      row_cosine.data_ptr())
+    nbytes = M * N * target.element_size() + p_rows * N * pred.element_size() + 8 * M + 2 * 32 * N + (4 * N if col_shift is not None else 0)
+    with stream_span("recon_metrics", nbytes):
+        L.check(L.load().mmvae_recon_metrics(C.byref(a), _stream()), "mmvae_recon_metrics")
+
+
 def adamw_step(items, lr, b1, b2, eps, wd, bc1, bc2, maximize=False, step_dev=None, lr_dev=None):
     """items: ctypes array of AdamWItem in host memory (device pointers inside).  step_dev: int64[CTR_COPIES] tensor of
     identical copies of the step count: bias corrections from the device counter, which the launch itself increments

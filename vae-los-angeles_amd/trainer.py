@@ -63,6 +63,13 @@ def load_pickled_dataset(path):
     return tpm, beta, site
 
 
+def split_indices(n):
+    """(val_idx, train_idx) of n samples: the one validation split of the trainers and of evaluate.py."""
+    perm = torch.randperm(n, generator=torch.Generator().manual_seed(Config.RANDOM_SEED))       # train_test_split(random_state=42) stand-in
+    n_val = int(n * Config.TRAIN_TEST_SPLIT)
+    return perm[:n_val], perm[n_val:]
+
+
 def build_parser(kind):
     ap = argparse.ArgumentParser(description=f"{KINDS[kind]['title']} trainer on MI355X")
     ap.add_argument("--data", default=None, help="processed_data.pkl produced by the reference's prepare scripts (default: synthetic)")
@@ -142,9 +149,7 @@ def run(kind, argv=None):
     if lo_ < 0 or hi_ >= args.n_sites:
         raise SystemExit(f"site labels must lie in [0, {args.n_sites}); found [{lo_}, {hi_}]")
     n = tpm.shape[0]
-    perm = torch.randperm(n, generator=torch.Generator().manual_seed(Config.RANDOM_SEED))       # train_test_split(random_state=42) stand-in
-    n_val = int(n * Config.TRAIN_TEST_SPLIT)
-    val_idx, train_idx = perm[:n_val], perm[n_val:]
+    val_idx, train_idx = split_indices(n)
     lo, hi = parallel.shard_rows(train_idx.numel(), rank, world, equal=True)   # equal shards: every rank runs the same number of steps
     tr = [t[train_idx[lo:hi]].to(dev).contiguous() for t in (tpm, beta_v, site)]
     va = [t[val_idx].to(dev).contiguous() for t in (tpm, beta_v, site)]
