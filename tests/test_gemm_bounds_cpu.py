@@ -391,3 +391,266 @@ def test_derived_statistics_bound_is_below_the_tolerance_it_replaces_in_test_gem
                 present = 1e-2 + 1e-4 * np.abs(G.stats_ref(c))
                 worst_ratio = max(worst_ratio, float((G.stats_tol(c, G.ROWS_TILE) / present).max()))
     assert worst_ratio <= 1.0, worst_ratio
+
+
+# =============================================================================================
+# the epilogue rules of tests/gemm_bounds.py (sigmoid / accumulate, ReLU mask, BatchNorm backward, loss epilogues, f32-atomic dW,
+# row blocks): float32 restatements hold under the three summation orders, deliberate mistakes fall outside.  The inputs come from
+# tests/gemm_cases.py, the generators of the GPU tests, at GPU shapes.
+# =============================================================================================
+import gemm_cases as GC  # noqa: E402
+
+EPI_SHAPES = [(31, 130, 20), (128, 40, 77), (389, 136, 256), (333, 200, 128)]
+
+
+def nt_setup(M, N, K, bf16=True, w_scale=None):
+    rng = np.random.default_rng(M + 3 * N + 7 * K)
+    a, w, bias = GC.nt_case(rng, M, N, K, w_scale)
+    if bf16:
+        a, w = O.bf16_round(a), O.bf16_round(w)
+    return rng, a, w, bias, G.nt_ref(a, w, bias), G.nt_tol(a, w, bias)
+
+
+def sigmoid32(x):
+    with np.errstate(over="ignore"):
+        return F32(1) / (F32(1) + np.exp2(-np.asarray(x, F32) * F32(G.LOG2E32)))
+
+
+def ln32(x):
+    with np.errstate(divide="ignore"):
+        return np.log2(np.asarray(x, F32)) * F32(0.6931471805599453)
+
+
+@pytest.mark.parametrize("order", ORDERS)
+@pytest.mark.parametrize("M,N,K", EPI_SHAPES)
+def test_sigmoid_and_accumulate_bounds_hold_and_see_the_activation_before_the_bias(M, N, K, order):
+    rng, a, w, bias, ref, tol = nt_setup(M, N, K, w_scale=6.0 * K ** -0.5)           # saturated logits included
+    assert np.abs(ref).max() > 17
+    x32 = nt32(a, w, bias, order)
+    p, tp = G.sigmoid(ref), G.sigmoid_tol(ref, tol)
+    holds(sigmoid32(x32), p, tp, "sigmoid")
+    holds(O.bf16_round(sigmoid32(x32)), p, G.bf16_out(tp, p), "sigmoid, bf16 out")
+    old = rnd(rng, M, N)
+    holds(old + x32, old.astype(F64) + ref, G.accumulate_tol(tol, ref, old), "C += acc + bias")
+    wrong = sigmoid32(nt32(a, w, None, order)) + bias[None, :]
+    bites(wrong, p, tp, "sigmoid applied before the bias")
+    # tail-only columns and the small rows are held by their own terms: a dropped last K chunk is outside in exactly those columns
+    drop = nt32(a[:, :K - 8], w[:, :K - 8], bias, order)
+    for j in GC.nt_tail_rows(N, K):
+        bites(drop[:, j], ref[:, j], tol[:, j], f"tail-only column {j}, last K chunk dropped")
+    bites(sigmoid32(drop)[GC.small_rows(M)], p[GC.small_rows(M)], tp[GC.small_rows(M)], "small rows through the sigmoid, last K chunk dropped")
+
+
+def epi_setup(M, N, K):
+    rng, a, w, bias, ref, tol = nt_setup(M, N, K)
+    e = GC.epi_case(rng, M, N)
+    e["h"], e["y"] = O.bf16_round(e["h"]), O.bf16_round(e["y"])
+    acc, tol = G.nt_ref(a, w, None), G.nt_tol(a, w, None)
+    return rng, a, w, acc, tol, e
+
+
+def bn_bwd32(acc32, e, masked, gate_y=False, no_inv_keep=False):
+    """EpiBnBwd::compute in float32 -> (d, xhat)."""
+    y = e["y"]
+    keep = e["mask"].astype(F32) * (F32(1) if no_inv_keep else F32(1.0 / 0.9)) if masked else F32(1)
+    gate = (y > 0) if gate_y else (y * e["scale"] + e["shift"] > 0)
+    d = np.where(gate, acc32 * keep, F32(0)).astype(F32)
+    return d, (y - e["mean"]) * e["rstd"]
+
+
+def colsums32(v, rows=G.ROWS_TILE):
+    """fp32 partial sums over `rows` rows, added in float64."""
+    s = np.zeros(v.shape[1])
+    for r0 in range(0, v.shape[0], rows):
+        part = np.zeros(v.shape[1], F32)
+        for r in range(r0, min(r0 + rows, v.shape[0])):
+            part = part + v[r]
+        s += part.astype(F64)
+    return s
+
+
+def shifted(x, by):
+    """Rows read one row block early: row r holds what belongs to row r - by (the first block is read correctly)."""
+    out = x.copy()
+    out[by:] = x[:-by]
+    return out
+
+
+@pytest.mark.parametrize("order", ORDERS)
+@pytest.mark.parametrize("M,N,K", EPI_SHAPES)
+def test_relu_mask_bound_holds_and_bites(M, N, K, order):
+    rng, a, w, acc, tol, e = epi_setup(M, N, K)
+    acc32 = nt32(a, w, None, order)
+    ref, t = G.relu_mask(acc, tol, e["h"])
+    tb = G.bf16_out(t, ref)
+    holds(O.bf16_round(np.where(e["h"] > 0, acc32, F32(0))), ref, tb, "ReLU mask")
+    assert (e["h"] == 0).any() and (tb[e["h"] == 0] == 0).all()
+    bites(O.bf16_round(np.where(e["h"] >= 0, acc32, F32(0))), ref, tb, "h >= 0 for h > 0")
+    if M > 64:
+        bites(O.bf16_round(np.where(shifted(e["h"], 32) > 0, acc32, F32(0))), ref, tb, "h read one row block early")
+
+
+@pytest.mark.parametrize("order", ORDERS)
+@pytest.mark.parametrize("masked", [True, False], ids=["mask", "nomask"])
+@pytest.mark.parametrize("M,N,K", EPI_SHAPES)
+def test_bn_bwd_epilogue_bounds_hold_and_bite(M, N, K, masked, order):
+    rng, a, w, acc, tol, e = epi_setup(M, N, K)
+    acc32 = nt32(a, w, None, order)
+    mask = e["mask"] if masked else None
+    ik = 1.0 / 0.9 if masked else 1.0
+    dref, dtol, share = G.bn_bwd_d(acc, tol, e["y"], e["scale"], e["shift"], mask, ik)
+    assert share < 0.02                                                     # the at-risk cap of the GPU cases, same generator
+    d32, xh32 = bn_bwd32(acc32, e, masked)
+    holds(d32, dref, dtol, "d"); holds(O.bf16_round(d32), dref, G.bf16_out(dtol, dref), "d, bf16 out (phase 2)")
+    sref, stol = G.bn_bwd_stats(dref, e["y"], e["mean"], e["rstd"]), G.bn_bwd_stats_tol(dref, dtol, e["y"], e["mean"], e["rstd"])
+    holds(np.stack([colsums32(d32), colsums32(d32 * xh32)]), sref, stol, "sum d, sum d xhat")
+    c = e["coef"]
+    p1ref, p1tol = E.bn_bwd_apply(dref, e["y"], e["mean"], e["rstd"], c, F64), G.bn_bwd_phase1_tol(dref, dtol, e["y"], e["mean"], e["rstd"], c)
+    holds(c[0] * (d32 - c[1] - xh32 * c[2]), p1ref, p1tol, "phase 1")
+    holds(O.bf16_round(c[0] * (d32 - c[1] - xh32 * c[2])), p1ref, G.bf16_out(p1tol, p1ref), "phase 1, bf16 out")
+    # the mistakes
+    bites(bn_bwd32(acc32, e, masked, gate_y=True)[0], dref, dtol, "gate on y > 0")
+    if masked:
+        bites(bn_bwd32(acc32, e, masked, no_inv_keep=True)[0], dref, dtol, "keep without inv_keep")
+        if M > 64:
+            wrong = np.where(e["y"] * e["scale"] + e["shift"] > 0, acc32 * shifted(e["mask"], 32).astype(F32) * F32(1.0 / 0.9), F32(0))
+            bites(wrong, dref, dtol, "mask read one row block early")
+    bites(colsums32(d32 * e["y"]), sref[1], stol[1], "sum d y for sum d xhat")
+    bites(c[0] * (d32 - xh32 * c[2]), p1ref, p1tol, "phase 1 without c1")
+
+
+def test_bn_bwd_gate_marks_the_elements_within_its_own_rounding_of_zero():
+    """y sc + sh exactly 0 in float64 and one float32 ulp to either side: at risk, allowance the whole |acc keep|; 1e-3 away: not."""
+    sc, sh = np.array([1.5], F32), np.array([-0.75], F32)
+    y = np.array([[0.5], [np.nextafter(F32(0.5), F32(1))], [np.nextafter(F32(0.5), F32(0))], [0.501], [0.499]], F32)
+    gate, risk = G.bn_bwd_gate(y, sc, sh)
+    assert risk[:3, 0].all() and not risk[3:, 0].any() and gate[3, 0] and not gate[4, 0]
+    acc = np.full((5, 1), 3.0)
+    d, tol, share = G.bn_bwd_d(acc, 1e-6, y, sc, sh, None, 1.0)
+    assert (tol[:3] >= 3.0).all() and (tol[3] < 1e-5) and tol[4] == 0 and share == 0.6
+
+
+LOSS_SHAPES = [(300, 333, 128), (389, 782, 128), (130, 572, 256)]
+
+
+def loss32(x32, t, bce, clamp=True, wrt_p=False):
+    """EpiLoss::term in float32 -> (gradient, terms)."""
+    t = np.asarray(t, F32)
+    if not bce:
+        d = x32 - t
+        return F32(2) * d, d * d
+    pe = sigmoid32(x32)
+    om = F32(1) - pe
+    lp, l1p = ln32(pe), ln32(om)
+    if clamp:
+        lp, l1p = np.maximum(lp, F32(-100)), np.maximum(l1p, F32(-100))
+    d = pe - t
+    with np.errstate(invalid="ignore", over="ignore"):
+        g = d / np.maximum(om * pe, F32(1e-12)) if wrt_p else d * np.minimum(om * pe * F32(1e12), F32(1))
+        term = -(t * lp + (F32(1) - t) * l1p)
+    return g, term
+
+
+def loss_sum32(terms):
+    """fp32 partial sums of G.LOSS_TERMS terms in sequence, added in float64."""
+    v = terms.reshape(-1)
+    s = 0.0
+    for i in range(0, v.size, G.LOSS_TERMS):
+        s += float(np.add.accumulate(v[i:i + G.LOSS_TERMS], dtype=F32)[-1])
+    return s
+
+
+@pytest.mark.parametrize("order", ORDERS)
+@pytest.mark.parametrize("bce", [False, True], ids=["mse", "bce"])
+@pytest.mark.parametrize("M,N,K", LOSS_SHAPES)
+def test_loss_epilogue_bounds_hold_and_bite(M, N, K, bce, order):
+    rng, a, w, bias, ref, tol = nt_setup(M, N, K, w_scale=(8.0 if bce else 1.0) * K ** -0.5)
+    t = GC.loss_case(rng, M, N, bce)
+    if bce:      # logits saturate on both sides of both hard target values
+        hard = ref[:M // 2]
+        assert all(((hard * s > 17.5) & (t[:M // 2] == v)).any() for s in (1, -1) for v in (0, 1))
+    gref, gtol, lref, ltol = (G.bce_epilogue if bce else G.mse_epilogue)(ref, tol, t)
+    gtol = G.bf16_out(gtol, gref)
+    x32 = nt32(a, w, bias, order)
+    g32, l32 = loss32(x32, t, bce)
+    holds(O.bf16_round(g32), gref, gtol, "gradient")
+    holds(l32, lref, ltol, "terms")
+    sref, stol = float(lref.sum()), G.loss_sum_tol(lref, ltol)
+    assert abs(loss_sum32(l32) - sref) <= stol
+    # the target read one row block early
+    gw, lw = loss32(x32, shifted(t, 32), bce)
+    bites(O.bf16_round(gw), gref, gtol, "target read one row block early (gradient)")
+    # BCE: the sum cannot see this mistake at any shape.  Its bound carries, for every saturated logit, the distance of L1P (or LP) at
+    # fl32(p +- tol_p) to the clamp -- tens per element -- while a row shift of targets that are independent of the logits changes
+    # the sum only by the scatter of its terms; the gradient rows above carry the bite for BCE.
+    if not bce:
+        assert abs(loss_sum32(lw) - sref) > stol, "target read one row block early (MSE sum)"
+    if bce:
+        gw, lw = loss32(x32, t, True, clamp=False)
+        bites(lw, lref, ltol, "log clamp missing")
+        assert not abs(loss_sum32(lw) - sref) <= stol
+        bites(O.bf16_round(loss32(x32, t, True, wrt_p=True)[0]), gref, gtol, "gradient with respect to p")
+        # float64 mathematics is the wrong reference: a saturated wrong prediction costs 100, not |x|
+        sat = (ref > 17.5) & (t == 0)
+        assert (lref[sat] == 100).all() and (np.log1p(np.exp(ref[sat])) < 60).all()
+
+
+DW_EDGE = [(130, 24, 64, None), (333, 128, 96, None), (1000, 40, 128, 352), (16384, 24, 36, 2048)]
+
+
+@pytest.mark.parametrize("order", ORDERS)
+@pytest.mark.parametrize("M,N,K,rps", DW_EDGE)
+def test_dw_atomics_bound_holds_and_the_tail_only_columns_see_a_dropped_row_at_any_batch_size(M, N, K, rps, order):
+    """The f32-atomics form (no slab; row blocks): the old value is one of the terms.  The tail-only columns of tests/gemm_cases.py are
+    zero outside the last 32-row step of the last split, so their bound counts 32 rows' terms at most: the dropped last row that
+    test_dw_bound_sees_a_dropped_last_row_of_a_short_split records as invisible at M = 16 384 is outside here."""
+    rng = np.random.default_rng(M + N + K)
+    tail = GC.dw_tail(M, rps)
+    p, q = (O.bf16_round(x) for x in GC.dw_case(rng, M, N, K, tail))
+    old_dw, old_db = rnd(rng, N, K), rnd(rng, N)
+    rw, rb = G.dw_ref(p, q, old_dw, old_db)
+    tw, tb = G.dw_tol(p, q, old_dw, old_db, atomics=True)
+    slab = G.dw_tol(p, q, old_dw, old_db)
+    assert (tw >= slab[0]).all() and (tb >= slab[1]).all()
+    gw, gb = dw32(p, q, old_dw, old_db, order, rps or 64)
+    holds(gw, rw, tw, "dW, atomics"); holds(gb, rb, tb, "db")
+    # row blocks: every block adds onto what the earlier ones left
+    half = M // 2
+    w1, b1 = dw32(p[:half], q[:half], old_dw, old_db, order, rps or 64)
+    w2, b2 = dw32(p[half:], q[half:], w1, b1, order, rps or 64)
+    holds(w2, rw, tw, "dW in two row blocks"); holds(b2, rb, tb, "db in two row blocks")
+    # mistakes
+    dw_, db_ = dw32(p[:-1], q[:-1], old_dw, old_db, order, rps or 64)
+    for c in (1 % N, N - 1):
+        bites(dw_[c], rw[c], tw[c], f"dW row {c} (tail-only P column), last row dropped")
+    for c in (2 % K, K - 1):
+        bites(dw_[:, c], rw[:, c], tw[:, c], f"dW column {c} (tail-only Q column), last row dropped")
+    bites(db_[[1 % N, N - 1]], rb[[1 % N, N - 1]], tb[[1 % N, N - 1]], "db of the tail-only P columns, last row dropped")
+    pad = gb.copy()
+    pad[N - 1] += F32(7.0 * M)                                              # the 7.0 pad column of P summed into the last db element
+    bites(pad, rb, tb, "db that includes a pad column")
+    # P read one row block early in the second block
+    w3, _ = dw32(shifted(p, 32)[half:], q[half:], w1, b1, order, rps or 64)
+    bites(w3, rw, tw, "P read one row block early")
+
+
+@pytest.mark.parametrize("M", [389, 1000])
+def test_at_risk_cap_of_the_gpu_operand_prologues(M):
+    """The at-risk share that tests/test_gemm_gpu.py asserts (< 2 %) on the inputs of its own generators: the BatchNorm + ReLU +
+    Dropout prologue of the NT row-block case (dh) and the BatchNorm-corrected P of the dW row-block case (dp)."""
+    K = 256
+    rng = np.random.default_rng(M)
+    y, _, _ = GC.nt_case(rng, M, 136, K)
+    scale, shift = rng.uniform(0.5, 1.5, K).astype(F32), GC.rnd(rng, K, scale=0.3)
+    mask = (rng.random((M, K)) < 0.9).astype(np.uint8)
+    _, dh = G.prologue_operand(G.q_bf16(y), scale, shift, 1.0 / 0.9, mask, True)
+    assert (dh > 0).mean() < 0.02
+    Mw, N, Kw = 1000, 256, 150
+    rng = np.random.default_rng(17)
+    d, _ = GC.dw_case(rng, Mw, N, Kw)
+    y = GC.rnd(rng, Mw, N, scale=2.0) + F32(0.3)
+    mean, rstd = GC.rnd(rng, N, scale=0.2), rng.uniform(0.5, 1.5, N).astype(F32)
+    coef = np.stack([rng.uniform(0.5, 1.5, N), rng.standard_normal(N) * 0.1, rng.standard_normal(N) * 0.1]).astype(F32)
+    d, y = G.q_bf16(d), G.q_bf16(y)
+    _, dp = G.operand_risk(E.bn_bwd_apply(d, y, mean, rstd, coef, np.float64), E.bn_bwd_apply_tol(d, y, mean, rstd, coef), True)
+    assert (dp > 0).mean() < 0.02

@@ -193,7 +193,7 @@ def test_reconstruction_loss_inside_the_decoder_gemms(B, weighted):
 
 
 @pytest.mark.parametrize("M,N,K,bce", [(1000, 782, 128, False), (777, 572, 512, True), (300, 333, 256, True), (4096, 128, 192, False),
-                                       # >= 16 384 rows, >= 8 K steps, 16-byte target rows: the software-pipelined kernel (gemm_nt2x.h) -- ragged last row
+                                       # >= 16 384 rows, >= 8 K steps, 16-byte target rows: more tiles than the persistent grid of the LDS-DMA kernel has workgroups (gemm_nt2.h), each going through several -- ragged last row
                                        # tile (16 640 = 65 x 256), ragged last column tile (572, 332), 8 / 10 / 9 K steps
                                        (16640, 572, 512, True), (16384, 332, 600, False), (32768, 128, 576, True)])
 def test_loss_epilogue_against_store_epilogue_plus_loss_kernel(M, N, K, bce):
@@ -275,3 +275,39 @@ def test_class_term_out_of_range_labels_are_counted(S):
     assert sums[4].item() == float(len(bad))
     np.testing.assert_allclose(sums[2].item(), ref.item(), rtol=2e-6)
     np.testing.assert_allclose(gc.cpu().numpy(), 0.5 * lr.grad.numpy(), atol=2e-6)
+
+
+LOSS_EPI_CASES = [  # M, N, K, bce, target kind, target row stride (None: N)
+    (300, 333, 256, True, "f32", None),          # 4-byte aligned fp32 rows
+    (300, 333, 256, True, "bf16", None),         # 2-byte aligned bf16 rows
+    (389, 782, 128, False, "f32", None),         # 8-byte aligned fp32 rows
+    (389, 782, 128, False, "bf16", 784),         # 16-byte aligned bf16 rows (the padded-row layout)
+    (777, 572, 512, True, "f32", None),          # 16-byte aligned fp32 rows
+    (777, 572, 512, True, "bf16", 574),          # 4-byte aligned bf16 rows
+    (389, 782, 128, False, "bf16", 788),         # 8-byte aligned bf16 rows
+    # one case of >= 16 384 rows per loss: more 128 x 128 tiles (130 x 5, 128 x 5) than the 512 workgroups of the persistent grid
+    # (launch_nt2, gemm_nt2.h), so workgroups go through several tiles -- the ring, the epilogue's column operands and its reduction
+    # scratch are reused after a loss epilogue; ragged last row tile (16 640 = 130 x 128) and last column tile (572, 600)
+    (16640, 572, 512, True, "f32", None),
+    (16384, 600, 128, False, "f32", None),
+]
+
+
+@pytest.mark.parametrize("M,N,K,bce,kind,ldt", LOSS_EPI_CASES)
+def test_loss_epilogue_against_float64(M, N, K, bce, kind, ldt):
+    """MMVAE_EPI_LOSS_MSE / MMVAE_EPI_LOSS_BCE_LOGIT against an independent float64 reference, element by element inside the derived
+    bounds of tests/gemm_bounds.py (mse_epilogue / bce_epilogue / loss_sum_tol): the gradient rows incl. zeroed pad columns and guards,
+    and the f64 loss sum.  BCE: hard targets in the first half of the rows, fractional ones in the second; logits of standard
+    deviation 4 plus two bias columns of +-20 saturate the sigmoid on both sides of both target values; the reference takes the logs
+    of the FP32 p, as torch and the kernel do.  Targets fp32 and bf16 at 16-, 8-, 4- and 2-byte aligned rows, pad columns NaN."""
+    import gemm_cases as GC
+    from gemm_gpu_util import NtCase, check_loss_epilogue, loss_target, tuning
+    from mmvae.ops import PREC_BF16
+    case = NtCase(PREC_BF16, M, N, K, "bf16", w_scale=(4.0 if bce else 1.0) * K ** -0.5)
+    assert M < 16384 or -(-M // 128) * -(-N // 128) > 512                        # the large cases: several tiles per workgroup
+    T, t_host = loss_target(GC.loss_case(case.rng, M, N, bce), kind, ldt)
+    if bce:
+        hard, x = t_host[:M // 2], case.ref[:M // 2]
+        assert all(((x * s > 17.5) & (hard == v)).any() for s in (1, -1) for v in (0, 1))
+    with tuning(k8=0):
+        check_loss_epilogue(case, bce, T, t_host, f"loss epilogue {'BCE' if bce else 'MSE'} target {kind} ld {ldt or N} {case.tag}")
