@@ -47,7 +47,8 @@ int mmvae_abi_version(void);    /* bumped on any struct change; the ctypes bindi
  * that tests reach that path at moderate sizes; key 4 = wide-tile kernel for the large weight gradients (gemm_tn_wide.hip) on/off;
  * key 6 / key 7 = row-coalesced LDS form of the BatchNorm-backward / ReLU-mask dX epilogue on/off; key 8 = wave-specialised NT kernel
  * (gemm_ntp.h: producer / consumer waves) on/off, key 9 = its minimum M (default 16384); key 10 = the fused latent launch
- * (mmvae_latent_fwd) on/off: off, it returns MMVAE_ERR_ARG and the caller issues the launches it replaces.  Other keys: MMVAE_ERR_ARG. */
+ * (mmvae_latent_fwd) on/off: off, it returns MMVAE_ERR_ARG and the caller issues the launches it replaces; key 12 = the fused class-head
+ * launch (mmvae_class_tail) on/off, in the same way.  Other keys: MMVAE_ERR_ARG. */
 int mmvae_set_tuning(int32_t key, int32_t value);
 
 /* ---------------------------------------------------------------------------------------------
@@ -305,6 +306,44 @@ typedef struct {
     void* h0; int64_t ldh0;
 } mmvae_latent_fwd_args;
 int mmvae_latent_fwd(const mmvae_latent_fwd_args* args, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The class head of the training step in ONE launch (class_tail.hip): the class decoder's last Linear, the weighted cross-entropy
+ * and KL terms of vae_loss with their gradients, and the back-propagation through that Linear and the ReLU in front of it, per
+ * 16-row slab without leaving the CU --
+ *   logits = h0 x W^T + bias                    (mmvae_gemm_nt on the bf16 hidden activation, K ascending; fp32, NOT stored)
+ *   sums[2] += sum_i w[site_i] * nll_i, sums[4] += labels outside [0, S), g_c = gamma * w[y] * (softmax - onehot)   (fp32, stored)
+ *   d0 = (h0 > 0) ? bf16(g_c) x W : 0           (mmvae_gemm_nt with MMVAE_EPI_RELU_MASK on the fp32 g_c; bf16, whole rows of d0)
+ *   sums[3] += KL, g_mu = beta * mu, g_lv = -0.5 * beta * (1 - exp(logvar))
+ * i.e. what mmvae_gemm_nt (the Linear), mmvae_vae_loss with only logits / mu / logvar given and mmvae_gemm_nt (its dX) compute:
+ * g_c, d0, g_mu, g_lv and the count in sums[4] bit for bit, sums[2] and sums[3] up to the order of their f64 additions.
+ *   h0 / d0: the class decoder's 64 columns of the merged hidden activation and of its gradient (column slices: ldh0 / ldd0 are the
+ *   leading dimensions of the whole buffers).  w: prepared weight ([>= 32][ldw] bf16, rows >= S zero); wt: its prepared transpose
+ *   ([>= 64][ldwt] bf16, columns >= S zero) -- what mmvae_prep_weights writes.  class_weights: fp32 [S] or NULL.  mu / logvar /
+ *   g_mu / g_lv: CONTIGUOUS [B][L] fp32.  beta_gamma_dev as in mmvae_loss_args.  sums: double[5] as mmvae_vae_loss.
+ * Limits (anything else: MMVAE_ERR_ARG before anything is enqueued; the caller then issues the three launches):
+ *   prec == MMVAE_PREC_BF16; hidden == 64; 4 <= S <= 32 and S % 4 == 0 (the row-per-thread class path
+ *   of mmvae_vae_loss, whose arithmetic this is); 1 <= L <= 24; B >= 1 and B * max(L, S) < 2^31; every pointer but class_weights and
+ *   beta_gamma_dev given; h0 16-byte aligned, ldh0 % 8 == 0, ldh0 >= 64; d0 rows are whole 128-byte lines (128-byte aligned,
+ *   ldd0 % 64 == 0); w and wt 16-byte aligned, ldw % 8 == 0, ldw >= 64, ldwt % 8 == 0, ldwt >= 32; g_c 16-byte aligned,
+ *   ld_gc % 4 == 0, ld_gc >= S; tuning key 12 on (mmvae_set_tuning).
+ * mmvae_class_tail_fits answers the shape part of these limits (and the tuning key) without operands: 0, or the error
+ * mmvae_class_tail would return.  A forward that wants to leave the Linear to this launch asks it first.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t prec, B, S, L, hidden;
+    const void* h0; int64_t ldh0;
+    const void* w; int64_t ldw; const void* wt; int64_t ldwt; const float* bias;
+    const int64_t* site; const float* class_weights;
+    const float* mu; const float* logvar;
+    float beta, gamma; const float* beta_gamma_dev;
+    double* sums;
+    float* g_c; int64_t ld_gc;
+    void* d0; int64_t ldd0;
+    float* g_mu; float* g_lv;
+} mmvae_class_tail_args;
+int mmvae_class_tail(const mmvae_class_tail_args* args, void* stream);
+int mmvae_class_tail_fits(int32_t prec, int32_t S, int32_t hidden, int32_t L, int64_t ldh0, int64_t ldd0);
 
 /* ---------------------------------------------------------------------------------------------
  * vae_loss (src/utils/losses.py:8-46) and the directional losses

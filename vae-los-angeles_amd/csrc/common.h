@@ -212,6 +212,7 @@ struct Tuning {
     int ntp_on = 1;                  // key 8: the wave-specialised NT kernel (gemm_ntp.h)
     int ntp_min_m = 16384;           // key 9: below this a persistent 256-workgroup grid has < 1 tile per CU
     int latent_on = 1;               // key 10: the fused latent launch (latent.hip); off: mmvae_latent_fwd answers MMVAE_ERR_ARG
+    int class_tail_on = 1;           // key 12: the fused class-head launch (class_tail.hip); off: mmvae_class_tail answers MMVAE_ERR_ARG
 };
 inline Tuning g_tuning;
 

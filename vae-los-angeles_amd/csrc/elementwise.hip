@@ -7,6 +7,7 @@
 #include "common.h"
 #include "mmvae_hip.h"
 #include "fuse_math.h"
+#include "loss_terms.h"
 
 namespace mm {
 
@@ -456,6 +457,7 @@ __global__ __launch_bounds__(256) void vae_loss_kernel(mmvae_loss_args a, int ce
     if (a.beta_gamma_dev) { a.beta = a.beta_gamma_dev[0]; a.gamma = a.beta_gamma_dev[1]; }     // hyper-parameters a captured graph can change
     const long tid0 = (long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long)gridDim.x * blockDim.x;
     float s[4] = {0.f, 0.f, 0.f, 0.f};
+    double ds[2] = {0.0, 0.0};       // TAIL: the class / KL terms, widened one by one
     float n_bad = 0.f;
     if (!TAIL && a.recon_a) s[0] = mse_part<GT, VA, TA>(a, tid0, stride);
     if (!TAIL && a.recon_b) s[1] = bce_part<GT, VD, TB>(a, tid0, stride);
@@ -473,23 +475,21 @@ __global__ __launch_bounds__(256) void vae_loss_kernel(mmvae_loss_args a, int ce
             f32x4 x[8];
 #pragma unroll
             for (int c = 0; c < 8; ++c) x[c] = c < nv ? lp[c] : f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-            long y = a.site[r];
-            const bool ign = y == -100;                      // ignore_index, as below
-            const bool bad = !ign && (y < 0 || y >= a.S);
-            if (bad || ign) y = 0;
-            const float w = ign ? 0.f : (a.class_weights ? a.class_weights[y] : 1.f);
+            const CeLabel lb = ce_label(a.site[r], a.S, a.class_weights);      // the row's arithmetic: loss_terms.h
+            const int y = lb.y;
+            const float w = lb.w;
             float m = -INFINITY, xy = 0.f;
 #pragma unroll
             for (int c = 0; c < 8; ++c)
 #pragma unroll
-                for (int j = 0; j < 4; ++j) { m = fmaxf(m, x[c][j]); xy = (c * 4 + j == (int)y) ? x[c][j] : xy; }
+                for (int j = 0; j < 4; ++j) { m = fmaxf(m, x[c][j]); xy = (c * 4 + j == y) ? x[c][j] : xy; }
             float se = 0.f;
 #pragma unroll
             for (int c = 0; c < 8; ++c)
 #pragma unroll
-                for (int j = 0; j < 4; ++j) { const float e = c < nv ? expf(x[c][j] - m) : 0.f; x[c][j] = e; se += e; }
-            s[2] += w * (m + logf(se) - xy);
-            if (bad) n_bad += 1.f;
+                for (int j = 0; j < 4; ++j) { const float e = c < nv ? ce_exp(x[c][j], m) : 0.f; x[c][j] = e; se += e; }
+            if constexpr (TAIL) ds[0] += (double)ce_term(w, m, se, xy); else s[2] += ce_term(w, m, se, xy);
+            if (lb.bad) n_bad += 1.f;
             if (a.g_c) {
                 f32x4* gp = (f32x4*)(a.g_c + r * a.ld_gc);
                 const float gw = a.gamma * w;
@@ -498,7 +498,7 @@ __global__ __launch_bounds__(256) void vae_loss_kernel(mmvae_loss_args a, int ce
                     if (c >= nv) break;
                     f32x4 g;
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) g[j] = gw * (x[c][j] / se - (c * 4 + j == (int)y ? 1.f : 0.f));
+                    for (int j = 0; j < 4; ++j) g[j] = ce_grad(gw, x[c][j], se, c * 4 + j == y);
                     gp[c] = g;
                 }
             }
@@ -580,15 +580,30 @@ __global__ __launch_bounds__(256) void vae_loss_kernel(mmvae_loss_args a, int ce
             for (int u = 0; u < KL_U; ++u) {
                 const long i = i0 + u * stride;
                 if (i >= total) break;
-                const float ex = expf(lv[u]);
-                s[3] += -0.5f * (1.f + lv[u] - mu[u] * mu[u] - ex);
-                if (a.g_mu) a.g_mu[i] = a.beta * mu[u];
-                if (a.g_lv) a.g_lv[i] = -0.5f * a.beta * (1.f - ex);
+                float gm, gl;
+                const float t = kl_elem(mu[u], lv[u], a.beta, gm, gl);             // loss_terms.h
+                if constexpr (TAIL) ds[1] += (double)t; else s[3] += t;
+                if (a.g_mu) a.g_mu[i] = gm;
+                if (a.g_lv) a.g_lv[i] = gl;
             }
         }
     }
-    __shared__ float red[4][5];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    if constexpr (TAIL) {
+        // class + KL alone: every term is widened to f64 before it is added, as the fused class-head launch does (class_tail.hip):
+        // the two forms' sums then differ only by the order of f64 additions
+        __shared__ double redd[4][3];
+        const double vc = wave_sum_f64(ds[0] + (double)s[2]), vk = wave_sum_f64(ds[1]);
+        const float vb = wave_sum(n_bad);
+        if (lane == 0) { redd[wid][0] = vc; redd[wid][1] = vk; redd[wid][2] = (double)vb; }
+        __syncthreads();
+        if (threadIdx.x < 3) {
+            const double v = redd[0][threadIdx.x] + redd[1][threadIdx.x] + redd[2][threadIdx.x] + redd[3][threadIdx.x];
+            if (v != 0.0) unsafeAtomicAdd(a.sums + 2 + threadIdx.x, v);
+        }
+        return;
+    }
+    __shared__ float red[4][5];
 #pragma unroll
     for (int k = 0; k < 4; ++k) { const float v = wave_sum(s[k]); if (lane == 0) red[wid][k] = v; }
     { const float v = wave_sum(n_bad); if (lane == 0) red[wid][4] = v; }

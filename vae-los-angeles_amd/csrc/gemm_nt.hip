@@ -396,6 +396,7 @@ extern "C" int mmvae_set_tuning(int32_t key, int32_t value) {
     case 8: t.ntp_on = value; return 0;
     case 9: t.ntp_min_m = value; return 0;
     case 10: t.latent_on = value; return 0;
+    case 12: t.class_tail_on = value; return 0;
     }
     return MMVAE_ERR_ARG;
 }

@@ -98,6 +98,19 @@ class LatentFwdArgs(C.Structure):
                 ("h0", vp), ("ldh0", i64)]
 
 
+class ClassTailArgs(C.Structure):
+    _fields_ = [("prec", i32), ("B", i32), ("S", i32), ("L", i32), ("hidden", i32),
+                ("h0", vp), ("ldh0", i64),
+                ("w", vp), ("ldw", i64), ("wt", vp), ("ldwt", i64), ("bias", vp),
+                ("site", vp), ("class_weights", vp),
+                ("mu", vp), ("logvar", vp),
+                ("beta", f32), ("gamma", f32), ("beta_gamma_dev", vp),
+                ("sums", vp),
+                ("g_c", vp), ("ld_gc", i64),
+                ("d0", vp), ("ldd0", i64),
+                ("g_mu", vp), ("g_lv", vp)]
+
+
 class FuseBwdArgs(C.Structure):
     _fields_ = [("B", i32), ("L", i32), ("n_mod", i32),
                 ("g_mu", vp), ("g_lv", vp), ("dz", vp), ("dz2", vp), ("dz3", vp), ("lddz", i64),
@@ -135,7 +148,7 @@ class AdamWItem(C.Structure):
     _fields_ = [("p", vp), ("g", vp), ("m", vp), ("v", vp), ("n", i64)]
 
 
-# name -> (argtypes); every function returns int and takes the stream last
+# name -> (argtypes); every function returns int; those that launch take the stream last
 _SIGNATURES = {
     "mmvae_set_tuning": [i32, i32],
     "mmvae_prep_weights": [vp, i32, vp],
@@ -152,6 +165,8 @@ _SIGNATURES = {
     "mmvae_fuse_reparam_fwd": [C.POINTER(FuseFwdArgs), vp],
     "mmvae_fuse_reparam_bwd": [C.POINTER(FuseBwdArgs), vp],
     "mmvae_latent_fwd": [C.POINTER(LatentFwdArgs), vp],
+    "mmvae_class_tail": [C.POINTER(ClassTailArgs), vp],
+    "mmvae_class_tail_fits": [i32, i32, i32, i32, i64, i64],
     "mmvae_vae_loss": [C.POINTER(LossArgs), vp],
     "mmvae_loss_finalize": [vp, f32, f32, vp, vp, vp],
     "mmvae_recon_metrics": [C.POINTER(MetricsArgs), vp],

@@ -216,6 +216,25 @@ class LossGrads:
 
 
 @dataclass(slots=True, eq=False)
+class ClassTail:
+    """The class decoder's last Linear, left out of the forward for the fused class-head launch (ops.class_tail): the loss runs it
+    with the class / KL terms and the Linear's dX in one launch, or -- where the library refuses -- issues the Linear itself."""
+    index: int                          # which decoder
+    head: object                        # its last layer's PreparedLinear
+    h0: torch.Tensor                    # (B, 64) its hidden activation: a column slice of the merged stems' output
+    d0: torch.Tensor                    # (B, stem.N) gradient w.r.t. the merged stems' output, allocated with the step state
+    d0_slice: torch.Tensor              # this decoder's columns of d0
+    name: str                           # the decoder's name, for the launch tags
+    done: bool = False                  # the fused launch ran: d0_slice holds the gradient, the backward skips the Linear's dX
+
+    def logits(self, prec):
+        """The launch the forward left out -> fp32 (B, S)."""
+        out = torch.empty(self.h0.shape[0], self.head.N, dtype=torch.float32, device=self.h0.device)
+        ops.gemm_nt(prec, self.h0, self.head.w, self.head.N, self.head.K, out, bias=self.head.bias, act=ACT_NONE, tag=f"{self.name}.L1.fwd")
+        return out
+
+
+@dataclass(slots=True, eq=False)
 class StepZeros:
     """Everything one step needs zeroed, in the order of its regions inside ONE allocation (VAEGraph.zero_pack).  The forward half
     is the first two fields (loss_ws only when a backward follows), the backward half the last three."""
@@ -243,6 +262,7 @@ class StepState:
     zeros: Optional[StepZeros] = None   # the forward's memset when a backward follows; dropped where the backward starts
     fused: Optional[FusedRecon] = None
     loss_grads: Optional[LossGrads] = None
+    class_tail: Optional[ClassTail] = None
     consumed: bool = False              # the backward ran: buffers are not retained
 
 
@@ -488,11 +508,12 @@ class DecoderMLP:
             h = out
         return h, acts
 
-    def backward(self, prec, acts, out, g_out, g_is_logit_grad, dz, grads, tn=ops.gemm_tn, d0_out=None):
+    def backward(self, prec, acts, out, g_out, g_is_logit_grad, dz, grads, tn=ops.gemm_tn, d0_out=None, dx_done=None):
         """g_out: gradient w.r.t. the decoder output ([B][>=N], fp32 or activation type).  For a
         sigmoid decoder it is w.r.t. the pre-sigmoid logits iff g_is_logit_grad.
         d0_out: where the gradient w.r.t. layer 0's output goes (a column slice of the buffer VAEGraph multiplies with the merged
-        first-layer weights of all decoders); layer 0's own dX GEMM is then skipped and dz is not touched."""
+        first-layer weights of all decoders); layer 0's own dX GEMM is then skipped and dz is not touched.
+        dx_done: the gradient w.r.t. the LAST layer's input, already computed (the fused class-head launch): its dX GEMM is skipped."""
         B, dev = g_out.shape[0], g_out.device
         adt = act_dtype(prec)
         d = g_out
@@ -503,7 +524,9 @@ class DecoderMLP:
         for j in reversed(range(len(self.pl))):
             pl, lin = self.pl[j], self.linears[j]
             tn(prec, d, acts[j], grads[lin.weight], grads[lin.bias], pl.N, pl.K, tag=f"{self.name}.L{j}.dW")
-            if j > 0:
+            if j > 0 and j == len(self.pl) - 1 and dx_done is not None:
+                d = dx_done
+            elif j > 0:
                 d_prev = d0_out if (j == 1 and d0_out is not None) else torch.empty(B, ceil_to(pl.K, 8), dtype=adt, device=dev)
                 ops.gemm_nt(prec, d, pl.wt, pl.K, pl.N, d_prev, epilogue=EPI_RELU_MASK, h=acts[j], tag=f"{self.name}.L{j}.dX")
                 d = d_prev
@@ -534,6 +557,9 @@ class VAEGraph:
         # Training-step fusion (mmvae.graphs): [target or None per decoder].  The next forward then computes those decoders'
         # reconstruction losses inside their last GEMM instead of returning the reconstruction (see DecoderMLP.forward).
         self.fused_recon = None
+        # Training-step fusion (mmvae.graphs): the caller hands the class logits straight to fused_loss and never reads them, so the
+        # next forward may leave the class decoder's last Linear to the loss (ClassTail).  Off, the forward returns real logits.
+        self.defer_class_head = False
 
     def _late_decoder_params(self):
         """Decoder tensors whose dW GEMM is small-output (latent / class widths: the decoders' first layers, DecoderC): they are
@@ -684,10 +710,19 @@ class VAEGraph:
         want = self.fused_recon
         if want is not None and any(t is not None and self.decoders[i].can_fuse_loss(prec) for i, t in enumerate(want)):
             fused = state.fused = FusedRecon(*(zeros.loss_ws if want_bwd else ops.loss_workspace(dev)), {}, {})
+        tail_i = self._class_tail_index(prec, H0, want, site) if (self.defer_class_head and fused is not None and want_bwd) else None
         for i in order:                                 # largest decoder first
             dec = self.decoders[i]
             tgt = want[i] if (fused is not None and want[i] is not None and dec.can_fuse_loss(prec)) else None
-            if tgt is not None:
+            if i == tail_i:
+                # the class head: its last Linear runs inside the loss (mmvae_class_tail), which also leaves the gradient w.r.t. this
+                # decoder's hidden activation in D0 -- allocated here, with the step state, because the loss writes it
+                D0 = torch.empty(B, stem.N, dtype=act_dtype(prec), device=dev)
+                off = sum(d.linears[0].out_features for d in self.decoders[:i])
+                state.class_tail = ClassTail(i, dec.pl[1], firsts[i], D0, D0[:, off:off + dec.linears[0].out_features], dec.name)
+                o = torch.empty(1, dtype=torch.float32, device=dev).expand(B, dec.out_dim)     # placeholder: no storage behind it
+                acts = [z, firsts[i]]
+            elif tgt is not None:
                 k = 1 if dec.final_sigmoid else 0                     # sums[0] = MSE, sums[1] = BCE (mmvae_vae_loss)
                 g, acts = dec.forward(prec, z, fused_loss=(tgt, fused.sums[k:k + 1]), first=firsts[i])
                 fused.g[i], fused.targets[i] = g, tgt
@@ -697,6 +732,18 @@ class VAEGraph:
             outs[i] = o
             state.dec[i] = (acts, o.detach())
         return outs, mu, logvar, state
+
+    def _class_tail_index(self, prec, H0, want, site):
+        """The decoder whose last Linear the fused class-head launch can take over, or None: the training step asked for it
+        (defer_class_head) and computes its reconstruction losses inside the decoder GEMMs (the caller checked both), labels are given, the stems are merged, and one decoder
+        without a reconstruction target is Linear -> ReLU -> Linear within the library's limits (asked, not duplicated here)."""
+        if self.dec_stem is None or site is None or H0 is None:
+            return None
+        for i, dec in enumerate(self.decoders):
+            if want[i] is None and isinstance(dec, DecoderMLP) and len(dec.pl) == 2 and not dec.final_sigmoid \
+                    and ops.class_tail_fits(prec, dec.pl[1].N, dec.pl[1].K, self.latent, H0.stride(0), H0.stride(0)):
+                return i
+        return None
 
     def backward(self, state, g_outs, g_logit_flags, g_mu, g_lv):
         with ops.pinned_stream():
@@ -739,18 +786,22 @@ class VAEGraph:
                 tiny.clear()
         stem = self.dec_stem if all(g is not None for g in g_outs) else None      # every decoder must fill its slice
         D0, off = None, 0
+        tail = state.class_tail
         if stem is not None:
-            D0 = torch.empty(B, stem.N, dtype=act_dtype(prec), device=dev)
-        for dec, (acts, out), g, is_logit in zip(self.decoders, state.dec, g_outs, g_logit_flags):
+            D0 = tail.d0 if tail is not None else torch.empty(B, stem.N, dtype=act_dtype(prec), device=dev)
+        for i, (dec, (acts, out), g, is_logit) in enumerate(zip(self.decoders, state.dec, g_outs, g_logit_flags)):
+            n0 = dec.linears[0].out_features if stem is not None else 0
             if g is None:
+                off += n0
                 continue
+            # the fused class-head launch has already left this decoder's hidden-activation gradient in its columns of D0
+            dx_done = tail.d0_slice if (tail is not None and tail.index == i and tail.done) else None
             if stem is not None:
-                n0 = dec.linears[0].out_features
-                dec.backward(prec, acts, out, g, is_logit, None, grads, tn, d0_out=D0[:, off:off + n0])
+                dec.backward(prec, acts, out, g, is_logit, None, grads, tn, d0_out=D0[:, off:off + n0], dx_done=dx_done)
                 off += n0
                 continue
             dz = torch.empty(B, Ld, dtype=torch.float32, device=dev)
-            dec.backward(prec, acts, out, g, is_logit, dz, grads, tn)
+            dec.backward(prec, acts, out, g, is_logit, dz, grads, tn, dx_done=dx_done)
             dzs.append(dz)
         if stem is not None:
             dz = torch.empty(B, Ld, dtype=torch.float32, device=dev)

@@ -229,6 +229,14 @@ def _fused_loss(terms, beta, gamma, class_weights=None, unit_grad=False, beta_ga
         ra = None
     if "b" in fused_idx:
         rb = None
+    # the class head whose last Linear the forward left to this loss (engine.ClassTail): `lg` is a placeholder of the logits' shape
+    tg = _tag_of(lg)
+    tail = tg.state.class_tail if (tg is not None and tg.kind == "out") else None
+    if tail is not None and (tail.index != tg.index or tail.done):
+        tail = None
+    lg_real = lg
+    if tail is not None:
+        lg = None                                      # nothing to read behind the placeholder: the logits are made below
 
     def prep(x):
         return None if x is None else (x if (x.dtype == torch.float32 and x.stride(-1) == 1) else x.float().contiguous())
@@ -244,7 +252,7 @@ def _fused_loss(terms, beta, gamma, class_weights=None, unit_grad=False, beta_ga
         sums = out4 = None                                 # out4: [total, recon, class, kld, labels out of range]
 
     # ---- fused hand-off: all differentiable inputs are outputs of ONE forward of our model --------------------
-    tags = [_tag_of(t) for t in (ra, rb, lg, mu, lv) if t is not None and t.requires_grad]
+    tags = [_tag_of(t) for t in (ra, rb, lg_real, mu, lv) if t is not None and t.requires_grad]
     state = tags[0].state if tags and all(t is not None and t.state is tags[0].state for t in tags) else None
     if need_grad and state is not None and not state.consumed and state.loss_grads is None:
         if sums is None:
@@ -264,25 +272,41 @@ def _fused_loss(terms, beta, gamma, class_weights=None, unit_grad=False, beta_ga
         if rb is not None and rb.requires_grad:
             gb = torch.empty(B, ceil_to(rb.shape[1], 8), dtype=adt, device=dev)
             g_outs[_tag_of(rb).index] = gb
-        if lg is not None and lg.requires_grad:
-            gc = torch.empty(B, lg.shape[1], dtype=torch.float32, device=dev)
-            g_outs[_tag_of(lg).index] = gc
+        if lg_real is not None and lg_real.requires_grad:
+            gc = torch.empty(B, lg_real.shape[1], dtype=torch.float32, device=dev)
+            g_outs[_tag_of(lg_real).index] = gc
         g_mu = torch.empty(B, mu.shape[1], dtype=torch.float32, device=dev) if mu is not None else None
         g_lv = torch.empty_like(g_mu) if mu is not None else None
-        ops.vae_loss(B, recon_a=ra_, a=a_, recon_b=rb_, b=b_, logits=lg_, site=site, class_weights=cw, mu=mu_, logvar=lv_,
-                     beta=beta, gamma=gamma, sums=sums, g_a=ga, g_b=gb, grad_b_wrt_logit=True, g_c=gc, g_mu=g_mu, g_lv=g_lv,
-                     beta_gamma_dev=beta_gamma_dev)
+        if tail is not None:
+            # ONE launch for the class head: its Linear, the class + KL terms and the Linear's dX (mmvae_class_tail).  It takes the
+            # captured step's form only (unit gradient: nothing rescales its dX afterwards; reconstruction terms inside the decoder
+            # GEMMs); otherwise, or where the library refuses (nothing enqueued), the Linear runs here and the step goes on as before
+            if unit_grad and ra_ is None and rb_ is None and mu_ is not None and gc is not None:
+                try:
+                    ops.class_tail(state.prec, B, tail.h0, tail.head, site, cw, mu_, lv_, beta, gamma, sums, gc, tail.d0_slice, g_mu, g_lv,
+                                   beta_gamma_dev=beta_gamma_dev)
+                    tail.done = True
+                except ops.L.MMVAEArgError:
+                    pass
+            if not tail.done:
+                lg_ = tail.logits(state.prec)
+        if tail is None or not tail.done:
+            ops.vae_loss(B, recon_a=ra_, a=a_, recon_b=rb_, b=b_, logits=lg_, site=site, class_weights=cw, mu=mu_, logvar=lv_,
+                         beta=beta, gamma=gamma, sums=sums, g_a=ga, g_b=gb, grad_b_wrt_logit=True, g_c=gc, g_mu=g_mu, g_lv=g_lv,
+                         beta_gamma_dev=beta_gamma_dev)
         ops.loss_finalize(sums, beta, gamma, out4, beta_gamma_dev)
         if g_mu is None:                       # KL term absent: nothing flows into mu/logvar from this loss
             g_mu = torch.zeros(B, state.logvar.shape[1], dtype=torch.float32, device=dev)
             g_lv = torch.zeros_like(g_mu)
         state.loss_grads = engine.LossGrads(g_outs=g_outs, g_mu=g_mu, g_lv=g_lv, unit_grad=bool(unit_grad))
-        pads = [t for t in (ra, rb, lg, mu, lv) if t is not None] + placeholders
+        pads = [t for t in (ra, rb, lg_real, mu, lv) if t is not None] + placeholders
         total = _LossHandleFn.apply(out4[0], state.loss_grads, *pads)
         return total, out4
 
     if fused is not None:
         raise RuntimeError("fused reconstruction loss: the loss terms are not all outputs of the one forward that computed it")
+    if tail is not None:
+        raise RuntimeError("fused class head: the loss terms are not all outputs of the one forward that left its logits to the loss")
 
     # ---- general path --------------------------------------------------------------------------------------------
     if sums is None:

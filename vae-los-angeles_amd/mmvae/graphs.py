@@ -96,6 +96,7 @@ class GraphedTrainStep:
         try:
             if self.kind == "multimodal":
                 g.fused_recon = [self.a, self.b, None]
+                g.defer_class_head = True               # nor at the class logits: the loss makes them (ops.class_tail)
                 ra, rb, rc, mu, lv = self.model(a=self.a, b=self.b, site=self.site)
                 terms = {"a": (ra, self.a), "b": (rb, self.b), "c": (rc, self.site), "kl": (mu, lv)}
             elif self.kind == "dna2rna":
@@ -108,6 +109,7 @@ class GraphedTrainStep:
                 terms = {"b": (rec, self.b), "kl": (mu, lv)}
         finally:
             g.fused_recon = None
+            g.defer_class_head = False
         return F_.fused_loss(terms, self.beta, self.gamma, self.class_weights, unit_grad=True, beta_gamma_dev=self.hyper)
 
     def run_eager(self):

@@ -572,6 +572,43 @@ def vae_loss(B, *, recon_a=None, a=None, recon_b=None, b=None, logits=None, site
         L.check(L.load().mmvae_vae_loss(C.byref(x), _stream()), "mmvae_vae_loss")
 
 
+def class_tail_fits(prec, S, hidden, Ld, ldh0, ldd0):
+    """Would mmvae_class_tail take a class head of these shapes (and is its tuning key on)?  The library's own limits: a forward
+    asks before it leaves the class decoder's last Linear to that launch."""
+    return L.load().mmvae_class_tail_fits(prec, S, hidden, Ld, ldh0, ldd0) == 0
+
+
+def class_tail_args(prec, B, h0, head, site, class_weights, mu, logvar, beta, gamma, sums, g_c, d0, g_mu, g_lv, beta_gamma_dev=None):
+    """-> (ClassTailArgs of mmvae_class_tail, its algorithmic HBM bytes).  The struct holds addresses only."""
+    a = L.ClassTailArgs()
+    a.prec, a.B, a.S, a.L, a.hidden = prec, B, head.N, mu.shape[1], head.K
+    a.h0, a.ldh0 = _mat(h0, "h0").data_ptr(), _ld(h0)
+    a.w, a.ldw, a.wt, a.ldwt, a.bias = head.w.data_ptr(), head.w.stride(0), head.wt.data_ptr(), head.wt.stride(0), _p(head.bias)
+    a.site, a.class_weights = site.data_ptr(), _p(class_weights)
+    a.mu, a.logvar = mu.data_ptr(), logvar.data_ptr()
+    a.beta, a.gamma, a.beta_gamma_dev, a.sums = beta, gamma, _p(beta_gamma_dev), sums.data_ptr()
+    a.g_c, a.ld_gc = _mat(g_c, "g_c").data_ptr(), _ld(g_c)
+    a.d0, a.ldd0 = _mat(d0, "d0").data_ptr(), _ld(d0)
+    a.g_mu, a.g_lv = g_mu.data_ptr(), g_lv.data_ptr()
+    # h0 slice read, d0 slice written (bf16), labels, fp32 class gradient written, mu / logvar read, their gradients written
+    nbytes = B * (2 * head.K * h0.element_size() + 8 + 4 * head.N + 16 * mu.shape[1])
+    return a, nbytes
+
+
+def class_tail(prec, B, h0, head, site, class_weights, mu, logvar, beta, gamma, sums, g_c, d0, g_mu, g_lv, beta_gamma_dev=None):
+    """mmvae_class_tail: the class decoder's last Linear (`head`, a PreparedLinear) on its hidden activation h0 (B, 64), the class +
+    KL terms of vae_loss with their gradients (g_c fp32 (B, S), g_mu / g_lv) and the Linear's dX behind the ReLU mask (d0, the
+    (B, 64) column slice of the merged stem gradient) in ONE launch.  mu, logvar, g_mu and g_lv are contiguous (B, L).  Raises
+    MMVAEArgError, with nothing enqueued, for what the kernel does not take: the caller then issues the launches it replaces."""
+    for t in (mu, logvar, g_mu, g_lv):
+        if tuple(t.shape) != (B, mu.shape[1]) or not t.is_contiguous() or t.dtype != torch.float32:
+            raise ValueError(f"class_tail: mu / logvar / g_mu / g_lv must be contiguous fp32 ({B}, L), got {tuple(t.shape)} / {t.stride()}")
+    assert sums.dtype == torch.float64 and sums.numel() >= 5 and site.dtype == torch.int64 and site.is_contiguous()
+    a, nbytes = class_tail_args(prec, B, h0, head, site, class_weights, mu, logvar, beta, gamma, sums, g_c, d0, g_mu, g_lv, beta_gamma_dev)
+    with stream_span("class_tail", nbytes):
+        L.check(L.load().mmvae_class_tail(C.byref(a), _stream()), "mmvae_class_tail")
+
+
 def loss_finalize(sums, beta, gamma, out5, beta_gamma_dev=None):
     assert out5.numel() >= 5
     L.check(L.load().mmvae_loss_finalize(sums.data_ptr(), beta, gamma, _p(beta_gamma_dev), out5.data_ptr(), _stream()), "mmvae_loss_finalize")
