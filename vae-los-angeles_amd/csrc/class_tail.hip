@@ -20,6 +20,7 @@
 #include "common.h"
 #include "mmvae_hip.h"
 #include "loss_terms.h"
+#include "wave_slab.h"
 
 namespace mm {
 
@@ -27,8 +28,7 @@ constexpr int CT_WAVES = 8, CT_THREADS = 64 * CT_WAVES;
 constexpr int CT_SP = 32;                         // class columns in LDS: two MFMA tiles
 constexpr int CT_HID = 64;                        // hidden width
 constexpr int CT_KU = 6;                          // KL elements per lane and slab: 16 rows x L <= 24
-// LDS rows are padded by one 16-byte chunk: the 16 lanes of a fragment read then hit 16 different bank groups
-constexpr int CT_WROW = 2 * CT_HID + 16;          // W row (64 bf16)
+constexpr int CT_WROW = 2 * CT_HID + 16;          // W row (64 bf16) + the pad chunk of every LDS row (wave_slab.h)
 constexpr int CT_TROW = 2 * CT_SP + 16;           // W^T row and gradient-image row (32 bf16)
 constexpr int CT_XLD = CT_SP + 4;                 // floats per row of the logit / exp images
 constexpr int CT_OFF_WT = CT_SP * CT_WROW;
@@ -49,9 +49,6 @@ struct CtArgs {
     float beta, gamma; const float* bg; double* sums;
     float* gc; long ldgc; bf16* d0; long ldd; float* gmu; float* glv;
 };
-
-// the wave's LDS writes are visible to its other lanes (LDS operations of a wave execute in order)
-__device__ __forceinline__ void ct_wave_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_wave_barrier(); }
 
 __global__ __launch_bounds__(CT_THREADS) void class_tail_kernel(const CtArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -90,17 +87,8 @@ __global__ __launch_bounds__(CT_THREADS) void class_tail_kernel(const CtArgs a) 
     if (slab < a.nslabs) fetch(slab);          // the first slab's loads fly under the set-up: they depend on nothing in LDS
 
     // ---------------------------------------------------------------------------------- once per workgroup
-    for (int c = tid; c < CT_SP * 8; c += CT_THREADS) {
-        const int r = c >> 3, ch = c & 7;
-        *(uint4*)(smem + r * CT_WROW + ch * 16) = *(const uint4*)(a.w + (long)r * a.ldw + ch * 8);
-    }
-    // LDS row x = 16 q + i of W^T holds its row 32 (q >> 1) + 8 (i >> 2) + 4 (q & 1) + (i & 3): tiles (2 h, 2 h + 1) interleaved, so
-    // a lane's 8 accumulators of a pair are 8 consecutive hidden columns (EpiCols<true>, gemm_nt_epi.h)
-    for (int c = tid; c < CT_HID * 4; c += CT_THREADS) {
-        const int x = c >> 2, ch = c & 3, q = x >> 4, i = x & 15;
-        const int wr = 32 * (q >> 1) + 8 * (i >> 2) + 4 * (q & 1) + (i & 3);
-        *(uint4*)(smem + CT_OFF_WT + x * CT_TROW + ch * 16) = *(const uint4*)(a.wt + (long)wr * a.ldwt + ch * 8);
-    }
+    stage_rows<CT_THREADS>(smem, CT_WROW, a.w, a.ldw, CT_SP, 8, tid, EpiCols<false>::wrow);
+    stage_rows<CT_THREADS>(smem + CT_OFF_WT, CT_TROW, a.wt, a.ldwt, CT_HID, 4, tid, EpiCols<true>::wrow);      // a lane's 8 dX accumulators of a tile pair: 8 consecutive columns
     if (tid < CT_SP) {
         sbias[tid] = (a.bias && tid < S) ? a.bias[tid] : 0.f;
         scw[tid] = (a.cw && tid < S) ? a.cw[tid] : 1.f;
@@ -151,7 +139,7 @@ __global__ __launch_bounds__(CT_THREADS) void class_tail_kernel(const CtArgs a) 
             *(f32x4*)(sx + li * CT_XLD + 16 * n + 4 * lg) = x[n];
             *(f32x4*)(sexp + li * CT_XLD + 16 * n + 4 * lg) = e[n];
         }
-        ct_wave_sync();
+        wave_lds_sync();
         float se = 0.f;                                                // every lane of the row: the same sum in ascending order
 #pragma unroll
         for (int c = 0; c < CT_SP / 4; ++c) {
@@ -174,14 +162,14 @@ __global__ __launch_bounds__(CT_THREADS) void class_tail_kernel(const CtArgs a) 
                 const int c = 16 * n + 4 * lg + j;
                 g[n][j] = c < S ? ce_grad(gw, e[n][j], se, c == lb.y) : 0.f;
             }
-        ct_wave_sync();                                                // the logit image is read: it takes the fp32 gradient
+        wave_lds_sync();                                                // the logit image is read: it takes the fp32 gradient
 #pragma unroll
         for (int n = 0; n < 2; ++n) {
             *(f32x4*)(sx + li * CT_XLD + 16 * n + 4 * lg) = g[n];
             const bf16x4 gb = {(bf16)g[n][0], (bf16)g[n][1], (bf16)g[n][2], (bf16)g[n][3]};      // as SrcPlain<bf16, float> rounds it
             *(bf16x4*)(sg + li * CT_TROW + (16 * n + 4 * lg) * 2) = gb;
         }
-        ct_wave_sync();
+        wave_lds_sync();
         // the fp32 class gradient (the grouped dW launch reads it): the slab's rows as consecutive 16-byte pieces
 #pragma unroll
         for (int it = 0; it < 2; ++it) {
@@ -208,23 +196,13 @@ __global__ __launch_bounds__(CT_THREADS) void class_tail_kernel(const CtArgs a) 
                 const int e0 = 2 * qd;                                 // hidden columns 32 h + 8 lg + e0, + 1: the lane's own h0 values
                 const float o0 = (float)hv[h][e0] > 0.f ? v[2 * (qd & 1)] : 0.f;
                 const float o1 = (float)hv[h][e0 + 1] > 0.f ? v[2 * (qd & 1) + 1] : 0.f;
-                typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
                 const bf16x2 t = {(bf16)o0, (bf16)o1};
                 pk[h][qd] = __builtin_bit_cast(uint32_t, t);
             }
         }
-        // lanes li < 8 give away their second half and get row li + 8's first half; lanes li >= 8 the other way round
-        const bool lowl = li < 8;
-        uint32_t st0[4], st1[4];
-#pragma unroll
-        for (int qd = 0; qd < 4; ++qd) {
-            const uint32_t send = lowl ? pk[1][qd] : pk[0][qd];
-            const uint32_t got = (uint32_t)__builtin_amdgcn_mov_dpp((int)send, 0x128, 0xf, 0xf, true);      // row_ror:8 == lane li ^ 8
-            st0[qd] = lowl ? pk[0][qd] : got;
-            st1[qd] = lowl ? got : pk[1][qd];
-        }
+        SWAP_HALVES(pk, li < 8, st0, st1);
         const int rbase = slab * 16 + (li & 7);
-        bf16* const crow = a.d0 + (long)rbase * a.ldd + 32 * (li >> 3) + 8 * lg;
+        bf16* const crow = line_col(a.d0 + (long)rbase * a.ldd, li, lg);
         if (rbase < a.B) *(uint4*)crow = uint4{st0[0], st0[1], st0[2], st0[3]};
         if (rbase + 8 < a.B) *(uint4*)(crow + 8 * a.ldd) = uint4{st1[0], st1[1], st1[2], st1[3]};
 
@@ -239,7 +217,7 @@ __global__ __launch_bounds__(CT_THREADS) void class_tail_kernel(const CtArgs a) 
                 a.gmu[idx] = gm; a.glv[idx] = gl;
             }
         }
-        ct_wave_sync();                               // the images are free for the next slab
+        wave_lds_sync();                               // the images are free for the next slab
     }
 
     // ---------------------------------------------------------------------------------- the three sums: one f64 atomic each
@@ -283,7 +261,5 @@ extern "C" int mmvae_class_tail(const mmvae_class_tail_args* a, void* stream) {
     k.bias = a->bias; k.site = (const long long*)a->site; k.cw = a->class_weights; k.mu = a->mu; k.lv = a->logvar;
     k.beta = a->beta; k.gamma = a->gamma; k.bg = a->beta_gamma_dev; k.sums = a->sums;
     k.gc = a->g_c; k.ldgc = a->ld_gc; k.d0 = (bf16*)a->d0; k.ldd = a->ldd0; k.gmu = a->g_mu; k.glv = a->g_lv;
-    int grid = (k.nslabs + CT_WAVES - 1) / CT_WAVES;
-    if (grid > 256) grid = 256;                      // one workgroup per CU
-    return launch_lds<class_tail_kernel>(dim3(grid), dim3(CT_THREADS), CT_LDS, (hipStream_t)stream, k);
+    return launch_lds<class_tail_kernel>(dim3(persistent_grid(k.nslabs, CT_WAVES)), dim3(CT_THREADS), CT_LDS, (hipStream_t)stream, k);
 }

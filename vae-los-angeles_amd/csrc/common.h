@@ -10,6 +10,7 @@ namespace mm {
 typedef __bf16 bf16;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
+typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 typedef __attribute__((ext_vector_type(4))) short s16x4;
@@ -18,6 +19,7 @@ constexpr int WAVE = 64;
 constexpr int TILE = 128;          // output tile edge of both GEMM kernels
 constexpr int NTHREADS = 256;      // 4 waves, 2x2, 64x64 each
 constexpr int ROW_BYTES = 128;     // bytes of one LDS row in the NT kernel (= one K step)
+constexpr int NUM_CU = 256;        // compute units of the MI355X, the only target: persistent kernels launch one workgroup per CU
 
 // ---- MFMA wrappers: one "fragment step" consumes 16 bytes per lane of A and of B ------------
 template <typename CT> struct Mma;
@@ -70,7 +72,7 @@ template <> struct VLoad<float, 1> { static __device__ __forceinline__ void ld(c
 template <> struct VLoad<float, 2> { static __device__ __forceinline__ void ld(const float* p, float* o) { f32x2 v = *(const f32x2*)p; o[0] = v[0]; o[1] = v[1]; } };
 template <> struct VLoad<float, 4> { static __device__ __forceinline__ void ld(const float* p, float* o) { f32x4 v = *(const f32x4*)p; o[0] = v[0]; o[1] = v[1]; o[2] = v[2]; o[3] = v[3]; } };
 template <> struct VLoad<bf16, 1> { static __device__ __forceinline__ void ld(const bf16* p, float* o) { o[0] = (float)p[0]; } };
-template <> struct VLoad<bf16, 2> { static __device__ __forceinline__ void ld(const bf16* p, float* o) { typedef __attribute__((ext_vector_type(2))) __bf16 v2; v2 v = *(const v2*)p; o[0] = (float)v[0]; o[1] = (float)v[1]; } };
+template <> struct VLoad<bf16, 2> { static __device__ __forceinline__ void ld(const bf16* p, float* o) { bf16x2 v = *(const bf16x2*)p; o[0] = (float)v[0]; o[1] = (float)v[1]; } };
 template <> struct VLoad<bf16, 4> { static __device__ __forceinline__ void ld(const bf16* p, float* o) { bf16x4 v = *(const bf16x4*)p; for (int i = 0; i < 4; ++i) o[i] = (float)v[i]; } };
 template <> struct VLoad<bf16, 8> { static __device__ __forceinline__ void ld(const bf16* p, float* o) { bf16x8 v = *(const bf16x8*)p; for (int i = 0; i < 8; ++i) o[i] = (float)v[i]; } };
 
@@ -202,7 +204,7 @@ int stamp_read_tnw(uint64_t*, int, int);
 
 // Dispatch knobs, set through mmvae_set_tuning (tests flip them inside one process to compare the kernel forms on the same data)
 struct Tuning {
-    int nt_wide_min_m = 256 * 128;   // key 0: 128x256 NT tiles only when there are >= 256 row tiles
+    int nt_wide_min_m = NUM_CU * 128;   // key 0: 128x256 NT tiles only when there are >= NUM_CU row tiles
     int nt2_on = 1;                  // key 2: the LDS-DMA NT generation (gemm_nt2.h) against the register-staged one
     long split_bytes = 1L << 32;     // key 3 (log2, 0 = default): operands of at least this many bytes are processed in row blocks
     long block_bytes = 1L << 31;     //   ... of this size; key 3 sets half the threshold

@@ -389,7 +389,7 @@ template <typename Epi, int WN>
 static int launch_nt2(const void* A, long lda, const void* W, long ldw, int M, int N, int K, const Epi& epi, hipStream_t st) {
     const int gx = (M + TILE - 1) / TILE, gy = (N + 64 * WN - 1) / (64 * WN);
     const int ntiles = ((gx + 7) / 8) * 8 * gy;
-    int grid = 256 * (WN == 2 ? 2 : 1);
+    int grid = NUM_CU * (WN == 2 ? 2 : 1);
     if (grid > ntiles) grid = ntiles;
     return launch_lds<gemm_nt2_kernel<Epi, WN>>(dim3(grid), dim3(128 * WN), Nt2Lds<WN>::TOTAL, st,
                                                 (const bf16*)A, lda, (const bf16*)W, ldw, M, N, K, gx, gy, epi);

@@ -5,7 +5,7 @@
 // accumulator tile comes out transposed: lane (li = lane & 15, lg = lane >> 4) holds, for tile (m, n),
 //     row  = 64*wr + 16*m + li                      (one activation row per lane)
 //     cols = 64*wc + wrow(16*n + 4*lg + j)          (j = 0..3: four consecutive columns)
-// where wrow() is the order in which the W rows of the wave's 64 columns were put into the MFMA tiles (EpiCols below: the
+// where wrow() is the order in which the W rows of the wave's 64 columns were put into the MFMA tiles (EpiCols, wave_slab.h: the
 // kernel applies it to the W row it FETCHES for each LDS row, which costs nothing).  For 4-byte outputs wrow is the
 // identity: a lane's 4 columns are 16 bytes and the 4 lane groups complete 64 contiguous bytes of the row.  For 2-byte
 // outputs tiles (2g, 2g+1) are interleaved so that a lane owns 8 consecutive columns (16 bytes) and the 4 lane groups
@@ -15,6 +15,7 @@
 // tile as an 8-step main loop (tools/stamp.py nt: 12-14 k cycles per wave, 64 ds_write_b16 per lane).
 #pragma once
 #include "common.h"
+#include "wave_slab.h"
 
 namespace mm {
 
@@ -206,22 +207,6 @@ struct EpiReluMaskStream {
     static constexpr int NCOL = 0;
     bool accumulate_requested() const { return false; }
     __device__ __forceinline__ void fill(float*, int, int, int, int) const {}
-};
-
-// Column order of a wave's 64 output columns inside its 4 MFMA n-tiles.
-template <bool PAIR> struct EpiCols {
-    static constexpr int G = PAIR ? 8 : 4;            // consecutive columns a lane owns per group
-    static constexpr int NG = 16 / G;                 // groups per lane (x 4 rows m)
-    // W row (relative to the wave's 64) that goes to LDS row x = 16*n + i of the wave's W block
-    static __device__ __forceinline__ int wrow(int x) {
-        if constexpr (!PAIR) return x;
-        const int n = x >> 4, i = x & 15;
-        return 32 * (n >> 1) + 8 * (i >> 2) + 4 * (n & 1) + (i & 3);
-    }
-    // first column (relative to the wave's 64) of group g for lane group lg; element e of the group is accumulator
-    // (n, j) = (PAIR ? 2g + (e >> 2) : g, e & 3)
-    static __device__ __forceinline__ int base(int g, int lg) { return PAIR ? 32 * g + 8 * lg : 16 * g + 4 * lg; }
-    static constexpr __device__ __forceinline__ int tile(int g, int e) { return PAIR ? 2 * g + (e >> 2) : g; }
 };
 
 // Epilogue operands (ReLU input / pre-BN output, keep mask) in the accumulator's own layout, fetched into registers a
@@ -437,7 +422,7 @@ __device__ __forceinline__ void nt_epilogue_body(const float* ecol, f32x4 (&acc)
                 }
             }
             if (full_lines) {
-                // lanes li < 8 give away their second half and get row li+8's first half; lanes li >= 8 the other way round
+                // SWAP_HALVES (wave_slab.h) in the bit-mask coding of the load side above: in the select coding 88 kernels of gemm_nt.hip come out different
                 uint32_t st0[4], st1[4];
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {

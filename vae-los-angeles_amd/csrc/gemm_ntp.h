@@ -278,11 +278,11 @@ void gemm_ntp_kernel(const AT* __restrict__ A, long lda, const bf16* __restrict_
                 // Every tile is interior and the 2-byte output rows are whole 128-byte lines (ntp_dispatch only takes such problems -- all
                 // of the forward first layers at B = 65 536; the tile kernels keep the edge cases): no bounds selects, no branches; two
                 // accumulators -> one v_cvt_pk_bf16_f32 = the packed store word, expanded again (2 VALU) for the statistics of the ROUNDED
-                // value; packed f32 adds / fmas; the half swap between lanes li and li ^ 8 is a DPP row_ror:8 move, not a ds_bpermute.
+                // value; packed f32 adds / fmas; the half swap between lanes li and li ^ 8 is SWAP_HALVES (wave_slab.h).
                 auto fast = [&](auto ACTC) __attribute__((always_inline)) {
                     constexpr int ACT = decltype(ACTC)::value;
                     const bool lowl = li < 8;
-                    OT* crow = epi.C + (long)(row0 + wr * 64 + (li & 7)) * epi.ldc + (col0 + wc * 16 * NT + 32 * (li >> 3) + 8 * lg);
+                    OT* crow = epi.C + (long)(row0 + wr * 64 + (li & 7)) * epi.ldc + (col0 + wc * 16 * NT + line_col(li, lg));
                     const long ld16 = 16 * epi.ldc, ld8 = 8 * epi.ldc;
 #pragma unroll
                     for (int hh = 0; hh < NH; ++hh) {
@@ -311,7 +311,6 @@ void gemm_ntp_kernel(const AT* __restrict__ A, long lda, const bf16* __restrict_
                                     f32x2 x = f32x2{a4[e & 3], a4[(e & 3) + 1]} + f32x2{bq[h][e], bq[h][e + 1]};
                                     if (ACT == 1) { x[0] = fmaxf(x[0], 0.f); x[1] = fmaxf(x[1], 0.f); }
                                     else if (ACT == 2) { x[0] = __builtin_amdgcn_rcpf(1.f + __expf(-x[0])); x[1] = __builtin_amdgcn_rcpf(1.f + __expf(-x[1])); }
-                                    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
                                     const bf16x2 t = {(bf16)x[0], (bf16)x[1]};
                                     const uint32_t w = __builtin_bit_cast(uint32_t, t);
                                     if (Epi::STATS) {
@@ -321,14 +320,7 @@ void gemm_ntp_kernel(const AT* __restrict__ A, long lda, const bf16* __restrict_
                                     }
                                     pk[h][qd] = w;
                                 }
-                            uint32_t st0[4], st1[4];
-#pragma unroll
-                            for (int qd = 0; qd < 4; ++qd) {
-                                const uint32_t send = lowl ? pk[1][qd] : pk[0][qd];
-                                const uint32_t got = (uint32_t)__builtin_amdgcn_mov_dpp((int)send, 0x128, 0xf, 0xf, true);      // row_ror:8 == lane li ^ 8
-                                st0[qd] = lowl ? pk[0][qd] : got;
-                                st1[qd] = lowl ? got : pk[1][qd];
-                            }
+                            SWAP_HALVES(pk, lowl, st0, st1);
                             OT* cp = crow + m * ld16 + hh * 64;
                             *(uint4*)cp = uint4{st0[0], st0[1], st0[2], st0[3]};
                             *(uint4*)(cp + ld8) = uint4{st1[0], st1[1], st1[2], st1[3]};
@@ -630,9 +622,7 @@ template <typename Cfg, typename AT, typename Epi, typename Pro = NtpProNone>
 static int launch_ntp(const void* A, long lda, const void* W, long ldw, int M, int N, int K, const Epi& epi, hipStream_t st, const Pro& pro = Pro{}) {
     const int gx = (M + Cfg::BM - 1) / Cfg::BM, gy = (N + Cfg::BN - 1) / Cfg::BN;
     const int ntiles = ((gx + 7) / 8) * 8 * gy;
-    int grid = 256;                                                  // one 8-wave workgroup per CU
-    if (grid > ntiles) grid = ntiles;
-    return launch_lds<gemm_ntp_kernel<Cfg, AT, Epi, Pro>>(dim3(grid), dim3(64 * Cfg::NWAVES), Cfg::TOTAL, st,
+    return launch_lds<gemm_ntp_kernel<Cfg, AT, Epi, Pro>>(dim3(persistent_grid(ntiles, 1)), dim3(64 * Cfg::NWAVES), Cfg::TOTAL, st,
                                                           (const AT*)A, lda, (const bf16*)W, ldw, M, N, K, gx, gy, epi, pro);
 }
 

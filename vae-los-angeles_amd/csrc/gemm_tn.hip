@@ -534,7 +534,7 @@ static int launch_tn(const mmvae_gemm_tn_args* a, const PSrc& ps, const QSrc& qs
             // multiples of 8 splits (XCD balance) on >= 7/8 of the CUs -- 8 or 7 tiles (512x256, 256x512, 782x128: 36-38 against 40-41 us
             // with the reduce).  The 20 tiles of 572x512 would make 160 workgroups, or 240 with 12 splits of which the last four are
             // shared by two XCDs each (tried: 69 against 64-65 us alone, the same inside the step).
-            const TnPlan p2 = tn_plan(a->M, a->N, a->K, G::MT, a->nsplit, 256);
+            const TnPlan p2 = tn_plan(a->M, a->N, a->K, G::MT, a->nsplit, NUM_CU);
             if (a->nsplit <= 0 && p2.nsplit % 8 == 0 && p2.nsplit * p2.ntiles >= 224) {
                 constexpr int LDS2 = 8 * G::MT * G::ROWB + 4096;          // four 64-row P + Q buffers
                 return tn_go<gemm_tn_kernel<CT, PSrc, QSrc, true, 2>>(a, ps, qs, p2, NTHREADS * 2, LDS2, st);

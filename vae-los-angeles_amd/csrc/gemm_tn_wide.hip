@@ -547,7 +547,7 @@ int launch_tn_wide(const mmvae_gemm_tn_args* a, hipStream_t st, int* nsplit_out)
     w.ntk = (a->K + KT - 1) / KT;
     w.ntiles = w.ntk * ((a->N + NT - 1) / NT);
     if (w.ntiles > (pmode ? 32 : 4096)) return NA;         // corrected P: every K tile redoes the correction -- the 128 x 128 kernel's case
-    const SplitPlan sp = plan_splits(a->M, 32, 0, w.ntiles, 256);      // 256: one workgroup per CU
+    const SplitPlan sp = plan_splits(a->M, 32, 0, w.ntiles, NUM_CU);      // one workgroup per CU
     const int nsplit = sp.nsplit, rps = sp.rps;
     if ((long)nsplit * a->N * a->K > a->slab_elems) return NA;
     if (pmode && nsplit < 2) return NA;

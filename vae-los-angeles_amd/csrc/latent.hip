@@ -21,6 +21,7 @@
 #include "mmvae_hip.h"
 #include "gemm_src.h"
 #include "fuse_math.h"
+#include "wave_slab.h"
 
 namespace mm {
 
@@ -30,8 +31,7 @@ constexpr int LAT_HN = 48;                        // head columns in LDS: three 
 constexpr int LAT_FU = LAT_HN / 2 * 16 / 64;      // fusion elements per lane and slab: 16 rows x L <= 24
 constexpr int LAT_NS = 448;                       // stem columns
 constexpr int LAT_MAXTAB = 1024;                  // floats of the EncoderC table
-// LDS rows are padded by one 16-byte chunk: the 16 lanes of a fragment read then hit 16 different bank groups
-constexpr int LAT_WROW = LAT_NK * 64 + 16;        // heads weight row (K <= 256 bf16)
+constexpr int LAT_WROW = LAT_NK * 64 + 16;        // heads weight row (K <= 256 bf16) + the pad chunk of every LDS row (wave_slab.h)
 constexpr int LAT_SROW = 64 + 16;                 // stem weight row and z row (32 bf16)
 constexpr int LAT_SUMLD = 52;                     // floats per row of the heads image
 constexpr int LAT_OFF_WS = 2 * LAT_HN * LAT_WROW;
@@ -53,9 +53,6 @@ struct LatArgs {
     bf16* h0; long ldh0;
     int nslabs;
 };
-
-// the wave's LDS writes are visible to its other lanes (LDS operations of a wave execute in order)
-__device__ __forceinline__ void lat_wave_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_wave_barrier(); }
 
 __global__ __launch_bounds__(LAT_THREADS) void latent_fwd_kernel(const LatArgs a) {
     typedef SrcBnReluDrop<bf16>::Raw Raw;
@@ -114,20 +111,11 @@ __global__ __launch_bounds__(LAT_THREADS) void latent_fwd_kernel(const LatArgs a
         // [512] scale | [512] shift: 1024 floats per encoder (LAT_OFF_AUX), and K <= 256 <= NTHREADS is one column per thread
         static_assert(NTHREADS <= LAT_THREADS && 32 * LAT_NK <= 512, "SrcBnReluDrop's table: 512 columns, filled by NTHREADS threads");
         if (tid < NTHREADS) a.e[e].src.init(aux + e * 1024, tid, 0);
-        const int cpr = a.e[e].nk * 4;                                         // 16-byte chunks per weight row
-        for (int c = tid; c < LAT_HN * cpr; c += LAT_THREADS) {
-            const int r = c / cpr, ch = c - r * cpr;
-            *(uint4*)(smem + (e * LAT_HN + r) * LAT_WROW + ch * 16) = *(const uint4*)(a.e[e].w + (long)r * a.e[e].ldw + ch * 8);
-        }
+        stage_rows<LAT_THREADS>(smem + e * LAT_HN * LAT_WROW, LAT_WROW, a.e[e].w, a.e[e].ldw, LAT_HN, a.e[e].nk * 4, tid, EpiCols<false>::wrow);
         if (tid < LAT_HN) sbias[e * LAT_HN + tid] = (a.e[e].bias && tid < L2) ? a.e[e].bias[tid] : 0.f;
     }
-    // LDS row x = 64 p + 16 q + i of the stem weights holds W row 64 p + 32 (q >> 1) + 8 (i >> 2) + 4 (q & 1) + (i & 3): tiles
-    // (2 h, 2 h + 1) interleaved, so a lane's 8 accumulators of a pair are 8 consecutive columns (EpiCols<true>, gemm_nt_epi.h)
-    for (int c = tid; c < a.ns * 4; c += LAT_THREADS) {
-        const int x = c >> 2, ch = c & 3, q = (x >> 4) & 3, i = x & 15;
-        const int wr = (x & ~63) + 32 * (q >> 1) + 8 * (i >> 2) + 4 * (q & 1) + (i & 3);
-        *(uint4*)(smem + LAT_OFF_WS + x * LAT_SROW + ch * 16) = *(const uint4*)(a.ws + (long)wr * a.ldws + ch * 8);
-    }
+    // every 64-column block of the stem weights in EpiCols<true>'s row order: a lane's 8 accumulators of a tile pair are 8 consecutive columns
+    stage_rows<LAT_THREADS>(smem + LAT_OFF_WS, LAT_SROW, a.ws, a.ldws, a.ns, 4, tid, [](int x) { return (x & ~63) + EpiCols<true>::wrow(x & 63); });
     for (int c = tid; c < a.ns; c += LAT_THREADS) sbias[2 * LAT_HN + c] = a.bs ? a.bs[c] : 0.f;
     if (a.table) for (int i = tid; i < a.S * L2; i += LAT_THREADS) stab[i] = a.table[i];
     for (int i = lane; i < 16 * LAT_SROW / 16; i += 64) ((uint4*)sz)[i] = uint4{0u, 0u, 0u, 0u};      // z pads (k >= L) stay zero
@@ -169,7 +157,7 @@ __global__ __launch_bounds__(LAT_THREADS) void latent_fwd_kernel(const LatArgs a
 #pragma unroll
         for (int i = 0; i < LAT_FU; ++i) { ep[i] = eps_r[i]; st[i] = site_r[i]; }
         if (slab + nw < a.nslabs) fetch(slab + nw);
-        lat_wave_sync();
+        wave_lds_sync();
 
         // ------------------------------------------------------------------------------ mean fusion + reparameterisation
 #pragma unroll
@@ -190,7 +178,7 @@ __global__ __launch_bounds__(LAT_THREADS) void latent_fwd_kernel(const LatArgs a
             if (idx < total) { a.mu[idx] = mu; a.logvar[idx] = lv; }
             ((bf16*)sz)[r * (LAT_SROW / 2) + l] = (bf16)zf;
         }
-        lat_wave_sync();
+        wave_lds_sync();
         if (lane < 16 * zcpr && slab * 16 + zr < a.B)
             *(uint4*)(a.z + (long)(slab * 16 + zr) * a.ldz + zc * 8) = *(const uint4*)(sz + zr * LAT_SROW + zc * 16);
 
@@ -198,7 +186,7 @@ __global__ __launch_bounds__(LAT_THREADS) void latent_fwd_kernel(const LatArgs a
         const bf16x8 zf8 = *(const bf16x8*)(sz + li * LAT_SROW + lg * 16);
         const bool lowl = li < 8;
         const int rbase = slab * 16 + (li & 7);
-        bf16* const crow = a.h0 + (long)rbase * a.ldh0 + 32 * (li >> 3) + 8 * lg;
+        bf16* const crow = line_col(a.h0 + (long)rbase * a.ldh0, li, lg);
         const bool ok0 = rbase < a.B, ok1 = rbase + 8 < a.B;
         for (int p = 0; p < (a.ns >> 6); ++p) {
             f32x4 acc[4];
@@ -217,24 +205,15 @@ __global__ __launch_bounds__(LAT_THREADS) void latent_fwd_kernel(const LatArgs a
 #pragma unroll
                 for (int qd = 0; qd < 4; ++qd) {
                     const f32x4 x = qd < 2 ? x0 : x1;
-                    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
                     const bf16x2 t = {(bf16)fmaxf(x[2 * (qd & 1)], 0.f), (bf16)fmaxf(x[2 * (qd & 1) + 1], 0.f)};
                     pk[h][qd] = __builtin_bit_cast(uint32_t, t);
                 }
             }
-            // lanes li < 8 give away their second half and get row li + 8's first half; lanes li >= 8 the other way round
-            uint32_t st0[4], st1[4];
-#pragma unroll
-            for (int qd = 0; qd < 4; ++qd) {
-                const uint32_t send = lowl ? pk[1][qd] : pk[0][qd];
-                const uint32_t got = (uint32_t)__builtin_amdgcn_mov_dpp((int)send, 0x128, 0xf, 0xf, true);      // row_ror:8 == lane li ^ 8
-                st0[qd] = lowl ? pk[0][qd] : got;
-                st1[qd] = lowl ? got : pk[1][qd];
-            }
+            SWAP_HALVES(pk, lowl, st0, st1);
             if (ok0) *(uint4*)(crow + 64 * p) = uint4{st0[0], st0[1], st0[2], st0[3]};
             if (ok1) *(uint4*)(crow + 8 * a.ldh0 + 64 * p) = uint4{st1[0], st1[1], st1[2], st1[3]};
         }
-        lat_wave_sync();                              // the images are free for the next slab
+        wave_lds_sync();                              // the images are free for the next slab
     }
 }
 
@@ -279,7 +258,5 @@ extern "C" int mmvae_latent_fwd(const mmvae_latent_fwd_args* a, void* stream) {
     k.ws = (const bf16*)a->w_stem; k.ldws = a->ldw_stem; k.bs = a->bias_stem; k.ns = a->N_stem;
     k.h0 = (bf16*)a->h0; k.ldh0 = a->ldh0;
     k.nslabs = (a->B + 15) / 16;
-    int grid = (k.nslabs + LAT_WAVES - 1) / LAT_WAVES;
-    if (grid > 256) grid = 256;                      // one workgroup per CU
-    return launch_lds<latent_fwd_kernel>(dim3(grid), dim3(LAT_THREADS), LAT_LDS, (hipStream_t)stream, k);
+    return launch_lds<latent_fwd_kernel>(dim3(persistent_grid(k.nslabs, LAT_WAVES)), dim3(LAT_THREADS), LAT_LDS, (hipStream_t)stream, k);
 }
