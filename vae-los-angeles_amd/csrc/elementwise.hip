@@ -427,7 +427,12 @@ __device__ __forceinline__ float mse_part(const mmvae_loss_args& a, long tid0, l
 template <typename GT, int V, bool WRT_LOGIT, typename TT>
 __device__ __forceinline__ float bce_part_g(const mmvae_loss_args& a, long tid0, long stride) {
     auto f = [](float pe, float te, float& g) {
-        const float lp = fmaxf(fast_ln(pe), -100.f), l1p = fmaxf(fast_ln(1.f - pe), -100.f);   // v_log_f32: 1 ulp, clamp as torch
+        // v_log_f32 reads a denormal input as 0: ln p came out as the clamp, -100, for the p in (0, 2^-126) that a CPU sigmoid returns for
+        // logits in (-103, -87.3), where torch gives 87.3 ... 100.  Such a p is scaled by 2^32 (exact) and 32 ln 2 is taken off again, as
+        // the compiler's own logf expansion does; every other p takes the same value as before (x - 0).  1 - pe is never denormal.
+        const bool tiny = pe < 1.17549435e-38f;
+        const float lnp = fast_ln(tiny ? pe * 4294967296.f : pe) - (tiny ? 22.18070977791825f : 0.f);
+        const float lp = fmaxf(lnp, -100.f), l1p = fmaxf(fast_ln(1.f - pe), -100.f);           // v_log_f32: 1 ulp, clamp as torch
         const float pq = (1.f - pe) * pe, d = pe - te;
         // torch: grad_p = (p - t) / max(p (1 - p), 1e-12); w.r.t. the logit that times p (1 - p): exactly (p - t) unless clamped
         if constexpr (WRT_LOGIT) g = d * fminf(pq * 1e12f, 1.f);             // as EpiLoss::term (gemm_nt_epi.h): d * 1 is exact
