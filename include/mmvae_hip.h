@@ -466,6 +466,57 @@ typedef struct {
 int mmvae_recon_metrics(const mmvae_metrics_args* args, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Brute-force k nearest neighbours (euclidean) of every query row among the training rows, as a GEMM whose epilogue is a running
+ * top-k (knn.hip): the Mq x Nt scores never reach memory, only k indices (and distances) per query do.  Replaces the neighbour
+ * search of sklearn's KNeighborsRegressor(n_neighbors=5) / ConditionedKNeighborsRegressor (compare_directional_imputation.py:235-254,
+ * vae_cross_modality_cv.py:320, src/clustering_evaluation/cluster_imputation_methods.py:297-403, src/models/conditioned_knn.py:18-93)
+ * and of calculate_neighborhood_hit (src/clustering_evaluation/metrics_utils.py:19-38), which run on host copies.
+ *   q [Mq][F], t [Nt][F]: MMVAE_F32 or MMVAE_BF16 each, row-major, leading dimension in elements >= F (padded bf16 rows, see
+ *   mmvae_rows_to_bf16, included; loads are as wide as base and stride allow; pad columns and rows outside the matrices are never
+ *   read).  shift [F] (fp32, NULL = 0) is subtracted from both operands in fp32 on load: distances do not change, the conditioning
+ *   of the GEMM form does (pass the training column means).
+ * Ranking key of candidate j for query i:  key = |t_j - c|^2 - 2 (q_i - c).(t_j - c),  products and sums in fp32 on the exact-f32
+ * MFMA path; bf16 storage is widened, never multiplied as bf16.  The key of a (query row, training row) pair depends only on the
+ * values of the two rows and of shift -- not on where the rows sit, on Mq, Nt, k or on how the work was split: duplicate training
+ * rows tie bit for bit.
+ *   idx [Mq][k] (int32, leading dimension ld_idx >= k): the k candidates with the smallest keys, ascending by (key, j): among
+ *   equal keys the smaller training index first.  A NaN key orders after every other key (+inf included); -0 and +0 are one key.
+ *   dist2 [Mq][k] (fp32, optional, ld_dist2 >= k): key + |q_i - c|^2, negative values replaced by 0.
+ * Results are bit-reproducible from run to run (no float atomics; partial lists are merged in a fixed order).
+ * A workgroup owns 128 query rows and walks the training rows in tiles of 128, the rows' current k-best lists live in LDS.  When Mq
+ * alone gives too few workgroups, the training rows are split across workgroups (mmvae_knn_splits says how), the partial lists go to
+ * `work` and a second small launch merges them.  work: caller-owned, 8-byte aligned, at least mmvae_knn_work_bytes(Mq, Nt, k) bytes
+ * = 4 (Mq + Nt) for the rows' squared norms (one more streaming launch) + 8 Mq k splits when split; the library allocates nothing.
+ * Limits: Mq, Nt, F >= 1 (any F); 1 <= k <= min(Nt, MMVAE_KNN_MAXK); row offsets are 64-bit.
+ * MMVAE_ERR_ARG (nothing enqueued): a null struct, null q / t / idx / work, a size < 1, k out of range, a leading dimension below its
+ *   width, a pointer not aligned to its element (work: 8 bytes), work_bytes below mmvae_knn_work_bytes.  MMVAE_ERR_DTYPE: a dtype
+ *   that is neither MMVAE_F32 nor MMVAE_BF16.
+ * ------------------------------------------------------------------------------------------- */
+#define MMVAE_KNN_MAXK 64
+typedef struct {
+    const void* q; const void* t; const float* shift;
+    int32_t* idx; float* dist2; void* work;
+    int64_t ld_q, ld_t, ld_idx, ld_dist2, work_bytes;
+    int32_t Mq, Nt, F, k, q_dtype, t_dtype;
+} mmvae_knn_args;
+int mmvae_knn_search(const mmvae_knn_args* args, void* stream);
+/* needs no device; MMVAE_ERR_ARG for sizes < 1, k out of range or a null result pointer */
+int mmvae_knn_work_bytes(int32_t Mq, int32_t Nt, int32_t k, int64_t* bytes);
+/* the decomposition mmvae_knn_search uses for these sizes: *splits workgroups per query block, each over *rows_per_split consecutive
+ * training rows (a multiple of 128, capped at 2^31 - 128; the last split takes the rest).  *splits == 1: no workspace lists, no merge
+ * launch. */
+int mmvae_knn_splits(int32_t Mq, int32_t Nt, int32_t* splits, int32_t* rows_per_split);
+
+/* Uniform k-NN regression from the indices of mmvae_knn_search:  out[i][:] = (sum_{n<k} y[idx[i][n]][:]) / k, in fp32, summed in
+ * ascending n (deterministic; what KNeighborsRegressor.predict with uniform weights computes, conditioned_knn.py:84-91).
+ * y [Ny][Fy]: MMVAE_F32 or MMVAE_BF16 rows (ld_y >= Fy), out [Mq][Fy] fp32 (ld_out >= Fy), idx [Mq][k] int32 (ld_idx >= k); indices
+ * outside [0, Ny) are clamped, as mmvae_gather_rows does.  A streaming gather: y[idx].mean(1) in torch materialises Mq k Fy values.
+ * MMVAE_ERR_ARG: null / misaligned pointers, sizes < 1, k > MMVAE_KNN_MAXK, a leading dimension below its width, Fy > 65535 * 256;
+ * MMVAE_ERR_DTYPE: another y_dtype. */
+int mmvae_knn_mean_rows(const int32_t* idx, int64_t ld_idx, const void* y, int32_t y_dtype, int64_t ld_y, float* out, int64_t ld_out,
+                        int32_t Mq, int32_t k, int32_t Ny, int32_t Fy, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * AdamW (torch.optim.AdamW, constructed by the caller: optimize_hyperparameters.py:93-97,
  * train_dna2rna.py:185-189), all tensors in one launch per 64 tensors (every record is checked before the first launch).  `items_host` is an array in HOST memory
  * (device pointers inside); it is copied into the kernel arguments, so nothing is uploaded and the call is graph-capturable:

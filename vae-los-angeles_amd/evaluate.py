@@ -7,6 +7,9 @@
 
 One table row per (route, target modality) with the columns of compute_metrics (compare_directional_imputation.py:167-210), and
 beside every target modality the mean-imputation baseline (training-set column means, compare_directional_imputation.py:213-232).
+--knn K adds the reference's second baseline, KNeighborsRegressor(n_neighbors=K) from the other modality fitted on the training rows
+(compare_directional_imputation.py:235-254), --knn-by-site its per-site form (src/models/conditioned_knn.py); both search on the
+device (mmvae.knn).
 Routes: the directional models' one route; MultiModalVAE: a -> b, b -> a and the full (a, b, site) reconstruction.  The metrics
 are computed on the device (mmvae.metrics: one streaming launch per batch and route), nothing but 32 bytes per feature and the
 per-row vectors' aggregates reaches the host.  Evaluation runs in eval mode under no_grad; eps is still sampled (vae.py:73), so
@@ -43,6 +46,8 @@ def build_parser(kind):
     ap.add_argument("--checkpoint", default=None, help="state_dict as the trainers save it (default: the run named by latest_<tag>_run_id.txt)")
     ap.add_argument("--checkpoint-dir", default=Config.CHECKPOINT_DIR)
     ap.add_argument("--seed", type=int, default=Config.RANDOM_SEED, help="Philox stream of eps")
+    ap.add_argument("--knn", type=int, default=0, metavar="K", help="add a kNN(k=K) imputation row per target modality (0 = off)")
+    ap.add_argument("--knn-by-site", action="store_true", help="with --knn: add the per-site (conditioned) k-NN rows as well")
     ap.add_argument("--out", default=None, help="write the table rows as JSON here")
     return ap
 
@@ -137,12 +142,34 @@ def run(kind, argv=None):
                     acc[(name, tgt)].update(truth[tgt], res[j])
             for tgt in targets:
                 base[tgt].update(truth[tgt], means[tgt])
+    knn_rows = []
+    if args.knn > 0:
+        from mmvae.knn import ConditionedKNeighborsRegressor, KNeighborsRegressor
+        tr = [t[train_idx].to(dev).contiguous() for t in (tpm, beta_v, site)]
+        if args.input_dtype == "bf16":
+            tr[:2] = [to_bf16_rows(t) for t in tr[:2]]
+        mod = {"a": 0, "b": 1}
+        for tgt in targets:
+            src = "b" if tgt == "a" else "a"
+            regs = [(f"{src}->{tgt}", f"kNN(k={args.knn})", KNeighborsRegressor(args.knn).fit(tr[mod[src]], tr[mod[tgt]]), False)]
+            if args.knn_by_site:
+                regs.append((f"{src}+site->{tgt}", f"kNN-site(k={args.knn})",
+                             ConditionedKNeighborsRegressor(args.knn).fit(tr[mod[src]], tr[mod[tgt]], tr[2]), True))
+            for route, model_name, reg, by_site in regs:
+                m = ImputationMetrics(dims[tgt], dev)
+                for i in range(0, n_val, B):
+                    xq = va[mod[src]][i:i + B]
+                    m.update(va[mod[tgt]][i:i + B], reg.predict(xq, va[2][i:i + B]) if by_site else reg.predict(xq))
+                knn_rows.append(_row(route, names[tgt], model_name, m.compute()))
+    elif args.knn_by_site:
+        raise SystemExit("--knn-by-site needs --knn K")
     rows = []
     for name, _, outs in plan:
         for _, tgt in outs:
             rows.append(_row(name, names[tgt], title, acc[(name, tgt)].compute()))
     for tgt in targets:
         rows.append(_row("train mean", names[tgt], "MeanImputation", base[tgt].compute()))
+    rows += knn_rows
     print(f"{title}: {path}  ({n_val} validation rows, batch {B}, {args.precision}, {args.input_dtype} inputs)")
     print_table(rows)
     if args.out:

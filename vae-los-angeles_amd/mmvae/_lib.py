@@ -19,6 +19,7 @@ EPI_STORE, EPI_RELU_MASK, EPI_BN_BWD, EPI_LOSS_MSE, EPI_LOSS_BCE_LOGIT = 0, 1, 2
 ACT_NONE, ACT_RELU, ACT_SIGMOID = 0, 1, 2
 TILE = 128
 TN_GROUP_MAX = 8        # MMVAE_TN_GROUP_MAX
+KNN_MAXK = 64           # MMVAE_KNN_MAXK
 CTR_COPIES = 16384      # MMVAE_CTR_COPIES: self-advancing device counters are stored as this many identical int64 copies
 
 i32, i64, f32, vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
@@ -140,6 +141,12 @@ class MetricsArgs(C.Structure):
                 ("col_shift", vp), ("col_acc", vp), ("row_pearson", vp), ("row_cosine", vp)]
 
 
+class KnnArgs(C.Structure):
+    _fields_ = [("q", vp), ("t", vp), ("shift", vp), ("idx", vp), ("dist2", vp), ("work", vp),
+                ("ld_q", i64), ("ld_t", i64), ("ld_idx", i64), ("ld_dist2", i64), ("work_bytes", i64),
+                ("Mq", i32), ("Nt", i32), ("F", i32), ("k", i32), ("q_dtype", i32), ("t_dtype", i32)]
+
+
 class GatherItem(C.Structure):
     _fields_ = [("src", vp), ("dst", vp), ("src_row_stride", i64), ("dst_row_stride", i64), ("row_bytes", i32), ("pad_", i32)]
 
@@ -170,6 +177,10 @@ _SIGNATURES = {
     "mmvae_vae_loss": [C.POINTER(LossArgs), vp],
     "mmvae_loss_finalize": [vp, f32, f32, vp, vp, vp],
     "mmvae_recon_metrics": [C.POINTER(MetricsArgs), vp],
+    "mmvae_knn_search": [C.POINTER(KnnArgs), vp],
+    "mmvae_knn_work_bytes": [i32, i32, i32, C.POINTER(i64)],
+    "mmvae_knn_splits": [i32, i32, C.POINTER(i32), C.POINTER(i32)],
+    "mmvae_knn_mean_rows": [vp, i64, vp, i32, i64, vp, i64, i32, i32, i32, i32, vp],
     "mmvae_gather_rows": [vp, i32, vp, i32, i64, vp],
     "mmvae_rows_to_bf16": [vp, i32, i64, vp, i64, i32, i32, vp],
     "mmvae_sigmoid_bwd": [i32, i32, vp, i64, vp, i64, vp, i32, i64, vp],

@@ -735,6 +735,85 @@ def recon_metrics(pred, target, col_shift, col_acc, row_pearson, row_cosine):
         L.check(L.load().mmvae_recon_metrics(C.byref(a), _stream()), "mmvae_recon_metrics")
 
 
+# --------------------------------------------------------------------------------------------
+# k nearest neighbours (include/mmvae_hip.h: mmvae_knn_search, mmvae_knn_mean_rows)
+# --------------------------------------------------------------------------------------------
+def _knn_operand(t, name, F=None):
+    """(pointer, dtype, leading dimension) of a (rows, F) fp32 / bf16 device matrix with unit inner stride and rows that do not overlap."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"knn: {name} must be a CUDA/HIP tensor; there is no CPU fallback")
+    _mat(t, name)
+    if t.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"knn: {name} must be fp32 or bf16, got {t.dtype}")
+    if t.shape[0] < 1 or t.shape[1] < 1 or (F is not None and t.shape[1] != F) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        raise ValueError(f"knn: {name} is {tuple(t.shape)} / {t.stride()}, need (rows >= 1, {F if F is not None else 'F >= 1'}) rows that do not overlap")
+    return t.data_ptr(), _dt(t), _ld(t)
+
+
+def knn_splits(Mq, Nt):
+    """(splits, training rows per split) of the decomposition knn_search uses for these sizes (mmvae_knn_splits); needs no device."""
+    ns, rps = C.c_int32(0), C.c_int32(0)
+    L.check(L.load().mmvae_knn_splits(Mq, Nt, C.byref(ns), C.byref(rps)), "mmvae_knn_splits")
+    return ns.value, rps.value
+
+
+def knn_work_bytes(Mq, Nt, k):
+    n = C.c_int64(0)
+    L.check(L.load().mmvae_knn_work_bytes(Mq, Nt, k, C.byref(n)), "mmvae_knn_work_bytes")
+    return n.value
+
+
+def knn_search(q, t, k, shift=None, dist2=True, *, idx_out=None, dist2_out=None):
+    """The k nearest training rows (euclidean) of every query row (mmvae_knn_search): idx int32 (Mq, k) ascending by (distance key,
+    training index), and the squared distances fp32 (Mq, k) unless dist2 is False (then None).  q (Mq, F), t (Nt, F): fp32 or bf16,
+    unit inner stride, any row stride (padded bf16 rows included).  shift (F,) fp32 is subtracted from both operands on load (pass the
+    training column means: the distances do not change, their rounding does).  idx_out / dist2_out: write into these (views allowed)."""
+    q_ptr, q_dt, q_ld = _knn_operand(q, "q")
+    Mq, F = q.shape
+    t_ptr, t_dt, t_ld = _knn_operand(t, "t", F)
+    Nt = t.shape[0]
+    k = int(k)
+    if not 1 <= k <= min(Nt, L.KNN_MAXK):
+        raise ValueError(f"knn_search: k = {k} outside [1, min({Nt} training rows, {L.KNN_MAXK})]")
+    if shift is not None and (not shift.is_cuda or shift.dtype != torch.float32 or tuple(shift.shape) != (F,) or not shift.is_contiguous()):
+        raise ValueError(f"knn_search: shift must be a contiguous fp32 ({F},) device tensor")
+    idx = torch.empty(Mq, k, dtype=torch.int32, device=q.device) if idx_out is None else idx_out
+    d2 = (torch.empty(Mq, k, dtype=torch.float32, device=q.device) if dist2_out is None else dist2_out) if dist2 else None
+    for o, name, dt in ((idx, "idx_out", torch.int32), (d2, "dist2_out", torch.float32)):
+        if o is not None and (not o.is_cuda or o.dtype != dt or tuple(o.shape) != (Mq, k) or o.stride(1) != 1 or (Mq > 1 and o.stride(0) < k)):
+            raise ValueError(f"knn_search: {name} must be a {dt} ({Mq}, {k}) device tensor with unit inner stride")
+    if len({x.device for x in (q, t, idx) + ((shift,) if shift is not None else ()) + ((d2,) if d2 is not None else ())}) != 1:
+        raise ValueError("knn_search: all operands must live on one device")
+    nbytes = knn_work_bytes(Mq, Nt, k)
+    work = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=q.device)
+    a = L.KnnArgs(q_ptr, t_ptr, _p(shift), idx.data_ptr(), _p(d2), work.data_ptr(), q_ld, t_ld, _ld(idx), _ld(d2) if d2 is not None else 0,
+                  work.numel() * 8, Mq, Nt, F, k, q_dt, t_dt)
+    with probe_span("knn_search", lambda: dict(kind="gemm", flops=2.0 * Mq * Nt * F, M=Mq, N=Nt, K=F)):
+        L.check(L.load().mmvae_knn_search(C.byref(a), _stream()), "mmvae_knn_search")
+    return idx, d2
+
+
+def knn_mean_rows(idx, y, out=None):
+    """out[i] = mean over n of y[idx[i][n]] in fp32, summed in ascending n (mmvae_knn_mean_rows): uniform k-NN regression.
+    idx int32 (Mq, k), y (Ny, Fy) fp32 or bf16, out fp32 (Mq, Fy); indices outside [0, Ny) are clamped."""
+    y_ptr, y_dt, y_ld = _knn_operand(y, "y")
+    if not isinstance(idx, torch.Tensor) or not idx.is_cuda or idx.dtype != torch.int32 or idx.dim() != 2 or idx.stride(1) != 1 or idx.shape[0] < 1 \
+            or not 1 <= idx.shape[1] <= L.KNN_MAXK:
+        raise ValueError(f"knn_mean_rows: idx must be an int32 (Mq, 1 <= k <= {L.KNN_MAXK}) device tensor with unit inner stride")
+    Mq, k = idx.shape
+    Ny, Fy = y.shape
+    if out is None:
+        out = torch.empty(Mq, Fy, dtype=torch.float32, device=y.device)
+    if not out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != (Mq, Fy) or out.stride(1) != 1 or (Mq > 1 and out.stride(0) < Fy):
+        raise ValueError(f"knn_mean_rows: out must be an fp32 ({Mq}, {Fy}) device tensor with unit inner stride")
+    if len({idx.device, y.device, out.device}) != 1:
+        raise ValueError("knn_mean_rows: all operands must live on one device")
+    with stream_span("knn_mean_rows", Mq * k * (4 + Fy * y.element_size()) + 4 * Mq * Fy):
+        L.check(L.load().mmvae_knn_mean_rows(idx.data_ptr(), _ld(idx), y_ptr, y_dt, y_ld, out.data_ptr(), _ld(out), Mq, k, Ny, Fy, _stream()),
+                "mmvae_knn_mean_rows")
+    return out
+
+
 def adamw_step(items, lr, b1, b2, eps, wd, bc1, bc2, maximize=False, step_dev=None, lr_dev=None):
     """items: ctypes array of AdamWItem in host memory (device pointers inside).  step_dev: int64[CTR_COPIES] tensor of
     identical copies of the step count: bias corrections from the device counter, which the launch itself increments
