@@ -517,6 +517,54 @@ int mmvae_knn_mean_rows(const int32_t* idx, int64_t ld_idx, const void* y, int32
                         int32_t Mq, int32_t k, int32_t Ny, int32_t Fy, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Silhouette coefficient of every row (sklearn.metrics.silhouette_samples, euclidean) as a distance GEMM whose epilogue is a square
+ * root and a per-class row sum (silhouette.hip): the N x N distances never reach memory.  Replaces silhouette_score over host copies
+ * (src/clustering_evaluation/cluster_imputation_methods.py:478-504, cluster_reconstructed.py:299-317).
+ * For rows x_i with class l_i in [0, C) and class sizes n_c:
+ *   S_ic = sum_{j : l_j = c} |x_i - x_j|  (the pair j = i contributes exactly 0)
+ *   a_i = S_{i,l_i} / (n_{l_i} - 1)       b_i = min over c != l_i with n_c > 0 of S_ic / n_c       s_i = (b_i - a_i) / max(a_i, b_i)
+ *   s_i = 0 and a_i = 0 when n_{l_i} = 1; s_i = 0 when max(a_i, b_i) = 0 (sklearn's nan_to_num).  A row without any other non-empty
+ *   class (sklearn raises) gets b_i = +inf and s_i = 0.
+ *   x [N][F]: MMVAE_F32 or MMVAE_BF16, row-major, ld_x >= F in elements (padded bf16 rows, see mmvae_rows_to_bf16, included; loads are
+ *   as wide as base and stride allow; pad columns and rows outside the matrix are never read).  shift [F] (fp32, NULL = 0) is subtracted
+ *   from every element in fp32 on load, as in mmvae_knn_search: pass the column means.
+ *   order [N] (int32, NULL = the rows are already grouped): the row indices grouped by class, class 0 first; the kernels read row
+ *   order[p] for position p, values outside [0, N) are clamped as in mmvae_gather_rows.  No gathered copy of x is needed.
+ *   class_start [C + 1] (int32, device): class c owns the positions class_start[c] .. class_start[c + 1] - 1; class_start[0] = 0,
+ *   non-decreasing, class_start[C] = N; empty classes are allowed and skipped in b.  It cannot be validated at the call: in the
+ *   kernels the values are clamped to [0, N], made non-decreasing and the two ends forced to 0 and N, so a bad vector gives wrong
+ *   numbers but no access out of range.
+ *   s (required), intra (= a, optional), inter (= b, optional): fp32 [N] in the caller's ROW order (written at index order[p]).
+ * d_ij = sqrt(max(|x_i - c|^2 + |x_j - c|^2 - 2 (x_i - c).(x_j - c), 0)), products and sums in fp32 on the exact-f32 MFMA path, bf16
+ * storage widened; correctly rounded square root and divisions.  Every sum has one fixed order (a lane's four columns, a butterfly
+ * over the 16 lanes of a row, the two column waves, the tiles of a class, the splits in ascending order): no float atomics, results
+ * are bit-identical from run to run for the same arguments and split count.
+ * A workgroup owns 128 positions as query rows and walks the columns class by class in tiles of 128 that never cross a class
+ * boundary.  splits: 0 = the library chooses (as mmvae_knn_search does: below 4 x 256 row blocks the column tiles are split),
+ * 1 .. 64 forces that many; either is clamped to an upper bound of the number of column tiles that needs no device,
+ * min(N, (N + 127 C) / 128), and mmvae_silhouette_splits returns the count used.  With more than one split every split writes [C]
+ * partial sums per row to `work` and a second small launch adds them in ascending split order.
+ * work: caller-owned, 8-byte aligned, at least mmvae_silhouette_work_bytes(N, C, splits) bytes = 4 N (rounded up to 8) for the rows'
+ * squared norms (one more streaming launch) + 4 N C splits_used when split; the library allocates nothing.
+ * Limits: 2 <= N < 2^31, F >= 1, 1 <= C <= MMVAE_SIL_MAXC; row offsets are 64-bit; class sizes are exact in fp32 below 2^24 rows.
+ * MMVAE_ERR_ARG (nothing enqueued): a null struct, null x / class_start / s / work, a size out of range, ld_x < F, a pointer not
+ *   aligned to its element (work: 8 bytes), work_bytes too small, splits outside [0, 64].  MMVAE_ERR_DTYPE: an x_dtype that is neither
+ *   MMVAE_F32 nor MMVAE_BF16.
+ * ------------------------------------------------------------------------------------------- */
+#define MMVAE_SIL_MAXC 64
+typedef struct {
+    const void* x; const float* shift; const int32_t* order; const int32_t* class_start;
+    float* s; float* intra; float* inter; void* work;
+    int64_t ld_x, work_bytes;
+    int32_t N, F, C, splits, x_dtype, pad_;
+} mmvae_silhouette_args;
+int mmvae_silhouette_samples(const mmvae_silhouette_args* args, void* stream);
+/* need no device; MMVAE_ERR_ARG for N < 2, C outside [1, MMVAE_SIL_MAXC], splits outside [0, 64] or a null result pointer.
+ * *splits_used: the number of column splits mmvae_silhouette_samples uses for (N, C, splits). */
+int mmvae_silhouette_work_bytes(int32_t N, int32_t C, int32_t splits, int64_t* bytes);
+int mmvae_silhouette_splits(int32_t N, int32_t C, int32_t splits, int32_t* splits_used);
+
+/* ---------------------------------------------------------------------------------------------
  * AdamW (torch.optim.AdamW, constructed by the caller: optimize_hyperparameters.py:93-97,
  * train_dna2rna.py:185-189), all tensors in one launch per 64 tensors (every record is checked before the first launch).  `items_host` is an array in HOST memory
  * (device pointers inside); it is copied into the kernel arguments, so nothing is uploaded and the call is graph-capturable:

@@ -20,6 +20,7 @@
 // The squared norms |t_j - c|^2, |q_i - c|^2 come from one streaming launch (a wave per row) into the workspace.
 #include "common.h"
 #include "wave_slab.h"
+#include "row_tile.h"
 
 namespace mm {
 
@@ -51,30 +52,6 @@ __device__ __forceinline__ unsigned knn_order(float key) {
     return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
 }
 __device__ __forceinline__ float knn_key(unsigned u) { return __uint_as_float((u >> 31) ? (u ^ 0x80000000u) : ~u); }
-
-__device__ __forceinline__ void knn_vld(const float* p, int vec, float (&r)[4]) {
-    if (vec >= 4) { const f32x4 v = *(const f32x4*)p; r[0] = v[0]; r[1] = v[1]; r[2] = v[2]; r[3] = v[3]; }
-    else if (vec == 2) { const f32x2 a = *(const f32x2*)p, b = *(const f32x2*)(p + 2); r[0] = a[0]; r[1] = a[1]; r[2] = b[0]; r[3] = b[1]; }
-    else { r[0] = p[0]; r[1] = p[1]; r[2] = p[2]; r[3] = p[3]; }
-}
-__device__ __forceinline__ void knn_vld(const bf16* p, int vec, bf16 (&r)[4]) {
-    if (vec >= 4) { const bf16x4 v = *(const bf16x4*)p; r[0] = v[0]; r[1] = v[1]; r[2] = v[2]; r[3] = v[3]; }
-    else if (vec == 2) { const bf16x2 a = *(const bf16x2*)p, b = *(const bf16x2*)(p + 2); r[0] = a[0]; r[1] = a[1]; r[2] = b[0]; r[3] = b[1]; }
-    else { r[0] = p[0]; r[1] = p[1]; r[2] = p[2]; r[3] = p[3]; }
-}
-// columns c0 .. c0 + 3 (c0 a multiple of 4) of a row, as stored: zeros for a row outside the matrix and for columns >= F, which are
-// not read
-template <typename T>
-__device__ __forceinline__ void knn_ld4(const T* row, bool rowok, int c0, int F, int vec, T (&r)[4]) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) r[j] = (T)0.f;
-    if (!rowok || c0 >= F) return;
-    if (c0 + 4 <= F) knn_vld(row + c0, vec, r);
-    else {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) if (c0 + j < F) r[j] = row[c0 + j];
-    }
-}
 
 // The 16 lanes of a row group (lane >> 4) insert their passing candidates into the group's list, one at a time; the wave's four groups
 // in lock step.  L: this lane's group's list (k sorted entries).
@@ -267,12 +244,7 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_norms_kernel(KnnP a, float* o
     const long r = isq ? row : row - a.Mq;
     const int dt = isq ? a.vq >> 8 : a.vt >> 8;            // the host passes the dtype above the vector width here
     const char* base = (const char*)(isq ? a.q : a.t) + r * (isq ? a.ldq : a.ldt) * (dt == MMVAE_BF16 ? 2 : 4);
-    float s = 0.f;
-    for (int c = lane; c < a.F; c += WAVE) {
-        const float x = (dt == MMVAE_BF16 ? (float)((const bf16*)base)[c] : ((const float*)base)[c]) - (a.shift ? a.shift[c] : 0.f);
-        s += x * x;
-    }
-    s = wave_sum(s);
+    const float s = row_sqnorm(base, dt, a.F, a.shift, lane);
     if (lane == 0) out[row] = s;
 }
 
@@ -289,13 +261,6 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_mean_kernel(const int* idx, l
         s += to_f32(y[j * ldy + c]);
     }
     out[row * ldo + c] = s / (float)k;
-}
-
-// elements per vector load (at most 4) that the base address and the leading dimension allow
-static int knn_vec(const void* p, long ld, int esize) {
-    for (int v = 4; v > 1; v >>= 1)
-        if (ld % v == 0 && ((uintptr_t)p % (uintptr_t)(v * esize)) == 0) return v;
-    return 1;
 }
 
 static bool knn_sizes_ok(int Mq, int Nt, int k) { return Mq >= 1 && Nt >= 1 && k >= 1 && k <= Nt && k <= MMVAE_KNN_MAXK; }

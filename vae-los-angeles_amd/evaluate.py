@@ -10,6 +10,10 @@ beside every target modality the mean-imputation baseline (training-set column m
 --knn K adds the reference's second baseline, KNeighborsRegressor(n_neighbors=K) from the other modality fitted on the training rows
 (compare_directional_imputation.py:235-254), --knn-by-site its per-site form (src/models/conditioned_knn.py); both search on the
 device (mmvae.knn).
+--clustering adds the reference's clustering table (src/clustering_evaluation/cluster_imputation_methods.py:478-504): silhouette score
+and neighbourhood hit (k = 5) of the standardised features [a | b] against the validation sites -- for the true features and, per
+single-target imputation route, with the target part replaced by the model's, the mean's and (with --knn) the k-NN imputations; both
+numbers are computed on the device (mmvae.clustering), one feature matrix at a time.
 Routes: the directional models' one route; MultiModalVAE: a -> b, b -> a and the full (a, b, site) reconstruction.  The metrics
 are computed on the device (mmvae.metrics: one streaming launch per batch and route), nothing but 32 bytes per feature and the
 per-row vectors' aggregates reaches the host.  Evaluation runs in eval mode under no_grad; eps is still sampled (vae.py:73), so
@@ -49,6 +53,8 @@ def build_parser(kind):
     ap.add_argument("--knn", type=int, default=0, metavar="K", help="add a kNN(k=K) imputation row per target modality (0 = off)")
     ap.add_argument("--knn-by-site", action="store_true", help="with --knn: add the per-site (conditioned) k-NN rows as well")
     ap.add_argument("--out", default=None, help="write the table rows as JSON here")
+    ap.add_argument("--clustering", action="store_true", help="add the clustering table: silhouette and neighbourhood hit (k=5) by site")
+    ap.add_argument("--clustering-out", default=None, help="with --clustering: write that table's rows as JSON here")
     return ap
 
 
@@ -78,7 +84,44 @@ def print_table(rows):
               + "".join(f"{r[c]:>17d}" if c == "PearsonValid" else f"{r[c]:>17.6f}" for c in COLUMNS))
 
 
-def run(kind, argv=None):
+CLUSTERING_COLUMNS = ("Silhouette", "NeighborhoodHit")
+NH_K = 5
+
+
+def print_clustering_table(rows):
+    head = f"{'Features':<16}{'Model':<16}" + "".join(f"{c:>17}" for c in CLUSTERING_COLUMNS)
+    print(head)
+    print("-" * len(head))
+    for r in rows:
+        print(f"{r['Features']:<16}{r['Model']:<16}" + "".join(f"{r[c]:>17.6f}" for c in CLUSTERING_COLUMNS))
+
+
+def clustering_table(entries, va, dims, B):
+    """[(features, model name, fill)] -> table rows.  fill(i, tgt) gives the imputed rows i .. i + B of its target modality, or is None
+    for the true features.  ONE (rows, A + D) fp32 matrix is filled batch by batch, standardised, judged and reused."""
+    from mmvae import clustering
+    from mmvae._lib import SIL_MAXC
+    n_val, labels = va[0].shape[0], va[2]
+    n_labels = int(torch.unique(labels).numel())
+    if not 2 <= n_labels <= min(n_val - 1, SIL_MAXC):
+        print(f"clustering table skipped: {n_labels} distinct sites among {n_val} validation rows "
+              f"(need 2 .. min(rows - 1, {SIL_MAXC}))")
+        return []
+    feats = torch.empty(n_val, dims["a"] + dims["b"], dtype=torch.float32, device=labels.device)
+    part = {"a": feats[:, :dims["a"]], "b": feats[:, dims["a"]:]}
+    rows = []
+    for features, model_name, tgt, fill in entries:
+        for i in range(0, n_val, B):
+            for m, j in (("a", 0), ("b", 1)):
+                part[m][i:i + B].copy_(fill(i) if m == tgt else va[j][i:i + B])
+        z = clustering.standardize(feats)
+        rows.append({"Features": features, "Model": model_name, "Silhouette": clustering.silhouette_score(z, labels),
+                     "NeighborhoodHit": clustering.neighborhood_hit(z, labels, k=NH_K)})
+        del z
+    return rows
+
+
+def run(kind, argv=None, return_clustering=False):
     args = build_parser(kind).parse_args(argv)
     tag, title = KINDS[kind]["tag"], KINDS[kind]["title"]
     if not torch.cuda.is_available():
@@ -142,7 +185,7 @@ def run(kind, argv=None):
                     acc[(name, tgt)].update(truth[tgt], res[j])
             for tgt in targets:
                 base[tgt].update(truth[tgt], means[tgt])
-    knn_rows = []
+    knn_rows, knn_regs = [], []
     if args.knn > 0:
         from mmvae.knn import ConditionedKNeighborsRegressor, KNeighborsRegressor
         tr = [t[train_idx].to(dev).contiguous() for t in (tpm, beta_v, site)]
@@ -161,8 +204,11 @@ def run(kind, argv=None):
                     xq = va[mod[src]][i:i + B]
                     m.update(va[mod[tgt]][i:i + B], reg.predict(xq, va[2][i:i + B]) if by_site else reg.predict(xq))
                 knn_rows.append(_row(route, names[tgt], model_name, m.compute()))
+                knn_regs.append((route, model_name, reg, by_site, mod[src], tgt))
     elif args.knn_by_site:
         raise SystemExit("--knn-by-site needs --knn K")
+    if args.clustering_out and not args.clustering:
+        raise SystemExit("--clustering-out needs --clustering")
     rows = []
     for name, _, outs in plan:
         for _, tgt in outs:
@@ -175,7 +221,29 @@ def run(kind, argv=None):
     if args.out:
         with open(args.out, "w") as f:
             json.dump(rows, f, indent=1)
-    return rows
+    if not args.clustering:
+        return (rows, []) if return_clustering else rows
+    # the clustering table: after the metrics, so that the table above does not depend on the flag (eps is drawn per forward)
+    entries = [("a|b", "original", None, None)]
+    with torch.no_grad():
+        for name, kwargs, outs in plan:
+            if len(outs) != 1:                               # the full reconstruction is not an imputation
+                continue
+            j, tgt = outs[0]
+            entries.append((name, title, tgt, lambda i, kwargs=kwargs, j=j: model(**kwargs(va[0][i:i + B], va[1][i:i + B], va[2][i:i + B]))[j]))
+            entries.append((name, "MeanImputation", tgt, lambda i, tgt=tgt: means[tgt].expand(min(B, n_val - i), -1)))
+            for route, model_name, reg, by_site, src_i, rtgt in knn_regs:
+                if rtgt == tgt:
+                    entries.append((route, model_name, tgt, lambda i, reg=reg, by_site=by_site, src_i=src_i:
+                                    reg.predict(va[src_i][i:i + B], va[2][i:i + B]) if by_site else reg.predict(va[src_i][i:i + B])))
+        crows = clustering_table(entries, va, dims, B)
+    if crows:
+        print(f"clustering by site: standardised [a | b] features, silhouette and neighbourhood hit (k={NH_K})")
+        print_clustering_table(crows)
+    if args.clustering_out:
+        with open(args.clustering_out, "w") as f:
+            json.dump(crows, f, indent=1)
+    return (rows, crows) if return_clustering else rows
 
 
 if __name__ == "__main__":

@@ -20,6 +20,7 @@ ACT_NONE, ACT_RELU, ACT_SIGMOID = 0, 1, 2
 TILE = 128
 TN_GROUP_MAX = 8        # MMVAE_TN_GROUP_MAX
 KNN_MAXK = 64           # MMVAE_KNN_MAXK
+SIL_MAXC = 64           # MMVAE_SIL_MAXC
 CTR_COPIES = 16384      # MMVAE_CTR_COPIES: self-advancing device counters are stored as this many identical int64 copies
 
 i32, i64, f32, vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
@@ -147,6 +148,12 @@ class KnnArgs(C.Structure):
                 ("Mq", i32), ("Nt", i32), ("F", i32), ("k", i32), ("q_dtype", i32), ("t_dtype", i32)]
 
 
+class SilhouetteArgs(C.Structure):
+    _fields_ = [("x", vp), ("shift", vp), ("order", vp), ("class_start", vp), ("s", vp), ("intra", vp), ("inter", vp), ("work", vp),
+                ("ld_x", i64), ("work_bytes", i64),
+                ("N", i32), ("F", i32), ("C", i32), ("splits", i32), ("x_dtype", i32), ("pad_", i32)]
+
+
 class GatherItem(C.Structure):
     _fields_ = [("src", vp), ("dst", vp), ("src_row_stride", i64), ("dst_row_stride", i64), ("row_bytes", i32), ("pad_", i32)]
 
@@ -181,6 +188,9 @@ _SIGNATURES = {
     "mmvae_knn_work_bytes": [i32, i32, i32, C.POINTER(i64)],
     "mmvae_knn_splits": [i32, i32, C.POINTER(i32), C.POINTER(i32)],
     "mmvae_knn_mean_rows": [vp, i64, vp, i32, i64, vp, i64, i32, i32, i32, i32, vp],
+    "mmvae_silhouette_samples": [C.POINTER(SilhouetteArgs), vp],
+    "mmvae_silhouette_work_bytes": [i32, i32, i32, C.POINTER(i64)],
+    "mmvae_silhouette_splits": [i32, i32, i32, C.POINTER(i32)],
     "mmvae_gather_rows": [vp, i32, vp, i32, i64, vp],
     "mmvae_rows_to_bf16": [vp, i32, i64, vp, i64, i32, i32, vp],
     "mmvae_sigmoid_bwd": [i32, i32, vp, i64, vp, i64, vp, i32, i64, vp],

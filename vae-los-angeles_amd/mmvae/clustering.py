@@ -1,0 +1,65 @@
+"""The two numbers the reference judges a clustering with, on the device: silhouette_score(StandardScaler().fit_transform(features),
+labels) and calculate_neighborhood_hit (src/clustering_evaluation/cluster_imputation_methods.py:478-504, cluster_reconstructed.py:299-317).
+
+    Z = standardize(features)                      # StandardScaler().fit_transform, fp32 on the device
+    s = silhouette_samples(Z, labels)              # fp32 (N,) on the device
+    score = silhouette_score(Z, labels)            # Python float
+    nh = neighborhood_hit(Z, labels, k=5)
+
+The silhouette runs on mmvae_silhouette_samples (a fp32 MFMA distance GEMM whose epilogue is a square root and a per-class row sum: the
+N x N distances never exist).  Euclidean metric only, no sample_size (nothing in the reference uses either)."""
+import torch
+
+from . import _lib as L
+from . import ops
+from .knn import _column_means, _device_matrix, neighborhood_hit  # noqa: F401  (neighborhood_hit: re-exported)
+
+__all__ = ["silhouette_samples", "silhouette_score", "standardize", "neighborhood_hit"]
+
+
+def _encode(labels, N, device):
+    """(order int32 (N,), class_start int32 (C + 1,)) of any integer labels: codes by torch.unique, a class's rows in their own order"""
+    labels = torch.as_tensor(labels)
+    if labels.dim() != 1 or labels.shape[0] != N or labels.dtype.is_floating_point or labels.dtype.is_complex or labels.dtype == torch.bool:
+        raise ValueError(f"labels must be an integer ({N},) tensor or array")
+    values, codes, counts = torch.unique(labels.to(device), return_inverse=True, return_counts=True)
+    n_labels = values.shape[0]
+    if not 1 < n_labels < N:
+        raise ValueError("Number of labels is %d. Valid values are 2 to n_samples - 1 (inclusive)" % n_labels)
+    if n_labels > L.SIL_MAXC:
+        raise ValueError(f"Number of labels is {n_labels}: at most {L.SIL_MAXC} (MMVAE_SIL_MAXC) are supported")
+    order = torch.argsort(codes, stable=True).to(torch.int32)
+    class_start = torch.zeros(n_labels + 1, dtype=torch.int32, device=device)
+    class_start[1:] = torch.cumsum(counts, 0)
+    return order, class_start
+
+
+def silhouette_samples(X, labels, metric="euclidean"):
+    """sklearn.metrics.silhouette_samples(X, labels) as an fp32 (N,) device tensor."""
+    if metric != "euclidean":
+        raise ValueError(f"metric={metric!r}: only 'euclidean' is implemented")
+    if not isinstance(X, torch.Tensor) or not X.is_cuda:
+        raise RuntimeError("mmvae.clustering: X must be a CUDA/HIP tensor; there is no CPU fallback")
+    X = _device_matrix(X, "X")
+    order, class_start = _encode(labels, X.shape[0], X.device)
+    return ops.silhouette_samples(X, order, class_start, _column_means(X))[0]
+
+
+def silhouette_score(X, labels, metric="euclidean"):
+    """sklearn.metrics.silhouette_score(X, labels): the mean of the samples, in float64."""
+    return float(silhouette_samples(X, labels, metric).double().mean())
+
+
+def standardize(X):
+    """StandardScaler().fit_transform(X): float64 column mean and population variance, a zero-variance (constant) column keeps scale 1; fp32,
+    contiguous, on X's device."""
+    if not isinstance(X, torch.Tensor) or X.dim() != 2:
+        raise ValueError("standardize: X must be a 2-D tensor")
+    Xd = X.detach().double()
+    mean = Xd.mean(dim=0)
+    var = Xd.var(dim=0, unbiased=False)
+    # a constant column's variance is zero up to the rounding of its mean: sklearn's bound (_is_constant_feature)
+    n, eps = Xd.shape[0], torch.finfo(torch.float64).eps
+    constant = var <= n * eps * var + (n * mean * eps) ** 2
+    scale = torch.where(constant, torch.ones_like(var), var.sqrt())
+    return ((Xd - mean) / scale).float().contiguous()

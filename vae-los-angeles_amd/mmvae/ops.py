@@ -814,6 +814,62 @@ def knn_mean_rows(idx, y, out=None):
     return out
 
 
+# --------------------------------------------------------------------------------------------
+# silhouette coefficient (include/mmvae_hip.h: mmvae_silhouette_samples)
+# --------------------------------------------------------------------------------------------
+def silhouette_splits(N, n_classes, splits=0):
+    """The number of column splits silhouette_samples uses for these sizes and this request (mmvae_silhouette_splits); needs no device."""
+    ns = C.c_int32(0)
+    L.check(L.load().mmvae_silhouette_splits(N, n_classes, splits, C.byref(ns)), "mmvae_silhouette_splits")
+    return ns.value
+
+
+def silhouette_work_bytes(N, n_classes, splits=0):
+    n = C.c_int64(0)
+    L.check(L.load().mmvae_silhouette_work_bytes(N, n_classes, splits, C.byref(n)), "mmvae_silhouette_work_bytes")
+    return n.value
+
+
+def silhouette_samples(x, order, class_start, shift=None, *, splits=0, s_out=None, intra_out=None, inter_out=None):
+    """Silhouette coefficient of every row of x (mmvae_silhouette_samples): (s, intra, inter), fp32 (N,) each in x's row order.
+    x (N, F): fp32 or bf16, unit inner stride, any row stride (padded bf16 rows included).  order: int32 (N,) row indices grouped by
+    class, or None when the rows are already grouped; class_start: int32 (C + 1,) positions, class c owns order[class_start[c] :
+    class_start[c + 1]].  shift (F,) fp32 is subtracted from every element on load (pass the column means).  splits: 0 = the library's
+    choice, 1 .. 64 forces that many column splits.  *_out: write into these (views allowed)."""
+    x_ptr, x_dt, x_ld = _knn_operand(x, "x")
+    N, F = x.shape
+    dev = x.device
+
+    def vec(t, name, dt, n, stride1=False):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt or tuple(t.shape) != (n,) or (not stride1 and not t.is_contiguous()) \
+                or (stride1 and n > 1 and t.stride(0) != 1) or t.device != dev:
+            raise ValueError(f"silhouette_samples: {name} must be a {'' if stride1 else 'contiguous '}{dt} ({n},) tensor on x's device")
+        return t
+
+    if not isinstance(class_start, torch.Tensor) or class_start.dim() != 1:
+        raise ValueError("silhouette_samples: class_start must be an int32 (C + 1,) device tensor")
+    nc = class_start.shape[0] - 1
+    if N < 2 or not 1 <= nc <= L.SIL_MAXC:
+        raise ValueError(f"silhouette_samples: N = {N}, C = {nc} outside N >= 2, 1 <= C <= {L.SIL_MAXC}")
+    vec(class_start, "class_start", torch.int32, nc + 1)
+    if order is not None:
+        vec(order, "order", torch.int32, N)
+    if shift is not None:
+        vec(shift, "shift", torch.float32, F)
+    splits = int(splits)
+    if not 0 <= splits <= 64:
+        raise ValueError(f"silhouette_samples: splits = {splits} outside [0, 64]")
+    outs = [vec(torch.empty(N, dtype=torch.float32, device=dev) if o is None else o, name, torch.float32, N, stride1=True)
+            for o, name in ((s_out, "s_out"), (intra_out, "intra_out"), (inter_out, "inter_out"))]
+    nbytes = silhouette_work_bytes(N, nc, splits)
+    work = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    a = L.SilhouetteArgs(x_ptr, _p(shift), _p(order), class_start.data_ptr(), outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(),
+                         work.data_ptr(), x_ld, work.numel() * 8, N, F, nc, splits, x_dt, 0)
+    with probe_span("silhouette_samples", lambda: dict(kind="gemm", flops=2.0 * N * N * F, M=N, N=N, K=F)):
+        L.check(L.load().mmvae_silhouette_samples(C.byref(a), _stream()), "mmvae_silhouette_samples")
+    return tuple(outs)
+
+
 def adamw_step(items, lr, b1, b2, eps, wd, bc1, bc2, maximize=False, step_dev=None, lr_dev=None):
     """items: ctypes array of AdamWItem in host memory (device pointers inside).  step_dev: int64[CTR_COPIES] tensor of
     identical copies of the step count: bias corrections from the device counter, which the launch itself increments
