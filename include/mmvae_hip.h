@@ -565,6 +565,64 @@ int mmvae_silhouette_work_bytes(int32_t N, int32_t C, int32_t splits, int64_t* b
 int mmvae_silhouette_splits(int32_t N, int32_t C, int32_t splits, int32_t* splits_used);
 
 /* ---------------------------------------------------------------------------------------------
+ * The two passes of an exact PCA over the data (pca.hip): the centred scatter matrix and the projection onto the components.  With
+ * the eigen-solve of the F x F matrix between them (the caller's) they replace PCA(n_components=2, random_state=42).fit_transform(
+ * StandardScaler().fit_transform(features)) and the PCA(50) in front of t-SNE over host copies
+ * (src/clustering_evaluation/cluster_imputation_methods.py:140-187).
+ *
+ * mmvae_pca_scatter:  S[a][b] = sum_i (x_ia - c_a)~ (x_ib - c_b)~   (~: rounded to fp32)
+ *   x [N][F]: MMVAE_F32 or MMVAE_BF16, row-major, ld_x >= F in elements (padded bf16 rows, see mmvae_rows_to_bf16, included; loads are
+ *   as wide as base and stride allow; pad columns and rows outside the matrix are never read).  shift [F] (fp32, NULL = 0) is
+ *   subtracted from every element in fp32 on load, as in mmvae_knn_search: pass the column means.  s [F][F]: fp32, ld_s >= F.
+ * Products and sums in fp32 on the exact-f32 MFMA path, bf16 storage widened, never multiplied as bf16.  The rows are the GEMM's K
+ * dimension; both operands are column tiles of one row tile of x, so no load is transposed.  Only the T (T + 1) / 2 pairs of 128 x 128
+ * tiles on or above the diagonal are computed, T = ceil(F / 128); element (a, b), a <= b, is stored at S[a][b] and at S[b][a], inside
+ * a diagonal tile too: S is bitwise symmetric.  Every element is one fused-multiply-add chain over its split's rows in ascending
+ * order, then the splits in ascending order: no float atomics, the same arguments and split count give the same bits.
+ * Rounding steps on the longest path of a term: 1 per centred operand, then at most N (rows_of_split fused multiply-adds +
+ * splits_used - 1 additions <= N, every split being non-empty).
+ * splits: 0 = the library chooses, 1 .. 64 forces that many; mmvae_pca_scatter_splits returns the count used:
+ *   P = T (T + 1) / 2,  chunks = ceil(N / 32)
+ *   want = splits > 0 ? splits : max(1, min(floor(512 / P), floor(chunks / 8)))      (512: the workgroups resident at once)
+ *   want = min(want, 64, chunks);  chunks_per_split = ceil(chunks / want);  splits_used = ceil(chunks / chunks_per_split)
+ * Split s takes the rows 32 s chunks_per_split .. (consecutive runs, none empty).  With more than one split every split writes its whole
+ * partial tiles to `work` and a second small launch adds them in ascending split order and writes both triangles; with one split the
+ * main kernel writes S itself and work may be NULL.
+ * work: caller-owned, 8-byte aligned, at least mmvae_pca_scatter_work_bytes(N, F, splits) bytes = 65 536 P splits_used when
+ * splits_used > 1, else 0; the library allocates nothing.
+ * Limits: N >= 1, 1 <= F <= 4 194 304 (P is a grid dimension); row offsets are 64-bit.
+ * MMVAE_ERR_ARG (nothing enqueued): a null struct, null x / s, null work where bytes > 0, a size < 1, ld_x < F or ld_s < F, a pointer
+ *   not aligned to its element (work: 8 bytes), work_bytes too small, splits outside [0, 64].  MMVAE_ERR_DTYPE: an x_dtype that is
+ *   neither MMVAE_F32 nor MMVAE_BF16.
+ *
+ * mmvae_pca_project:  y[i][j] = sum_f (x_if - c_f)~ v[j][f]
+ *   x, shift as above; v [k][F]: fp32, ld_v >= F; y [N][k]: fp32, ld_y >= k; 1 <= k <= MMVAE_PCA_MAXK (the reference's 2 and 50).
+ * A workgroup owns 128 rows and walks F in chunks of 32 columns, staging the chunk of all k components in LDS (v does not fit whole).
+ * y[i][j] is one fused-multiply-add chain over f in ascending order on the exact-f32 MFMA path: its bits depend only on row i's
+ * values, shift and v -- not on N, on where the row sits or on a leading dimension.  Rounding steps per term: 1 for the centred
+ * operand, then at most F.
+ * MMVAE_ERR_ARG (nothing enqueued): a null struct, null x / v / y, a size < 1, k outside [1, MMVAE_PCA_MAXK], a leading dimension
+ *   below its width, a pointer not aligned to its element.  MMVAE_ERR_DTYPE: another x_dtype.
+ * ------------------------------------------------------------------------------------------- */
+#define MMVAE_PCA_MAXK 64
+typedef struct {
+    const void* x; const float* shift; float* s; void* work;
+    int64_t ld_x, ld_s, work_bytes;
+    int32_t N, F, splits, x_dtype;
+} mmvae_pca_scatter_args;
+int mmvae_pca_scatter(const mmvae_pca_scatter_args* args, void* stream);
+/* need no device; MMVAE_ERR_ARG for N < 1, F outside [1, 4 194 304], splits outside [0, 64] or a null result pointer.
+ * *splits_used: the number of row splits mmvae_pca_scatter uses for (N, F, splits). */
+int mmvae_pca_scatter_splits(int32_t N, int32_t F, int32_t splits, int32_t* splits_used);
+int mmvae_pca_scatter_work_bytes(int32_t N, int32_t F, int32_t splits, int64_t* bytes);
+typedef struct {
+    const void* x; const float* shift; const float* v; float* y;
+    int64_t ld_x, ld_v, ld_y;
+    int32_t N, F, k, x_dtype;
+} mmvae_pca_project_args;
+int mmvae_pca_project(const mmvae_pca_project_args* args, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * AdamW (torch.optim.AdamW, constructed by the caller: optimize_hyperparameters.py:93-97,
  * train_dna2rna.py:185-189), all tensors in one launch per 64 tensors (every record is checked before the first launch).  `items_host` is an array in HOST memory
  * (device pointers inside); it is copied into the kernel arguments, so nothing is uploaded and the call is graph-capturable:

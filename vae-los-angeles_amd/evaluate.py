@@ -14,6 +14,9 @@ device (mmvae.knn).
 and neighbourhood hit (k = 5) of the standardised features [a | b] against the validation sites -- for the true features and, per
 single-target imputation route, with the target part replaced by the model's, the mean's and (with --knn) the k-NN imputations; both
 numbers are computed on the device (mmvae.clustering), one feature matrix at a time.
+--clustering-pca K adds the table's second half (its "PCA Silh | NH" columns, cluster_imputation_methods.py:140-187, 473-504): the
+same two numbers on the projection of the same standardised matrix onto its first K principal components (the reference's K is 2), and
+the share of the variance those components explain; the PCA runs on the device too (mmvae.pca).
 Routes: the directional models' one route; MultiModalVAE: a -> b, b -> a and the full (a, b, site) reconstruction.  The metrics
 are computed on the device (mmvae.metrics: one streaming launch per batch and route), nothing but 32 bytes per feature and the
 per-row vectors' aggregates reaches the host.  Evaluation runs in eval mode under no_grad; eps is still sampled (vae.py:73), so
@@ -55,6 +58,8 @@ def build_parser(kind):
     ap.add_argument("--out", default=None, help="write the table rows as JSON here")
     ap.add_argument("--clustering", action="store_true", help="add the clustering table: silhouette and neighbourhood hit (k=5) by site")
     ap.add_argument("--clustering-out", default=None, help="with --clustering: write that table's rows as JSON here")
+    ap.add_argument("--clustering-pca", type=int, default=0, metavar="K",
+                    help="with --clustering: add silhouette and neighbourhood hit of the K-component PCA projection (0 = off)")
     return ap
 
 
@@ -85,20 +90,23 @@ def print_table(rows):
 
 
 CLUSTERING_COLUMNS = ("Silhouette", "NeighborhoodHit")
+PCA_COLUMNS = ("PCASilhouette", "PCANeighborhoodHit", "PCAExplained")
 NH_K = 5
 
 
 def print_clustering_table(rows):
-    head = f"{'Features':<16}{'Model':<16}" + "".join(f"{c:>17}" for c in CLUSTERING_COLUMNS)
+    cols = CLUSTERING_COLUMNS + (PCA_COLUMNS if rows and PCA_COLUMNS[0] in rows[0] else ())
+    head = f"{'Features':<16}{'Model':<16}" + "".join(f"{c:>{max(17, len(c) + 2)}}" for c in cols)
     print(head)
     print("-" * len(head))
     for r in rows:
-        print(f"{r['Features']:<16}{r['Model']:<16}" + "".join(f"{r[c]:>17.6f}" for c in CLUSTERING_COLUMNS))
+        print(f"{r['Features']:<16}{r['Model']:<16}" + "".join(f"{r[c]:>{max(17, len(c) + 2)}.6f}" for c in cols))
 
 
-def clustering_table(entries, va, dims, B):
+def clustering_table(entries, va, dims, B, pca_k=0):
     """[(features, model name, fill)] -> table rows.  fill(i, tgt) gives the imputed rows i .. i + B of its target modality, or is None
-    for the true features.  ONE (rows, A + D) fp32 matrix is filled batch by batch, standardised, judged and reused."""
+    for the true features.  ONE (rows, A + D) fp32 matrix is filled batch by batch, standardised, judged and reused.  pca_k > 0: the
+    same two numbers on the standardised matrix's projection onto its first pca_k principal components as well."""
     from mmvae import clustering
     from mmvae._lib import SIL_MAXC
     n_val, labels = va[0].shape[0], va[2]
@@ -117,6 +125,13 @@ def clustering_table(entries, va, dims, B):
         z = clustering.standardize(feats)
         rows.append({"Features": features, "Model": model_name, "Silhouette": clustering.silhouette_score(z, labels),
                      "NeighborhoodHit": clustering.neighborhood_hit(z, labels, k=NH_K)})
+        if pca_k > 0:
+            pca = clustering.PCA(pca_k)
+            y = pca.fit_transform(z)
+            rows[-1].update({"PCASilhouette": clustering.silhouette_score(y, labels),
+                             "PCANeighborhoodHit": clustering.neighborhood_hit(y, labels, k=NH_K),
+                             "PCAExplained": float(pca.explained_variance_ratio_.sum())})
+            del y
         del z
     return rows
 
@@ -209,6 +224,11 @@ def run(kind, argv=None, return_clustering=False):
         raise SystemExit("--knn-by-site needs --knn K")
     if args.clustering_out and not args.clustering:
         raise SystemExit("--clustering-out needs --clustering")
+    if args.clustering_pca and not args.clustering:
+        raise SystemExit("--clustering-pca needs --clustering")
+    from mmvae._lib import PCA_MAXK
+    if not 0 <= args.clustering_pca <= min(PCA_MAXK, va[0].shape[0], args.input_dim_a + args.input_dim_b):
+        raise SystemExit(f"--clustering-pca {args.clustering_pca} outside [0, min({PCA_MAXK}, validation rows, features)]")
     rows = []
     for name, _, outs in plan:
         for _, tgt in outs:
@@ -236,9 +256,10 @@ def run(kind, argv=None, return_clustering=False):
                 if rtgt == tgt:
                     entries.append((route, model_name, tgt, lambda i, reg=reg, by_site=by_site, src_i=src_i:
                                     reg.predict(va[src_i][i:i + B], va[2][i:i + B]) if by_site else reg.predict(va[src_i][i:i + B])))
-        crows = clustering_table(entries, va, dims, B)
+        crows = clustering_table(entries, va, dims, B, args.clustering_pca)
     if crows:
-        print(f"clustering by site: standardised [a | b] features, silhouette and neighbourhood hit (k={NH_K})")
+        print(f"clustering by site: standardised [a | b] features, silhouette and neighbourhood hit (k={NH_K})"
+              + (f"; PCA columns: the same on the first {args.clustering_pca} principal components" if args.clustering_pca else ""))
         print_clustering_table(crows)
     if args.clustering_out:
         with open(args.clustering_out, "w") as f:

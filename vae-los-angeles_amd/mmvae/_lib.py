@@ -21,6 +21,7 @@ TILE = 128
 TN_GROUP_MAX = 8        # MMVAE_TN_GROUP_MAX
 KNN_MAXK = 64           # MMVAE_KNN_MAXK
 SIL_MAXC = 64           # MMVAE_SIL_MAXC
+PCA_MAXK = 64           # MMVAE_PCA_MAXK
 CTR_COPIES = 16384      # MMVAE_CTR_COPIES: self-advancing device counters are stored as this many identical int64 copies
 
 i32, i64, f32, vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
@@ -154,6 +155,18 @@ class SilhouetteArgs(C.Structure):
                 ("N", i32), ("F", i32), ("C", i32), ("splits", i32), ("x_dtype", i32), ("pad_", i32)]
 
 
+class PcaScatterArgs(C.Structure):
+    _fields_ = [("x", vp), ("shift", vp), ("s", vp), ("work", vp),
+                ("ld_x", i64), ("ld_s", i64), ("work_bytes", i64),
+                ("N", i32), ("F", i32), ("splits", i32), ("x_dtype", i32)]
+
+
+class PcaProjectArgs(C.Structure):
+    _fields_ = [("x", vp), ("shift", vp), ("v", vp), ("y", vp),
+                ("ld_x", i64), ("ld_v", i64), ("ld_y", i64),
+                ("N", i32), ("F", i32), ("k", i32), ("x_dtype", i32)]
+
+
 class GatherItem(C.Structure):
     _fields_ = [("src", vp), ("dst", vp), ("src_row_stride", i64), ("dst_row_stride", i64), ("row_bytes", i32), ("pad_", i32)]
 
@@ -191,6 +204,10 @@ _SIGNATURES = {
     "mmvae_silhouette_samples": [C.POINTER(SilhouetteArgs), vp],
     "mmvae_silhouette_work_bytes": [i32, i32, i32, C.POINTER(i64)],
     "mmvae_silhouette_splits": [i32, i32, i32, C.POINTER(i32)],
+    "mmvae_pca_scatter": [C.POINTER(PcaScatterArgs), vp],
+    "mmvae_pca_scatter_splits": [i32, i32, i32, C.POINTER(i32)],
+    "mmvae_pca_scatter_work_bytes": [i32, i32, i32, C.POINTER(i64)],
+    "mmvae_pca_project": [C.POINTER(PcaProjectArgs), vp],
     "mmvae_gather_rows": [vp, i32, vp, i32, i64, vp],
     "mmvae_rows_to_bf16": [vp, i32, i64, vp, i64, i32, i32, vp],
     "mmvae_sigmoid_bwd": [i32, i32, vp, i64, vp, i64, vp, i32, i64, vp],

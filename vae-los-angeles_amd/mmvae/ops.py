@@ -870,6 +870,73 @@ def silhouette_samples(x, order, class_start, shift=None, *, splits=0, s_out=Non
     return tuple(outs)
 
 
+# --------------------------------------------------------------------------------------------
+# PCA: centred scatter matrix and projection (include/mmvae_hip.h: mmvae_pca_scatter, mmvae_pca_project)
+# --------------------------------------------------------------------------------------------
+def pca_scatter_splits(N, F, splits=0):
+    """The number of row splits pca_scatter uses for these sizes and this request (mmvae_pca_scatter_splits); needs no device."""
+    ns = C.c_int32(0)
+    L.check(L.load().mmvae_pca_scatter_splits(N, F, splits, C.byref(ns)), "mmvae_pca_scatter_splits")
+    return ns.value
+
+
+def pca_scatter_work_bytes(N, F, splits=0):
+    n = C.c_int64(0)
+    L.check(L.load().mmvae_pca_scatter_work_bytes(N, F, splits, C.byref(n)), "mmvae_pca_scatter_work_bytes")
+    return n.value
+
+
+def _pca_shift(shift, F, dev, what):
+    if shift is not None and (not isinstance(shift, torch.Tensor) or not shift.is_cuda or shift.dtype != torch.float32
+                              or tuple(shift.shape) != (F,) or not shift.is_contiguous() or shift.device != dev):
+        raise ValueError(f"{what}: shift must be a contiguous fp32 ({F},) tensor on x's device")
+
+
+def _pca_out(out, rows, cols, dev, what):
+    if out is None:
+        return torch.empty(rows, cols, dtype=torch.float32, device=dev)
+    if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != (rows, cols) or out.stride(1) != 1 \
+            or (rows > 1 and out.stride(0) < cols) or out.device != dev:
+        raise ValueError(f"{what}: out must be an fp32 ({rows}, {cols}) tensor on x's device with unit inner stride")
+    return out
+
+
+def pca_scatter(x, shift, splits=0, out=None):
+    """S = (x - shift)^T (x - shift), fp32 (F, F), bitwise symmetric (mmvae_pca_scatter).  x (N, F): fp32 or bf16, unit inner stride, any
+    row stride (padded bf16 rows included); shift (F,) fp32 or None is subtracted from every element on load (pass the column means).
+    splits: 0 = the library's choice, 1 .. 64 forces that many row splits.  out: write into this (a view is allowed)."""
+    x_ptr, x_dt, x_ld = _knn_operand(x, "x")
+    N, F = x.shape
+    _pca_shift(shift, F, x.device, "pca_scatter")
+    splits = int(splits)
+    if not 0 <= splits <= 64:
+        raise ValueError(f"pca_scatter: splits = {splits} outside [0, 64]")
+    s = _pca_out(out, F, F, x.device, "pca_scatter")
+    nbytes = pca_scatter_work_bytes(N, F, splits)
+    work = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=x.device) if nbytes else None
+    a = L.PcaScatterArgs(x_ptr, _p(shift), s.data_ptr(), _p(work), x_ld, _ld(s), nbytes, N, F, splits, x_dt)
+    with probe_span("pca_scatter", lambda: dict(kind="gemm", flops=1.0 * N * F * F, M=F, N=F, K=N)):
+        L.check(L.load().mmvae_pca_scatter(C.byref(a), _stream()), "mmvae_pca_scatter")
+    return s
+
+
+def pca_project(x, shift, v, out=None):
+    """y = (x - shift) v^T, fp32 (N, k) (mmvae_pca_project).  x, shift as pca_scatter; v (k, F) fp32 with unit inner stride,
+    1 <= k <= PCA_MAXK.  A row of y depends on that row of x, shift and v alone."""
+    x_ptr, x_dt, x_ld = _knn_operand(x, "x")
+    N, F = x.shape
+    _pca_shift(shift, F, x.device, "pca_project")
+    v_ptr, v_dt, v_ld = _knn_operand(v, "v", F)
+    k = v.shape[0]
+    if v.dtype != torch.float32 or not 1 <= k <= L.PCA_MAXK or v.device != x.device:
+        raise ValueError(f"pca_project: v must be an fp32 (1 <= k <= {L.PCA_MAXK}, {F}) tensor on x's device, got {tuple(v.shape)} {v.dtype}")
+    y = _pca_out(out, N, k, x.device, "pca_project")
+    a = L.PcaProjectArgs(x_ptr, _p(shift), v_ptr, y.data_ptr(), x_ld, v_ld, _ld(y), N, F, k, x_dt)
+    with probe_span("pca_project", lambda: dict(kind="gemm", flops=2.0 * N * F * k, M=N, N=k, K=F)):
+        L.check(L.load().mmvae_pca_project(C.byref(a), _stream()), "mmvae_pca_project")
+    return y
+
+
 def adamw_step(items, lr, b1, b2, eps, wd, bc1, bc2, maximize=False, step_dev=None, lr_dev=None):
     """items: ctypes array of AdamWItem in host memory (device pointers inside).  step_dev: int64[CTR_COPIES] tensor of
     identical copies of the step count: bias corrections from the device counter, which the launch itself increments
