@@ -13,37 +13,13 @@ pytestmark = pytest.mark.gpu
 
 import knn_bounds as KB  # noqa: E402
 import knn_ref as KR  # noqa: E402
-from mmvae import ops, to_bf16_rows  # noqa: E402
+from mmvae import ops  # noqa: E402
 from mmvae.knn import ConditionedKNeighborsRegressor, KNeighborsRegressor, neighborhood_hit  # noqa: E402
+from rowmat_gpu_util import in_nan_frame, operand  # noqa: E402
 
 DEV = "cuda"
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "knn_baselines.npz")
 SENTINEL_I, SENTINEL_F = -77, -7.0
-
-
-def in_nan_frame(x, top, left, right, dtype=torch.float32):
-    """x (numpy (M, F) float32) as a device view of a wider and taller NaN-filled buffer"""
-    M, F = x.shape
-    buf = torch.full((M + top + 1, left + F + right), float("nan"), dtype=dtype, device=DEV)
-    view = buf[top:top + M, left:left + F]
-    view.copy_(torch.from_numpy(x).to(DEV))
-    return view
-
-
-def bf16_rows_nan_pads(x):
-    """padded bf16 rows of x with the pad columns overwritten by NaN"""
-    t = to_bf16_rows(torch.from_numpy(x).to(DEV))
-    ld = t.stride(0)
-    if ld > t.shape[1]:
-        torch.as_strided(t, (t.shape[0], ld - t.shape[1]), (ld, 1), t.storage_offset() + t.shape[1]).fill_(float("nan"))
-    return t
-
-
-def operand(x, bf16, left):
-    """left 8: rows on 16-byte boundaries (padded bf16 rows / a frame 64 elements wide); left 7: rows aligned to one element only"""
-    if bf16:
-        return bf16_rows_nan_pads(x) if left == 8 else in_nan_frame(x, 2, left, 3, torch.bfloat16)
-    return in_nan_frame(x, 2, left, 64 - (left + x.shape[1]) % 64 if left == 8 else 3)
 
 
 def f64(t):

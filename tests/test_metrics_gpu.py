@@ -13,6 +13,7 @@ import metrics_bounds as MB  # noqa: E402
 import metrics_ref as MR  # noqa: E402
 from mmvae import _lib, ops, to_bf16_rows  # noqa: E402
 from mmvae.metrics import ImputationMetrics, imputation_metrics  # noqa: E402
+from rowmat_gpu_util import bf16_rows_nan_pads, in_nan_frame  # noqa: E402
 
 DEV = "cuda"
 
@@ -26,24 +27,6 @@ def make(M, F, seed, specials=True):
         y[1] = 0.5
         p[M - 2] = 0.0
     return y, p
-
-
-def in_nan_frame(x, top, left, right, dtype=torch.float32):
-    """x (numpy (M, F)) as a device view of a wider and taller NaN-filled buffer: `left` / `right` NaN columns, `top` NaN rows"""
-    M, F = x.shape
-    buf = torch.full((M + top + 1, left + F + right), float("nan"), dtype=dtype, device=DEV)
-    view = buf[top:top + M, left:left + F]
-    view.copy_(torch.from_numpy(x).to(DEV))
-    return view
-
-
-def bf16_rows_nan_pads(x):
-    """padded bf16 rows of x with the pad columns overwritten by NaN: the kernel must not read them as data"""
-    t = to_bf16_rows(torch.from_numpy(x).to(DEV))
-    ld = t.stride(0)
-    if ld > t.shape[1]:
-        torch.as_strided(t, (t.shape[0], ld - t.shape[1]), (ld, 1), t.storage_offset() + t.shape[1]).fill_(float("nan"))
-    return t
 
 
 def f64(t):

@@ -12,36 +12,11 @@ pytestmark = pytest.mark.gpu
 
 import silhouette_bounds as SB  # noqa: E402
 import silhouette_ref as SR  # noqa: E402
-from mmvae import _lib, clustering, ops, to_bf16_rows  # noqa: E402
+from mmvae import _lib, clustering, ops  # noqa: E402
+from rowmat_gpu_util import operand  # noqa: E402
 
 DEV = "cuda"
 SENTINEL = -7.0
-
-
-def in_nan_frame(x, top, left, right, dtype=torch.float32):
-    """x (numpy (N, F) float32) as a device view of a wider and taller NaN-filled buffer"""
-    N, F = x.shape
-    buf = torch.full((N + top + 1, left + F + right), float("nan"), dtype=dtype, device=DEV)
-    view = buf[top:top + N, left:left + F]
-    view.copy_(torch.from_numpy(x).to(DEV))
-    return view
-
-
-def bf16_rows_nan_pads(x):
-    """padded bf16 rows of x with the pad columns overwritten by NaN"""
-    t = to_bf16_rows(torch.from_numpy(x).to(DEV))
-    ld = t.stride(0)
-    if ld > t.shape[1]:
-        torch.as_strided(t, (t.shape[0], ld - t.shape[1]), (ld, 1), t.storage_offset() + t.shape[1]).fill_(float("nan"))
-    return t
-
-
-def operand(x, bf16, left):
-    """left 8: rows on 16-byte boundaries (padded bf16 rows / a frame whose width is a multiple of 64); left 7: rows aligned to one
-    element only"""
-    if bf16:
-        return bf16_rows_nan_pads(x) if left == 8 else in_nan_frame(x, 2, left, 3, torch.bfloat16)
-    return in_nan_frame(x, 2, left, 64 - (left + x.shape[1]) % 64 if left == 8 else 3)
 
 
 def _dev(a, dtype=None):

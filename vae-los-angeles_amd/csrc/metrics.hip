@@ -183,7 +183,8 @@ __global__ __launch_bounds__(MET_THREADS) __attribute__((amdgpu_waves_per_eu(4, 
     }
 }
 
-// elements per vector load (at most 16 bytes) that the base address and the leading dimension allow
+// elements per vector load (at most 16 bytes) that the base address and the leading dimension allow.  Not row_tile.h's rt_vec, which
+// stops at 4 elements: bf16 rows may answer 8 here (met_load takes any answer >= 4 as 4).
 static int met_vec(const void* p, long ld, int esize) {
     for (int v = 16 / esize; v > 1; v >>= 1)
         if (ld % v == 0 && ((uintptr_t)p % (uintptr_t)(v * esize)) == 0) return v;

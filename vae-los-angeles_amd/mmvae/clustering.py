@@ -13,7 +13,7 @@ import torch
 
 from . import _lib as L
 from . import ops
-from .knn import _column_means, _device_matrix, neighborhood_hit  # noqa: F401  (neighborhood_hit: re-exported)
+from .knn import neighborhood_hit  # noqa: F401  (neighborhood_hit: re-exported)
 from .pca import PCA  # noqa: F401  (re-exported: the table's PCA columns)
 
 __all__ = ["silhouette_samples", "silhouette_score", "standardize", "neighborhood_hit", "PCA"]
@@ -42,9 +42,9 @@ def silhouette_samples(X, labels, metric="euclidean"):
         raise ValueError(f"metric={metric!r}: only 'euclidean' is implemented")
     if not isinstance(X, torch.Tensor) or not X.is_cuda:
         raise RuntimeError("mmvae.clustering: X must be a CUDA/HIP tensor; there is no CPU fallback")
-    X = _device_matrix(X, "X")
+    X = ops._device_matrix(X, "X", "mmvae.clustering")
     order, class_start = _encode(labels, X.shape[0], X.device)
-    return ops.silhouette_samples(X, order, class_start, _column_means(X))[0]
+    return ops.silhouette_samples(X, order, class_start, ops._column_means(X))[0]
 
 
 def silhouette_score(X, labels, metric="euclidean"):

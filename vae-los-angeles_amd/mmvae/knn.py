@@ -25,18 +25,7 @@ def _check_kind(weights, metric):
 
 
 def _device_matrix(t, name):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"mmvae.knn: {name} must be a CUDA/HIP tensor; there is no CPU fallback")
-    if t.dim() == 1:
-        t = t.unsqueeze(1)
-    if t.dim() != 2 or t.dtype not in (torch.float32, torch.bfloat16):
-        raise ValueError(f"mmvae.knn: {name} must be a 2-D fp32 or bf16 tensor, got {tuple(t.shape)} {t.dtype}")
-    t = t.detach()
-    return t if t.stride(1) == 1 and (t.shape[0] <= 1 or t.stride(0) >= t.shape[1]) else t.contiguous()
-
-
-def _column_means(x):
-    return x.double().mean(dim=0).float().contiguous()
+    return ops._device_matrix(t, name, "mmvae.knn")
 
 
 class KNeighborsRegressor:
@@ -54,7 +43,7 @@ class KNeighborsRegressor:
             raise ValueError(f"fit: X {tuple(X.shape)} against Y {tuple(Y.shape)}")
         if self.n_neighbors > X.shape[0]:
             raise ValueError(f"n_neighbors={self.n_neighbors} > {X.shape[0]} training rows")       # sklearn raises at predict
-        self.X, self.Y, self.shift = X, Y, _column_means(X)
+        self.X, self.Y, self.shift = X, Y, ops._column_means(X)
         return self
 
     def kneighbors(self, Xq, dist2=True):
@@ -128,6 +117,6 @@ def neighborhood_hit(features, labels, k=5):
     labels = torch.as_tensor(labels).to(features.device)
     if labels.dim() != 1 or labels.shape[0] != features.shape[0]:
         raise ValueError(f"labels must be ({features.shape[0]},)")
-    idx, _ = ops.knn_search(features, features, k + 1, _column_means(features), dist2=False)
+    idx, _ = ops.knn_search(features, features, k + 1, ops._column_means(features), dist2=False)
     hits = labels[idx[:, 1:].long()] == labels[:, None]
     return float(hits.double().mean(dim=1).mean())

@@ -128,6 +128,22 @@ def _ld(t):
     return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
 
 
+def _device_matrix(t, name, what):
+    """t as a 2-D fp32 / bf16 device matrix the kernels can read in place (a 1-D tensor is one column); `what` names the caller"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"{what}: {name} must be a CUDA/HIP tensor; there is no CPU fallback")
+    if t.dim() == 1:
+        t = t.unsqueeze(1)
+    if t.dim() != 2 or t.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"{what}: {name} must be a 2-D fp32 or bf16 tensor, got {tuple(t.shape)} {t.dtype}")
+    t = t.detach()
+    return t if t.stride(1) == 1 and (t.shape[0] <= 1 or t.stride(0) >= t.shape[1]) else t.contiguous()
+
+
+def _column_means(x):
+    return x.double().mean(dim=0).float().contiguous()
+
+
 # --------------------------------------------------------------------------------------------
 # inputs in bf16 storage ("padded bf16 rows", include/mmvae_hip.h: mmvae_rows_to_bf16)
 # --------------------------------------------------------------------------------------------
@@ -736,31 +752,75 @@ def recon_metrics(pred, target, col_shift, col_acc, row_pearson, row_cosine):
 
 
 # --------------------------------------------------------------------------------------------
-# k nearest neighbours (include/mmvae_hip.h: mmvae_knn_search, mmvae_knn_mean_rows)
+# what the wrappers of the row-tile kernels share (k-NN, silhouette, PCA below): operand, vector, output and workspace checks
 # --------------------------------------------------------------------------------------------
-def _knn_operand(t, name, F=None):
+def _rows_operand(t, name, what, F=None):
     """(pointer, dtype, leading dimension) of a (rows, F) fp32 / bf16 device matrix with unit inner stride and rows that do not overlap."""
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"knn: {name} must be a CUDA/HIP tensor; there is no CPU fallback")
+        raise RuntimeError(f"{what}: {name} must be a CUDA/HIP tensor; there is no CPU fallback")
     _mat(t, name)
     if t.dtype not in (torch.float32, torch.bfloat16):
-        raise ValueError(f"knn: {name} must be fp32 or bf16, got {t.dtype}")
+        raise ValueError(f"{what}: {name} must be fp32 or bf16, got {t.dtype}")
     if t.shape[0] < 1 or t.shape[1] < 1 or (F is not None and t.shape[1] != F) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
-        raise ValueError(f"knn: {name} is {tuple(t.shape)} / {t.stride()}, need (rows >= 1, {F if F is not None else 'F >= 1'}) rows that do not overlap")
+        raise ValueError(f"{what}: {name} is {tuple(t.shape)} / {t.stride()}, need (rows >= 1, {F if F is not None else 'F >= 1'}) rows that do not overlap")
     return t.data_ptr(), _dt(t), _ld(t)
 
 
+def _vector(t, name, what, dt, n, dev, strided=False):
+    """t, a `dt` (n,) tensor on `dev`: contiguous, or (strided) a view with unit stride"""
+    ok = isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and tuple(t.shape) == (n,) and t.device == dev
+    if ok and strided:
+        ok = n <= 1 or t.stride(0) == 1
+    elif ok:
+        ok = t.is_contiguous()
+    if not ok:
+        raise ValueError(f"{what}: {name} must be a {'' if strided else 'contiguous '}{dt} ({n},) tensor on the operand's device")
+    return t
+
+
+def _shift(shift, what, F, dev):
+    return None if shift is None else _vector(shift, "shift", what, torch.float32, F, dev)
+
+
+def _out_view(out, name, what, dt, rows, cols, dev):
+    """`out`, a `dt` (rows, cols) tensor on `dev` with unit inner stride (a view is allowed), or a new one"""
+    if out is None:
+        return torch.empty(rows, cols, dtype=dt, device=dev)
+    if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != dt or tuple(out.shape) != (rows, cols) or out.stride(1) != 1 \
+            or (rows > 1 and out.stride(0) < cols) or out.device != dev:
+        raise ValueError(f"{what}: {name} must be a {dt} ({rows}, {cols}) tensor on the operand's device with unit inner stride")
+    return out
+
+
+def _workspace(nbytes, dev):
+    """8-byte aligned device scratch of at least nbytes; None for 0"""
+    return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev) if nbytes else None
+
+
+def _plan(symbol, *args, outs=(C.c_int32,)):
+    """The answer(s) of a planning entry point (`*_splits`, `*_work_bytes`: sizes in, integers out; needs no device)."""
+    vals = [t(0) for t in outs]
+    L.check(getattr(L.load(), symbol)(*args, *(C.byref(v) for v in vals)), symbol)
+    return vals[0].value if len(vals) == 1 else tuple(v.value for v in vals)
+
+
+def _splits_arg(splits, what):
+    splits = int(splits)
+    if not 0 <= splits <= 64:
+        raise ValueError(f"{what}: splits = {splits} outside [0, 64]")
+    return splits
+
+
+# --------------------------------------------------------------------------------------------
+# k nearest neighbours (include/mmvae_hip.h: mmvae_knn_search, mmvae_knn_mean_rows)
+# --------------------------------------------------------------------------------------------
 def knn_splits(Mq, Nt):
     """(splits, training rows per split) of the decomposition knn_search uses for these sizes (mmvae_knn_splits); needs no device."""
-    ns, rps = C.c_int32(0), C.c_int32(0)
-    L.check(L.load().mmvae_knn_splits(Mq, Nt, C.byref(ns), C.byref(rps)), "mmvae_knn_splits")
-    return ns.value, rps.value
+    return _plan("mmvae_knn_splits", Mq, Nt, outs=(C.c_int32, C.c_int32))
 
 
 def knn_work_bytes(Mq, Nt, k):
-    n = C.c_int64(0)
-    L.check(L.load().mmvae_knn_work_bytes(Mq, Nt, k, C.byref(n)), "mmvae_knn_work_bytes")
-    return n.value
+    return _plan("mmvae_knn_work_bytes", Mq, Nt, k, outs=(C.c_int64,))
 
 
 def knn_search(q, t, k, shift=None, dist2=True, *, idx_out=None, dist2_out=None):
@@ -768,24 +828,19 @@ def knn_search(q, t, k, shift=None, dist2=True, *, idx_out=None, dist2_out=None)
     training index), and the squared distances fp32 (Mq, k) unless dist2 is False (then None).  q (Mq, F), t (Nt, F): fp32 or bf16,
     unit inner stride, any row stride (padded bf16 rows included).  shift (F,) fp32 is subtracted from both operands on load (pass the
     training column means: the distances do not change, their rounding does).  idx_out / dist2_out: write into these (views allowed)."""
-    q_ptr, q_dt, q_ld = _knn_operand(q, "q")
+    q_ptr, q_dt, q_ld = _rows_operand(q, "q", "knn_search")
     Mq, F = q.shape
-    t_ptr, t_dt, t_ld = _knn_operand(t, "t", F)
+    t_ptr, t_dt, t_ld = _rows_operand(t, "t", "knn_search", F)
     Nt = t.shape[0]
     k = int(k)
     if not 1 <= k <= min(Nt, L.KNN_MAXK):
         raise ValueError(f"knn_search: k = {k} outside [1, min({Nt} training rows, {L.KNN_MAXK})]")
-    if shift is not None and (not shift.is_cuda or shift.dtype != torch.float32 or tuple(shift.shape) != (F,) or not shift.is_contiguous()):
-        raise ValueError(f"knn_search: shift must be a contiguous fp32 ({F},) device tensor")
-    idx = torch.empty(Mq, k, dtype=torch.int32, device=q.device) if idx_out is None else idx_out
-    d2 = (torch.empty(Mq, k, dtype=torch.float32, device=q.device) if dist2_out is None else dist2_out) if dist2 else None
-    for o, name, dt in ((idx, "idx_out", torch.int32), (d2, "dist2_out", torch.float32)):
-        if o is not None and (not o.is_cuda or o.dtype != dt or tuple(o.shape) != (Mq, k) or o.stride(1) != 1 or (Mq > 1 and o.stride(0) < k)):
-            raise ValueError(f"knn_search: {name} must be a {dt} ({Mq}, {k}) device tensor with unit inner stride")
-    if len({x.device for x in (q, t, idx) + ((shift,) if shift is not None else ()) + ((d2,) if d2 is not None else ())}) != 1:
+    if t.device != q.device:
         raise ValueError("knn_search: all operands must live on one device")
-    nbytes = knn_work_bytes(Mq, Nt, k)
-    work = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=q.device)
+    shift = _shift(shift, "knn_search", F, q.device)
+    idx = _out_view(idx_out, "idx_out", "knn_search", torch.int32, Mq, k, q.device)
+    d2 = _out_view(dist2_out, "dist2_out", "knn_search", torch.float32, Mq, k, q.device) if dist2 else None
+    work = _workspace(knn_work_bytes(Mq, Nt, k), q.device)
     a = L.KnnArgs(q_ptr, t_ptr, _p(shift), idx.data_ptr(), _p(d2), work.data_ptr(), q_ld, t_ld, _ld(idx), _ld(d2) if d2 is not None else 0,
                   work.numel() * 8, Mq, Nt, F, k, q_dt, t_dt)
     with probe_span("knn_search", lambda: dict(kind="gemm", flops=2.0 * Mq * Nt * F, M=Mq, N=Nt, K=F)):
@@ -796,18 +851,15 @@ def knn_search(q, t, k, shift=None, dist2=True, *, idx_out=None, dist2_out=None)
 def knn_mean_rows(idx, y, out=None):
     """out[i] = mean over n of y[idx[i][n]] in fp32, summed in ascending n (mmvae_knn_mean_rows): uniform k-NN regression.
     idx int32 (Mq, k), y (Ny, Fy) fp32 or bf16, out fp32 (Mq, Fy); indices outside [0, Ny) are clamped."""
-    y_ptr, y_dt, y_ld = _knn_operand(y, "y")
+    y_ptr, y_dt, y_ld = _rows_operand(y, "y", "knn_mean_rows")
     if not isinstance(idx, torch.Tensor) or not idx.is_cuda or idx.dtype != torch.int32 or idx.dim() != 2 or idx.stride(1) != 1 or idx.shape[0] < 1 \
             or not 1 <= idx.shape[1] <= L.KNN_MAXK:
         raise ValueError(f"knn_mean_rows: idx must be an int32 (Mq, 1 <= k <= {L.KNN_MAXK}) device tensor with unit inner stride")
     Mq, k = idx.shape
     Ny, Fy = y.shape
-    if out is None:
-        out = torch.empty(Mq, Fy, dtype=torch.float32, device=y.device)
-    if not out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != (Mq, Fy) or out.stride(1) != 1 or (Mq > 1 and out.stride(0) < Fy):
-        raise ValueError(f"knn_mean_rows: out must be an fp32 ({Mq}, {Fy}) device tensor with unit inner stride")
-    if len({idx.device, y.device, out.device}) != 1:
+    if idx.device != y.device:
         raise ValueError("knn_mean_rows: all operands must live on one device")
+    out = _out_view(out, "out", "knn_mean_rows", torch.float32, Mq, Fy, y.device)
     with stream_span("knn_mean_rows", Mq * k * (4 + Fy * y.element_size()) + 4 * Mq * Fy):
         L.check(L.load().mmvae_knn_mean_rows(idx.data_ptr(), _ld(idx), y_ptr, y_dt, y_ld, out.data_ptr(), _ld(out), Mq, k, Ny, Fy, _stream()),
                 "mmvae_knn_mean_rows")
@@ -819,15 +871,11 @@ def knn_mean_rows(idx, y, out=None):
 # --------------------------------------------------------------------------------------------
 def silhouette_splits(N, n_classes, splits=0):
     """The number of column splits silhouette_samples uses for these sizes and this request (mmvae_silhouette_splits); needs no device."""
-    ns = C.c_int32(0)
-    L.check(L.load().mmvae_silhouette_splits(N, n_classes, splits, C.byref(ns)), "mmvae_silhouette_splits")
-    return ns.value
+    return _plan("mmvae_silhouette_splits", N, n_classes, splits)
 
 
 def silhouette_work_bytes(N, n_classes, splits=0):
-    n = C.c_int64(0)
-    L.check(L.load().mmvae_silhouette_work_bytes(N, n_classes, splits, C.byref(n)), "mmvae_silhouette_work_bytes")
-    return n.value
+    return _plan("mmvae_silhouette_work_bytes", N, n_classes, splits, outs=(C.c_int64,))
 
 
 def silhouette_samples(x, order, class_start, shift=None, *, splits=0, s_out=None, intra_out=None, inter_out=None):
@@ -836,33 +884,23 @@ def silhouette_samples(x, order, class_start, shift=None, *, splits=0, s_out=Non
     class, or None when the rows are already grouped; class_start: int32 (C + 1,) positions, class c owns order[class_start[c] :
     class_start[c + 1]].  shift (F,) fp32 is subtracted from every element on load (pass the column means).  splits: 0 = the library's
     choice, 1 .. 64 forces that many column splits.  *_out: write into these (views allowed)."""
-    x_ptr, x_dt, x_ld = _knn_operand(x, "x")
+    what = "silhouette_samples"
+    x_ptr, x_dt, x_ld = _rows_operand(x, "x", what)
     N, F = x.shape
     dev = x.device
-
-    def vec(t, name, dt, n, stride1=False):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt or tuple(t.shape) != (n,) or (not stride1 and not t.is_contiguous()) \
-                or (stride1 and n > 1 and t.stride(0) != 1) or t.device != dev:
-            raise ValueError(f"silhouette_samples: {name} must be a {'' if stride1 else 'contiguous '}{dt} ({n},) tensor on x's device")
-        return t
-
     if not isinstance(class_start, torch.Tensor) or class_start.dim() != 1:
         raise ValueError("silhouette_samples: class_start must be an int32 (C + 1,) device tensor")
     nc = class_start.shape[0] - 1
     if N < 2 or not 1 <= nc <= L.SIL_MAXC:
         raise ValueError(f"silhouette_samples: N = {N}, C = {nc} outside N >= 2, 1 <= C <= {L.SIL_MAXC}")
-    vec(class_start, "class_start", torch.int32, nc + 1)
+    _vector(class_start, "class_start", what, torch.int32, nc + 1, dev)
     if order is not None:
-        vec(order, "order", torch.int32, N)
-    if shift is not None:
-        vec(shift, "shift", torch.float32, F)
-    splits = int(splits)
-    if not 0 <= splits <= 64:
-        raise ValueError(f"silhouette_samples: splits = {splits} outside [0, 64]")
-    outs = [vec(torch.empty(N, dtype=torch.float32, device=dev) if o is None else o, name, torch.float32, N, stride1=True)
+        _vector(order, "order", what, torch.int32, N, dev)
+    shift = _shift(shift, what, F, dev)
+    splits = _splits_arg(splits, what)
+    outs = [_vector(torch.empty(N, dtype=torch.float32, device=dev) if o is None else o, name, what, torch.float32, N, dev, strided=True)
             for o, name in ((s_out, "s_out"), (intra_out, "intra_out"), (inter_out, "inter_out"))]
-    nbytes = silhouette_work_bytes(N, nc, splits)
-    work = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    work = _workspace(silhouette_work_bytes(N, nc, splits), dev)
     a = L.SilhouetteArgs(x_ptr, _p(shift), _p(order), class_start.data_ptr(), outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(),
                          work.data_ptr(), x_ld, work.numel() * 8, N, F, nc, splits, x_dt, 0)
     with probe_span("silhouette_samples", lambda: dict(kind="gemm", flops=2.0 * N * N * F, M=N, N=N, K=F)):
@@ -875,45 +913,24 @@ def silhouette_samples(x, order, class_start, shift=None, *, splits=0, s_out=Non
 # --------------------------------------------------------------------------------------------
 def pca_scatter_splits(N, F, splits=0):
     """The number of row splits pca_scatter uses for these sizes and this request (mmvae_pca_scatter_splits); needs no device."""
-    ns = C.c_int32(0)
-    L.check(L.load().mmvae_pca_scatter_splits(N, F, splits, C.byref(ns)), "mmvae_pca_scatter_splits")
-    return ns.value
+    return _plan("mmvae_pca_scatter_splits", N, F, splits)
 
 
 def pca_scatter_work_bytes(N, F, splits=0):
-    n = C.c_int64(0)
-    L.check(L.load().mmvae_pca_scatter_work_bytes(N, F, splits, C.byref(n)), "mmvae_pca_scatter_work_bytes")
-    return n.value
-
-
-def _pca_shift(shift, F, dev, what):
-    if shift is not None and (not isinstance(shift, torch.Tensor) or not shift.is_cuda or shift.dtype != torch.float32
-                              or tuple(shift.shape) != (F,) or not shift.is_contiguous() or shift.device != dev):
-        raise ValueError(f"{what}: shift must be a contiguous fp32 ({F},) tensor on x's device")
-
-
-def _pca_out(out, rows, cols, dev, what):
-    if out is None:
-        return torch.empty(rows, cols, dtype=torch.float32, device=dev)
-    if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != (rows, cols) or out.stride(1) != 1 \
-            or (rows > 1 and out.stride(0) < cols) or out.device != dev:
-        raise ValueError(f"{what}: out must be an fp32 ({rows}, {cols}) tensor on x's device with unit inner stride")
-    return out
+    return _plan("mmvae_pca_scatter_work_bytes", N, F, splits, outs=(C.c_int64,))
 
 
 def pca_scatter(x, shift, splits=0, out=None):
     """S = (x - shift)^T (x - shift), fp32 (F, F), bitwise symmetric (mmvae_pca_scatter).  x (N, F): fp32 or bf16, unit inner stride, any
     row stride (padded bf16 rows included); shift (F,) fp32 or None is subtracted from every element on load (pass the column means).
     splits: 0 = the library's choice, 1 .. 64 forces that many row splits.  out: write into this (a view is allowed)."""
-    x_ptr, x_dt, x_ld = _knn_operand(x, "x")
+    x_ptr, x_dt, x_ld = _rows_operand(x, "x", "pca_scatter")
     N, F = x.shape
-    _pca_shift(shift, F, x.device, "pca_scatter")
-    splits = int(splits)
-    if not 0 <= splits <= 64:
-        raise ValueError(f"pca_scatter: splits = {splits} outside [0, 64]")
-    s = _pca_out(out, F, F, x.device, "pca_scatter")
+    shift = _shift(shift, "pca_scatter", F, x.device)
+    splits = _splits_arg(splits, "pca_scatter")
+    s = _out_view(out, "out", "pca_scatter", torch.float32, F, F, x.device)
     nbytes = pca_scatter_work_bytes(N, F, splits)
-    work = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=x.device) if nbytes else None
+    work = _workspace(nbytes, x.device)
     a = L.PcaScatterArgs(x_ptr, _p(shift), s.data_ptr(), _p(work), x_ld, _ld(s), nbytes, N, F, splits, x_dt)
     with probe_span("pca_scatter", lambda: dict(kind="gemm", flops=1.0 * N * F * F, M=F, N=F, K=N)):
         L.check(L.load().mmvae_pca_scatter(C.byref(a), _stream()), "mmvae_pca_scatter")
@@ -923,14 +940,14 @@ def pca_scatter(x, shift, splits=0, out=None):
 def pca_project(x, shift, v, out=None):
     """y = (x - shift) v^T, fp32 (N, k) (mmvae_pca_project).  x, shift as pca_scatter; v (k, F) fp32 with unit inner stride,
     1 <= k <= PCA_MAXK.  A row of y depends on that row of x, shift and v alone."""
-    x_ptr, x_dt, x_ld = _knn_operand(x, "x")
+    x_ptr, x_dt, x_ld = _rows_operand(x, "x", "pca_project")
     N, F = x.shape
-    _pca_shift(shift, F, x.device, "pca_project")
-    v_ptr, v_dt, v_ld = _knn_operand(v, "v", F)
+    shift = _shift(shift, "pca_project", F, x.device)
+    v_ptr, v_dt, v_ld = _rows_operand(v, "v", "pca_project", F)
     k = v.shape[0]
     if v.dtype != torch.float32 or not 1 <= k <= L.PCA_MAXK or v.device != x.device:
         raise ValueError(f"pca_project: v must be an fp32 (1 <= k <= {L.PCA_MAXK}, {F}) tensor on x's device, got {tuple(v.shape)} {v.dtype}")
-    y = _pca_out(out, N, k, x.device, "pca_project")
+    y = _out_view(out, "out", "pca_project", torch.float32, N, k, x.device)
     a = L.PcaProjectArgs(x_ptr, _p(shift), v_ptr, y.data_ptr(), x_ld, v_ld, _ld(y), N, F, k, x_dt)
     with probe_span("pca_project", lambda: dict(kind="gemm", flops=2.0 * N * F * k, M=N, N=k, K=F)):
         L.check(L.load().mmvae_pca_project(C.byref(a), _stream()), "mmvae_pca_project")

@@ -14,7 +14,6 @@ import torch
 
 from . import _lib as L
 from . import ops
-from .knn import _column_means, _device_matrix
 
 __all__ = ["PCA"]
 
@@ -36,14 +35,14 @@ class PCA:
         self.mean_ = self.components_ = None
 
     def fit(self, X):
-        X = _device_matrix(X, "X")
+        X = ops._device_matrix(X, "X", "mmvae.pca")
         N, F = X.shape
         k = self.n_components
         if N < 2:
             raise ValueError(f"PCA needs at least 2 samples, got n_samples={N}")
         if k > min(N, F):
             raise ValueError(f"n_components={k} must be between 0 and min(n_samples, n_features)={min(N, F)} with svd_solver='full'")
-        self.mean_ = _column_means(X)
+        self.mean_ = ops._column_means(X)
         S = ops.pca_scatter(X, self.mean_)
         lam, vec = torch.linalg.eigh(S.double())            # ascending
         lam = lam.clamp_min(0.0).flip(0)[:k]
@@ -61,7 +60,7 @@ class PCA:
     def transform(self, X):
         if self.components_ is None:
             raise RuntimeError("transform() before fit()")
-        X = _device_matrix(X, "X")
+        X = ops._device_matrix(X, "X", "mmvae.pca")
         if X.shape[1] != self.n_features_in_:
             raise ValueError(f"X has {X.shape[1]} features, PCA was fitted with {self.n_features_in_}")
         return ops.pca_project(X, self.mean_, self.components_)
