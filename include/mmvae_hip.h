@@ -487,12 +487,13 @@ int mmvae_recon_metrics(const mmvae_metrics_args* args, void* stream);
  * alone gives too few workgroups, the training rows are split across workgroups (mmvae_knn_splits says how), the partial lists go to
  * `work` and a second small launch merges them.  work: caller-owned, 8-byte aligned, at least mmvae_knn_work_bytes(Mq, Nt, k) bytes
  * = 4 (Mq + Nt) for the rows' squared norms (one more streaming launch) + 8 Mq k splits when split; the library allocates nothing.
- * Limits: Mq, Nt, F >= 1 (any F); 1 <= k <= min(Nt, MMVAE_KNN_MAXK); row offsets are 64-bit.
+ * Limits: Mq, Nt, F >= 1 (any F); 1 <= k <= min(Nt, MMVAE_KNN_MAXK); row offsets are 64-bit.  MMVAE_KNN_MAXK = 96 covers the 92 of t-SNE at
+ *   perplexity 30 (91 neighbours and the row itself); a row's list takes k rounded up to 16 entries of LDS, so k <= 64 runs as it did at 64.
  * MMVAE_ERR_ARG (nothing enqueued): a null struct, null q / t / idx / work, a size < 1, k out of range, a leading dimension below its
  *   width, a pointer not aligned to its element (work: 8 bytes), work_bytes below mmvae_knn_work_bytes.  MMVAE_ERR_DTYPE: a dtype
  *   that is neither MMVAE_F32 nor MMVAE_BF16.
  * ------------------------------------------------------------------------------------------- */
-#define MMVAE_KNN_MAXK 64
+#define MMVAE_KNN_MAXK 96
 typedef struct {
     const void* q; const void* t; const float* shift;
     int32_t* idx; float* dist2; void* work;
@@ -621,6 +622,89 @@ typedef struct {
     int32_t N, F, k, x_dtype;
 } mmvae_pca_project_args;
 int mmvae_pca_project(const mmvae_pca_project_args* args, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * t-SNE in two dimensions with the exact all-pairs repulsion (tsne.hip): sklearn's TSNE(2, method="barnes_hut") at angle = 0 -- the
+ * sparse P of the int(3 perplexity + 1) nearest neighbours, every pair in the repulsion -- with no tree.  Replaces
+ * TSNE(n_components=2, random_state=42, perplexity=min(30, n - 1)) over host copies
+ * (src/clustering_evaluation/cluster_imputation_methods.py:140-187).  fp32 throughout, no atomics; every sum has one fixed order, so
+ * the same arguments and split count give the same bits.  The neighbour search in front is mmvae_knn_search, the symmetrisation of P
+ * (a sort of 64-bit keys) is the caller's.
+ *
+ * mmvae_tsne_affinities: sklearn's _binary_search_perplexity, a wave per row.
+ *   dist2 [N][k] (fp32, ld_dist2 >= k): a row's squared distances to its k neighbours, the row itself not among them.
+ *   p [N][k] (fp32, ld_p >= k): p_{j|i} = exp(-beta_i (d_ij - m_i)) / sum_j exp(-beta_i (d_ij - m_i)), m_i = min_j d_ij (p and the entropy
+ *   do not depend on m; with it the largest exponential is exp(0) = 1 and the sum cannot underflow, where sklearn adds an epsilon).
+ *   beta [N]: the precision the search ended on, the one p was evaluated at.  The search: beta = 1; H = log(sum) + beta sum_j (d - m) p_j;
+ *   done when |H - log(perplexity)| <= 1e-5; H too large: beta doubles while no upper bracket exists, else bisects upwards; otherwise it
+ *   halves while no lower bracket exists, else bisects downwards; at most 100 evaluations whatever the data (a row of equal distances
+ *   runs all 100 and gets p = 1 / k; a row with inf or NaN ends too, with NaN in p).  A row's lanes add its terms 64 apart, then a fixed
+ *   butterfly: at most ceil(k / 64) + 6 additions deep.  expf, logf: the device library's (1 ulp); the division is correctly rounded.
+ *   MMVAE_ERR_ARG (nothing enqueued): a null struct or pointer, N < 1, k < 1, perplexity <= 0 or >= k (or NaN), a leading dimension
+ *   below k, a pointer not aligned to 4 bytes.
+ *
+ * mmvae_tsne_gradient: the gradient of KL(P || Q) at the embedding y, two launches.
+ *   y [N][2] (fp32, contiguous, 8-byte aligned).  P as CSR: row_ptr [N + 1], col [nnz] (int32), val [nnz] (fp32); it cannot be
+ *   validated at the call: row_ptr is clamped to [0, nnz] and made non-decreasing per row, col to [0, N), so a bad matrix gives wrong
+ *   numbers but no access out of range.  No order of a row's entries is assumed; the attraction's bits depend on it.
+ *   w_ij = 1 / (1 + |y_i - y_j|^2)        A_i = sum_{j in P(i)} p_ij w_ij (y_i - y_j)        R_i = sum_{j != i} w_ij^2 (y_i - y_j)
+ *   Z = sum_{i != j} w_ij                  grad [N][2] = 4 (exaggeration A_i - R_i / Z)
+ *   z [1]: Z.  err [N] (optional): err_i = sum_{j in P(i), p_ij > 0} p_ij (log p_ij + log(1 + |y_i - y_j|^2) + log Z); their sum is
+ *   sklearn's Barnes-Hut error sum p log(p / q) over the stored entries (the caller adds them: in float64, in one fixed order).  p is
+ *   used as given: with exaggeration != 1 sklearn's error would take exaggeration p inside the logarithm too.  z_row [N] (optional):
+ *   z_i = sum_{j != i} w_ij.
+ *   1 + d^2 is fma(dy, dy, fma(dx, dx, 1)); w is v_rcp_f32 of it (1 ulp); the diagonal pair gets w = 0, so it adds exactly 0 to R_i and
+ *   nothing to z_i; columns >= N are never walked.
+ *   Repulsion launch: a workgroup owns 512 rows (a lane rows t and t + 256 of the block, in registers) and walks its split's columns in
+ *   ascending order, 1024 at a time through LDS (every lane reads the same y_j: a broadcast): R_i and z_i of a split are single chains of
+ *   its columns.  The columns are cut into splits_used consecutive runs of 64-column chunks:
+ *     blocks = ceil(N / 512),  chunks = ceil(N / 64)
+ *     want = splits > 0 ? splits : (blocks >= 2048 ? 1 : ceil(2048 / blocks));   want = min(want, 64, chunks)
+ *     chunks_per_split = ceil(chunks / want);   splits_used = ceil(chunks / chunks_per_split)        (mmvae_tsne_gradient_splits)
+ *   Every split writes (R_x, R_y, z_i) per row, and every workgroup one fp32 sum of its rows' z_i (a lane's two rows, a 6-step butterfly
+ *   over the wave, the four waves in order: at most 1 + 6 + 3 additions on top of z_i), to `work`.
+ *   Second launch: Z = the float64 sum of the splits_used x blocks workgroup sums (256 strided chains, then a binary tree of 8 levels; the
+ *   same in every workgroup), rounded to fp32.  A wave per row: the row's partials in ascending split order; the row's entries 64 apart
+ *   per lane (any row length), the lane sums of A_i and err_i by a 6-step butterfly; R_i / Z is a correctly rounded division.
+ *   work: caller-owned, 8-byte aligned, at least mmvae_tsne_gradient_work_bytes(N, splits) = 12 N splits_used + 4 splits_used blocks
+ *   bytes (each rounded up to 8); the library allocates nothing.
+ *   Limits: 2 <= N, 0 <= nnz < 2^31.  Z underflows to 0 (and grad is not finite) only when every |y_i - y_j|^2 exceeds about 1e38.
+ *   MMVAE_ERR_ARG (nothing enqueued): a null struct, null y / row_ptr / grad / z / work, null col or val with nnz > 0, N < 2, nnz < 0,
+ *   splits outside [0, 64], a pointer not aligned to its element (y, work: 8 bytes), work_bytes too small.
+ *
+ * mmvae_tsne_update: one step of sklearn's _gradient_descent, in place, an element e of the 2 N per thread:
+ *   gains_e = max(update_e grad_e < 0 ? gains_e + 0.2 : 0.8 gains_e, 0.01);   update_e = fma(momentum, update_e, -(learning_rate (grad_e gains_e)));
+ *   y_e += update_e.
+ *   grad_norm [1] (optional): |gains * grad|_2, the norm sklearn's stopping rule reads (it takes it after grad *= gains): squares added
+ *   by a butterfly per wave, the four waves in order, then the workgroups' sums in float64 by a second one-workgroup launch (256
+ *   strided chains and a binary tree), the square root rounded to fp32.  It needs work: 8-byte aligned, at least
+ *   mmvae_tsne_update_work_bytes(N) = 4 ceil(2 N / 256) bytes (rounded up to 8).
+ *   MMVAE_ERR_ARG (nothing enqueued): a null struct, null y / update / gains / grad, N < 1, a misaligned pointer, grad_norm without
+ *   enough work.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct {
+    const float* dist2; float* p; float* beta;
+    int64_t ld_dist2, ld_p;
+    int32_t N, k; float perplexity; int32_t pad_;
+} mmvae_tsne_affinities_args;
+int mmvae_tsne_affinities(const mmvae_tsne_affinities_args* args, void* stream);
+typedef struct {
+    const float* y; const int32_t* row_ptr; const int32_t* col; const float* val;
+    float* grad; float* z; float* err; float* z_row; void* work;
+    int64_t nnz, work_bytes;
+    int32_t N, splits; float exaggeration; int32_t pad_;
+} mmvae_tsne_gradient_args;
+int mmvae_tsne_gradient(const mmvae_tsne_gradient_args* args, void* stream);
+/* need no device; MMVAE_ERR_ARG for N < 2, splits outside [0, 64] or a null result pointer. */
+int mmvae_tsne_gradient_splits(int32_t N, int32_t splits, int32_t* splits_used);
+int mmvae_tsne_gradient_work_bytes(int32_t N, int32_t splits, int64_t* bytes);
+typedef struct {
+    float* y; float* update; float* gains; const float* grad; float* grad_norm; void* work;
+    int64_t work_bytes;
+    int32_t N; float momentum, learning_rate; int32_t pad_;
+} mmvae_tsne_update_args;
+int mmvae_tsne_update(const mmvae_tsne_update_args* args, void* stream);
+int mmvae_tsne_update_work_bytes(int32_t N, int64_t* bytes);
 
 /* ---------------------------------------------------------------------------------------------
  * AdamW (torch.optim.AdamW, constructed by the caller: optimize_hyperparameters.py:93-97,

@@ -12,7 +12,7 @@
 // unsigned compare and an empty slot is the largest entry.  After a tile a lane holds 64 keys; the compare path is one fp32 FMA, the
 // order transform and a compare against the high word of the row's k-th entry, and a wave-wide vote skips the rest when no lane
 // passed (after the first tiles: nearly always).  The insert path takes the 16 lanes that share a query row in the MFMA layout: they
-// insert one candidate at a time, each lane rewriting the list positions li, li + 16, .. (new[p] = old[p] <= c ? old[p] :
+// insert one candidate at a time, each lane rewriting the list positions li, li + 16, .. < k (new[p] = old[p] <= c ? old[p] :
 // max(old[p-1], c)), the four row groups of the wave in lock step.  The two waves that share query rows take turns (one barrier each).
 // Nothing in it depends on the order in which candidates arrive, so the result is a function of the keys alone.
 // Split: grid.y workgroups per query block take consecutive runs of tiles; their lists go to the workspace and knn_merge_kernel ranks
@@ -26,11 +26,13 @@ namespace mm {
 
 constexpr int KNN_BM = 128, KNN_BN = 128;       // query rows of a workgroup, training rows of a tile
 constexpr int KNN_TILE_BYTES = (KNN_BM + KNN_BN) * RT_LDR * 4;
-constexpr int KNN_MAX_LDS = KNN_TILE_BYTES + KNN_BM * MMVAE_KNN_MAXK * 8;
+constexpr int knn_max_lds(int slots) { return KNN_TILE_BYTES + KNN_BM * 16 * slots * 8; }   // operand tile + 128 lists of 16 slots entries
 constexpr int KNN_TARGET_WG = 4 * NUM_CU;      // below this many query blocks the training rows are split
 constexpr int KNN_MAX_SPLITS = 64;
 constexpr unsigned long long KNN_EMPTY = ~0ull;
-static_assert(MMVAE_KNN_MAXK % 16 == 0 && MMVAE_KNN_MAXK <= 64, "knn_insert: 16 lanes x 4 positions");
+constexpr int KNN_SLOTS = MMVAE_KNN_MAXK / 16;  // list positions a lane of a row group rewrites at most
+static_assert(MMVAE_KNN_MAXK % 16 == 0 && KNN_SLOTS * 16 == MMVAE_KNN_MAXK, "knn_insert: 16 lanes x KNN_SLOTS positions");
+static_assert(knn_max_lds(KNN_SLOTS) <= 160 * 1024, "knn_kernel: operand tile + 128 lists of MMVAE_KNN_MAXK entries in one workgroup's LDS");
 
 struct KnnP {
     const void* q; const void* t; const float* shift;
@@ -52,7 +54,10 @@ __device__ __forceinline__ unsigned knn_order(float key) {
 __device__ __forceinline__ float knn_key(unsigned u) { return __uint_as_float((u >> 31) ? (u ^ 0x80000000u) : ~u); }
 
 // The 16 lanes of a row group (lane >> 4) insert their passing candidates into the group's list, one at a time; the wave's four groups
-// in lock step.  L: this lane's group's list (k sorted entries).
+// in lock step.  L: this lane's group's list (k sorted entries).  S: positions per lane, 16 S >= k.  The kernel is instantiated for
+// S = 4 (k <= 64: the code of every search before MMVAE_KNN_MAXK grew, instruction for instruction) and for S = KNN_SLOTS beyond; one
+// kernel holding both inserts at its 64 call sites ran the k = 50 search a third slower.
+template <int S>
 __device__ __forceinline__ void knn_insert(unsigned long long* L, bool pass, unsigned long long cand, int lane, int k) {
     const int li = lane & 15, g0 = lane & 48;
     unsigned long long pend = __ballot(pass);
@@ -61,10 +66,10 @@ __device__ __forceinline__ void knn_insert(unsigned long long* L, bool pass, uns
         const bool act = gm != 0;
         const int src = g0 + (act ? __ffs(gm) - 1 : 0);
         const unsigned long long c = __shfl(cand, src, WAVE);
-        unsigned long long nv[4];
-        bool wr[4];
+        unsigned long long nv[S];
+        bool wr[S];
 #pragma unroll
-        for (int s = 0; s < 4; ++s) {
+        for (int s = 0; s < S; ++s) {
             const int p = li + 16 * s;
             wr[s] = false;
             nv[s] = 0;
@@ -77,7 +82,7 @@ __device__ __forceinline__ void knn_insert(unsigned long long* L, bool pass, uns
         }
         wave_lds_sync();                                   // every position is read before any is rewritten
 #pragma unroll
-        for (int s = 0; s < 4; ++s)
+        for (int s = 0; s < S; ++s)
             if (wr[s]) L[li + 16 * s] = nv[s];
         wave_lds_sync();
         if (lane == src) pass = false;
@@ -85,7 +90,7 @@ __device__ __forceinline__ void knn_insert(unsigned long long* L, bool pass, uns
     }
 }
 
-template <typename TQ, typename TT>
+template <typename TQ, typename TT, int S>
 __global__ __launch_bounds__(RT_THREADS) void knn_kernel(KnnP a) {
     extern __shared__ __align__(16) unsigned char knn_smem[];
     float* sQ = (float*)knn_smem;                          // [KNN_BM][RT_LDR]
@@ -165,7 +170,7 @@ __global__ __launch_bounds__(RT_THREADS) void knn_kernel(KnnP a) {
                             for (int ni = 0; ni < 4; ++ni) {
                                 const unsigned u = knn_order(tnv[ni] - 2.f * acc[mi][ni][r]);
                                 const bool pass = jok[ni] && row < nr && u <= thr;
-                                if (__any(pass)) knn_insert(L, pass, ((unsigned long long)u << 32) | jlo[ni], lane, k);
+                                if (__any(pass)) knn_insert<S>(L, pass, ((unsigned long long)u << 32) | jlo[ni], lane, k);
                             }
                         }
                 }
@@ -226,6 +231,16 @@ __global__ __launch_bounds__(KNN_MEAN_THREADS) void knn_mean_kernel(const int* i
         s += to_f32(y[j * ldy + c]);
     }
     out[row * ldo + c] = s / (float)k;
+}
+
+template <int S>
+static int knn_launch(int q_dtype, int t_dtype, const KnnP& p, dim3 grid, int lds, hipStream_t st) {
+    constexpr int MAX_LDS = knn_max_lds(S);
+    if (q_dtype == MMVAE_F32)
+        return t_dtype == MMVAE_F32 ? rt_launch_dyn_lds<knn_kernel<float, float, S>, MAX_LDS>(p, grid, lds, st)
+                                    : rt_launch_dyn_lds<knn_kernel<float, bf16, S>, MAX_LDS>(p, grid, lds, st);
+    return t_dtype == MMVAE_F32 ? rt_launch_dyn_lds<knn_kernel<bf16, float, S>, MAX_LDS>(p, grid, lds, st)
+                                : rt_launch_dyn_lds<knn_kernel<bf16, bf16, S>, MAX_LDS>(p, grid, lds, st);
 }
 
 static bool knn_sizes_ok(int Mq, int Nt, int k) { return Mq >= 1 && Nt >= 1 && k >= 1 && k <= Nt && k <= MMVAE_KNN_MAXK; }
@@ -290,13 +305,7 @@ extern "C" int mmvae_knn_search(const mmvae_knn_args* a, void* stream) {
 
     const dim3 grid((unsigned)(((long)a->Mq + KNN_BM - 1) / KNN_BM), (unsigned)p.nsplit);
     const int lds = KNN_TILE_BYTES + KNN_BM * p.kp * 8;
-    if (a->q_dtype == MMVAE_F32) {
-        rc = a->t_dtype == MMVAE_F32 ? rt_launch_dyn_lds<knn_kernel<float, float>, KNN_MAX_LDS>(p, grid, lds, st)
-                                     : rt_launch_dyn_lds<knn_kernel<float, bf16>, KNN_MAX_LDS>(p, grid, lds, st);
-    } else {
-        rc = a->t_dtype == MMVAE_F32 ? rt_launch_dyn_lds<knn_kernel<bf16, float>, KNN_MAX_LDS>(p, grid, lds, st)
-                                     : rt_launch_dyn_lds<knn_kernel<bf16, bf16>, KNN_MAX_LDS>(p, grid, lds, st);
-    }
+    rc = p.kp <= 64 ? knn_launch<4>(a->q_dtype, a->t_dtype, p, grid, lds, st) : knn_launch<KNN_SLOTS>(a->q_dtype, a->t_dtype, p, grid, lds, st);
     if (rc) return rc;
     if (p.nsplit > 1) {
         hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)a->Mq), dim3(WAVE), 0, st, p);

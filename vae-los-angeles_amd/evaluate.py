@@ -17,6 +17,9 @@ numbers are computed on the device (mmvae.clustering), one feature matrix at a t
 --clustering-pca K adds the table's second half (its "PCA Silh | NH" columns, cluster_imputation_methods.py:140-187, 473-504): the
 same two numbers on the projection of the same standardised matrix onto its first K principal components (the reference's K is 2), and
 the share of the variance those components explain; the PCA runs on the device too (mmvae.pca).
+--clustering-tsne adds its last part (its "t-SNE Silh | NH" columns, same lines): the same two numbers on TSNE(2, perplexity=min(30, n - 1),
+random_state=seed) of the standardised matrix, through a PCA(50) first when it has more than 50 columns, as the reference does; the
+t-SNE runs on the device as well (mmvae.tsne: exact repulsion, no tree).  --tsne-perplexity and --tsne-iters change its 30 and 1000.
 Routes: the directional models' one route; MultiModalVAE: a -> b, b -> a and the full (a, b, site) reconstruction.  The metrics
 are computed on the device (mmvae.metrics: one streaming launch per batch and route), nothing but 32 bytes per feature and the
 per-row vectors' aggregates reaches the host.  Evaluation runs in eval mode under no_grad; eps is still sampled (vae.py:73), so
@@ -60,6 +63,10 @@ def build_parser(kind):
     ap.add_argument("--clustering-out", default=None, help="with --clustering: write that table's rows as JSON here")
     ap.add_argument("--clustering-pca", type=int, default=0, metavar="K",
                     help="with --clustering: add silhouette and neighbourhood hit of the K-component PCA projection (0 = off)")
+    ap.add_argument("--clustering-tsne", action="store_true",
+                    help="with --clustering: add silhouette and neighbourhood hit of the 2-D t-SNE embedding (PCA(50) first beyond 50 features)")
+    ap.add_argument("--tsne-perplexity", type=float, default=30.0, help="with --clustering-tsne: perplexity (capped at rows - 1)")
+    ap.add_argument("--tsne-iters", type=int, default=1000, help="with --clustering-tsne: iterations (at least 250)")
     return ap
 
 
@@ -91,11 +98,14 @@ def print_table(rows):
 
 CLUSTERING_COLUMNS = ("Silhouette", "NeighborhoodHit")
 PCA_COLUMNS = ("PCASilhouette", "PCANeighborhoodHit", "PCAExplained")
+TSNE_COLUMNS = ("TSNESilhouette", "TSNENeighborhoodHit")
+TSNE_PCA_K = 50                                              # the reference reduces to 50 components in front of t-SNE
 NH_K = 5
 
 
 def print_clustering_table(rows):
-    cols = CLUSTERING_COLUMNS + (PCA_COLUMNS if rows and PCA_COLUMNS[0] in rows[0] else ())
+    cols = CLUSTERING_COLUMNS + (PCA_COLUMNS if rows and PCA_COLUMNS[0] in rows[0] else ()) \
+        + (TSNE_COLUMNS if rows and TSNE_COLUMNS[0] in rows[0] else ())
     head = f"{'Features':<16}{'Model':<16}" + "".join(f"{c:>{max(17, len(c) + 2)}}" for c in cols)
     print(head)
     print("-" * len(head))
@@ -103,10 +113,19 @@ def print_clustering_table(rows):
         print(f"{r['Features']:<16}{r['Model']:<16}" + "".join(f"{r[c]:>{max(17, len(c) + 2)}.6f}" for c in cols))
 
 
-def clustering_table(entries, va, dims, B, pca_k=0):
+def tsne_embedding(z, perplexity, iters, seed):
+    """The reference's t-SNE of a standardised matrix: PCA(50) first when it has more than 50 columns, perplexity capped at rows - 1."""
+    from mmvae import clustering
+    if z.shape[1] > TSNE_PCA_K:
+        z = clustering.PCA(TSNE_PCA_K).fit_transform(z)
+    return clustering.TSNE(2, perplexity=min(perplexity, z.shape[0] - 1), max_iter=iters, random_state=seed).fit_transform(z)
+
+
+def clustering_table(entries, va, dims, B, pca_k=0, tsne=None):
     """[(features, model name, fill)] -> table rows.  fill(i, tgt) gives the imputed rows i .. i + B of its target modality, or is None
     for the true features.  ONE (rows, A + D) fp32 matrix is filled batch by batch, standardised, judged and reused.  pca_k > 0: the
-    same two numbers on the standardised matrix's projection onto its first pca_k principal components as well."""
+    same two numbers on the standardised matrix's projection onto its first pca_k principal components as well.  tsne = (perplexity,
+    iterations, seed): and on its t-SNE embedding."""
     from mmvae import clustering
     from mmvae._lib import SIL_MAXC
     n_val, labels = va[0].shape[0], va[2]
@@ -131,6 +150,11 @@ def clustering_table(entries, va, dims, B, pca_k=0):
             rows[-1].update({"PCASilhouette": clustering.silhouette_score(y, labels),
                              "PCANeighborhoodHit": clustering.neighborhood_hit(y, labels, k=NH_K),
                              "PCAExplained": float(pca.explained_variance_ratio_.sum())})
+            del y
+        if tsne is not None:
+            y = tsne_embedding(z, *tsne)
+            rows[-1].update({"TSNESilhouette": clustering.silhouette_score(y, labels),
+                             "TSNENeighborhoodHit": clustering.neighborhood_hit(y, labels, k=NH_K)})
             del y
         del z
     return rows
@@ -226,6 +250,10 @@ def run(kind, argv=None, return_clustering=False):
         raise SystemExit("--clustering-out needs --clustering")
     if args.clustering_pca and not args.clustering:
         raise SystemExit("--clustering-pca needs --clustering")
+    if args.clustering_tsne and not args.clustering:
+        raise SystemExit("--clustering-tsne needs --clustering")
+    if args.clustering_tsne and (not args.tsne_perplexity > 0 or args.tsne_iters < 250):
+        raise SystemExit("--tsne-perplexity must be positive and --tsne-iters at least 250")
     from mmvae._lib import PCA_MAXK
     if not 0 <= args.clustering_pca <= min(PCA_MAXK, va[0].shape[0], args.input_dim_a + args.input_dim_b):
         raise SystemExit(f"--clustering-pca {args.clustering_pca} outside [0, min({PCA_MAXK}, validation rows, features)]")
@@ -256,10 +284,13 @@ def run(kind, argv=None, return_clustering=False):
                 if rtgt == tgt:
                     entries.append((route, model_name, tgt, lambda i, reg=reg, by_site=by_site, src_i=src_i:
                                     reg.predict(va[src_i][i:i + B], va[2][i:i + B]) if by_site else reg.predict(va[src_i][i:i + B])))
-        crows = clustering_table(entries, va, dims, B, args.clustering_pca)
+        crows = clustering_table(entries, va, dims, B, args.clustering_pca,
+                                 (args.tsne_perplexity, args.tsne_iters, args.seed) if args.clustering_tsne else None)
     if crows:
         print(f"clustering by site: standardised [a | b] features, silhouette and neighbourhood hit (k={NH_K})"
-              + (f"; PCA columns: the same on the first {args.clustering_pca} principal components" if args.clustering_pca else ""))
+              + (f"; PCA columns: the same on the first {args.clustering_pca} principal components" if args.clustering_pca else "")
+              + (f"; TSNE columns: the same on the 2-D t-SNE embedding (perplexity {min(args.tsne_perplexity, n_val - 1):g}, "
+                 f"{args.tsne_iters} iterations)" if args.clustering_tsne else ""))
         print_clustering_table(crows)
     if args.clustering_out:
         with open(args.clustering_out, "w") as f:

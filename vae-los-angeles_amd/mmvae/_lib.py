@@ -19,7 +19,7 @@ EPI_STORE, EPI_RELU_MASK, EPI_BN_BWD, EPI_LOSS_MSE, EPI_LOSS_BCE_LOGIT = 0, 1, 2
 ACT_NONE, ACT_RELU, ACT_SIGMOID = 0, 1, 2
 TILE = 128
 TN_GROUP_MAX = 8        # MMVAE_TN_GROUP_MAX
-KNN_MAXK = 64           # MMVAE_KNN_MAXK
+KNN_MAXK = 96           # MMVAE_KNN_MAXK
 SIL_MAXC = 64           # MMVAE_SIL_MAXC
 PCA_MAXK = 64           # MMVAE_PCA_MAXK
 CTR_COPIES = 16384      # MMVAE_CTR_COPIES: self-advancing device counters are stored as this many identical int64 copies
@@ -167,6 +167,24 @@ class PcaProjectArgs(C.Structure):
                 ("N", i32), ("F", i32), ("k", i32), ("x_dtype", i32)]
 
 
+class TsneAffinitiesArgs(C.Structure):
+    _fields_ = [("dist2", vp), ("p", vp), ("beta", vp),
+                ("ld_dist2", i64), ("ld_p", i64),
+                ("N", i32), ("k", i32), ("perplexity", f32), ("pad_", i32)]
+
+
+class TsneGradientArgs(C.Structure):
+    _fields_ = [("y", vp), ("row_ptr", vp), ("col", vp), ("val", vp), ("grad", vp), ("z", vp), ("err", vp), ("z_row", vp), ("work", vp),
+                ("nnz", i64), ("work_bytes", i64),
+                ("N", i32), ("splits", i32), ("exaggeration", f32), ("pad_", i32)]
+
+
+class TsneUpdateArgs(C.Structure):
+    _fields_ = [("y", vp), ("update", vp), ("gains", vp), ("grad", vp), ("grad_norm", vp), ("work", vp),
+                ("work_bytes", i64),
+                ("N", i32), ("momentum", f32), ("learning_rate", f32), ("pad_", i32)]
+
+
 class GatherItem(C.Structure):
     _fields_ = [("src", vp), ("dst", vp), ("src_row_stride", i64), ("dst_row_stride", i64), ("row_bytes", i32), ("pad_", i32)]
 
@@ -208,6 +226,12 @@ _SIGNATURES = {
     "mmvae_pca_scatter_splits": [i32, i32, i32, C.POINTER(i32)],
     "mmvae_pca_scatter_work_bytes": [i32, i32, i32, C.POINTER(i64)],
     "mmvae_pca_project": [C.POINTER(PcaProjectArgs), vp],
+    "mmvae_tsne_affinities": [C.POINTER(TsneAffinitiesArgs), vp],
+    "mmvae_tsne_gradient": [C.POINTER(TsneGradientArgs), vp],
+    "mmvae_tsne_gradient_splits": [i32, i32, C.POINTER(i32)],
+    "mmvae_tsne_gradient_work_bytes": [i32, i32, C.POINTER(i64)],
+    "mmvae_tsne_update": [C.POINTER(TsneUpdateArgs), vp],
+    "mmvae_tsne_update_work_bytes": [i32, C.POINTER(i64)],
     "mmvae_gather_rows": [vp, i32, vp, i32, i64, vp],
     "mmvae_rows_to_bf16": [vp, i32, i64, vp, i64, i32, i32, vp],
     "mmvae_sigmoid_bwd": [i32, i32, vp, i64, vp, i64, vp, i32, i64, vp],

@@ -5,7 +5,8 @@ labels) and calculate_neighborhood_hit (src/clustering_evaluation/cluster_imputa
     s = silhouette_samples(Z, labels)              # fp32 (N,) on the device
     score = silhouette_score(Z, labels)            # Python float
     nh = neighborhood_hit(Z, labels, k=5)
-    Y = PCA(n_components=2).fit_transform(Z)       # mmvae.pca: the table's second half, the same two numbers on Y
+    Y = PCA(n_components=2).fit_transform(Z)       # mmvae.pca: the table's second part, the same two numbers on Y
+    T = TSNE(n_components=2, perplexity=30.0, random_state=42).fit_transform(PCA(50).fit_transform(Z))    # mmvae.tsne: its third
 
 The silhouette runs on mmvae_silhouette_samples (a fp32 MFMA distance GEMM whose epilogue is a square root and a per-class row sum: the
 N x N distances never exist).  Euclidean metric only, no sample_size (nothing in the reference uses either)."""
@@ -15,8 +16,9 @@ from . import _lib as L
 from . import ops
 from .knn import neighborhood_hit  # noqa: F401  (neighborhood_hit: re-exported)
 from .pca import PCA  # noqa: F401  (re-exported: the table's PCA columns)
+from .tsne import TSNE  # noqa: F401  (re-exported: the table's t-SNE columns)
 
-__all__ = ["silhouette_samples", "silhouette_score", "standardize", "neighborhood_hit", "PCA"]
+__all__ = ["silhouette_samples", "silhouette_score", "standardize", "neighborhood_hit", "PCA", "TSNE"]
 
 
 def _encode(labels, N, device):

@@ -954,6 +954,110 @@ def pca_project(x, shift, v, out=None):
     return y
 
 
+# --------------------------------------------------------------------------------------------
+# t-SNE (include/mmvae_hip.h: mmvae_tsne_affinities, mmvae_tsne_gradient, mmvae_tsne_update)
+# --------------------------------------------------------------------------------------------
+def _f32_matrix(t, name, what, cols=None):
+    """t, an fp32 (rows >= 1, cols) device tensor with unit inner stride (a view is allowed)"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"{what}: {name} must be a CUDA/HIP tensor; there is no CPU fallback")
+    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1 or t.stride(1) != 1 \
+            or (t.shape[0] > 1 and t.stride(0) < t.shape[1]) or (cols is not None and t.shape[1] != cols):
+        raise ValueError(f"{what}: {name} must be an fp32 (rows, {cols or 'cols'}) tensor with unit inner stride, got {tuple(t.shape)} {t.dtype}")
+    return t
+
+
+def tsne_affinities(dist2, perplexity, *, p_out=None, beta_out=None):
+    """(p, beta): the conditional p_{j|i} fp32 (N, k) of sklearn's _binary_search_perplexity on a row's k squared neighbour distances
+    dist2 fp32 (N, k) (the row itself not among them), and the precision fp32 (N,) each row's search ended on (mmvae_tsne_affinities)."""
+    what = "tsne_affinities"
+    d = _f32_matrix(dist2, "dist2", what)
+    N, k = d.shape
+    perplexity = float(perplexity)
+    if not 0.0 < perplexity < k:
+        raise ValueError(f"{what}: perplexity = {perplexity} outside (0, k = {k})")
+    p = _out_view(p_out, "p_out", what, torch.float32, N, k, d.device)
+    beta = _vector(torch.empty(N, dtype=torch.float32, device=d.device) if beta_out is None else beta_out, "beta_out", what, torch.float32, N,
+                   d.device, strided=True)
+    a = L.TsneAffinitiesArgs(d.data_ptr(), p.data_ptr(), beta.data_ptr(), _ld(d), _ld(p), N, k, perplexity, 0)
+    with stream_span(what, 8 * N * k):
+        L.check(L.load().mmvae_tsne_affinities(C.byref(a), _stream()), "mmvae_tsne_affinities")
+    return p, beta
+
+
+def tsne_gradient_splits(N, splits=0):
+    """The number of column splits tsne_gradient uses for N points and this request (mmvae_tsne_gradient_splits); needs no device."""
+    return _plan("mmvae_tsne_gradient_splits", N, splits)
+
+
+def tsne_gradient_work_bytes(N, splits=0):
+    return _plan("mmvae_tsne_gradient_work_bytes", N, splits, outs=(C.c_int64,))
+
+
+def tsne_gradient(y, row_ptr, col, val, exaggeration=1.0, *, error=False, z_row=False, splits=0, grad_out=None, work=None):
+    """(grad fp32 (N, 2), Z fp32 (1,), err fp32 (N,) or None, z_row fp32 (N,) or None) of the t-SNE objective at the embedding y fp32
+    (N, 2) contiguous, for the symmetric P in CSR (row_ptr int32 (N + 1,), col int32 (nnz,), val fp32 (nnz,)) (mmvae_tsne_gradient).
+    err.double().sum() is the KL divergence over the stored entries.  splits: 0 = the library's choice, 1 .. 64 forces that many column
+    splits.  work: a workspace from an earlier call's sizes (an int64 tensor of tsne_gradient_work_bytes(N, splits) / 8 elements)."""
+    what = "tsne_gradient"
+    y = _f32_matrix(y, "y", what, 2)
+    N = y.shape[0]
+    dev = y.device
+    if N < 2 or not y.is_contiguous():
+        raise ValueError(f"{what}: y must be a contiguous (N >= 2, 2) tensor")
+    _vector(row_ptr, "row_ptr", what, torch.int32, N + 1, dev)
+    if not isinstance(col, torch.Tensor) or col.dim() != 1:
+        raise ValueError(f"{what}: col must be an int32 (nnz,) device tensor")
+    nnz = col.shape[0]
+    _vector(col, "col", what, torch.int32, nnz, dev)
+    _vector(val, "val", what, torch.float32, nnz, dev)
+    splits = _splits_arg(splits, what)
+    grad = _out_view(grad_out, "grad_out", what, torch.float32, N, 2, dev)
+    if not grad.is_contiguous():
+        raise ValueError(f"{what}: grad_out must be contiguous")
+    z = torch.empty(1, dtype=torch.float32, device=dev)
+    err = torch.empty(N, dtype=torch.float32, device=dev) if error else None
+    zr = torch.empty(N, dtype=torch.float32, device=dev) if z_row else None
+    nbytes = tsne_gradient_work_bytes(N, splits)
+    if work is None:
+        work = _workspace(nbytes, dev)
+    elif not isinstance(work, torch.Tensor) or work.dtype != torch.int64 or not work.is_contiguous() or work.numel() * 8 < nbytes or work.device != dev:
+        raise ValueError(f"{what}: work must be a contiguous int64 tensor of at least {nbytes} bytes on y's device")
+    a = L.TsneGradientArgs(y.data_ptr(), row_ptr.data_ptr(), _p(col) if nnz else None, _p(val) if nnz else None, grad.data_ptr(), z.data_ptr(),
+                           _p(err), _p(zr), work.data_ptr(), nnz, work.numel() * 8, N, splits, float(exaggeration), 0)
+    with probe_span(what, lambda: dict(kind="valu", flops=10.0 * N * N, M=N, N=N, K=2)):
+        L.check(L.load().mmvae_tsne_gradient(C.byref(a), _stream()), "mmvae_tsne_gradient")
+    return grad, z, err, zr
+
+
+def tsne_update_work_bytes(N):
+    return _plan("mmvae_tsne_update_work_bytes", N, outs=(C.c_int64,))
+
+
+def tsne_update(y, update, gains, grad, momentum, learning_rate, *, grad_norm=False, work=None):
+    """One step of sklearn's _gradient_descent in place on y, update, gains (fp32 (N, 2), contiguous) from grad (mmvae_tsne_update).
+    Returns |gains * grad|_2 as an fp32 (1,) device tensor when grad_norm is set, else None."""
+    what = "tsne_update"
+    y = _f32_matrix(y, "y", what, 2)
+    N, dev = y.shape[0], y.device
+    for t, name in ((y, "y"), (update, "update"), (gains, "gains"), (grad, "grad")):
+        _f32_matrix(t, name, what, 2)
+        if t.shape[0] != N or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{what}: {name} must be a contiguous fp32 ({N}, 2) tensor on y's device")
+    gn = torch.empty(1, dtype=torch.float32, device=dev) if grad_norm else None
+    nbytes = tsne_update_work_bytes(N)
+    if grad_norm and work is None:
+        work = _workspace(nbytes, dev)
+    if work is not None and (not isinstance(work, torch.Tensor) or work.dtype != torch.int64 or not work.is_contiguous()
+                             or work.numel() * 8 < nbytes or work.device != dev):
+        raise ValueError(f"{what}: work must be a contiguous int64 tensor of at least {nbytes} bytes on y's device")
+    a = L.TsneUpdateArgs(y.data_ptr(), update.data_ptr(), gains.data_ptr(), grad.data_ptr(), _p(gn), _p(work),
+                         work.numel() * 8 if work is not None else 0, N, float(momentum), float(learning_rate), 0)
+    with stream_span(what, 7 * 8 * N):
+        L.check(L.load().mmvae_tsne_update(C.byref(a), _stream()), "mmvae_tsne_update")
+    return gn
+
+
 def adamw_step(items, lr, b1, b2, eps, wd, bc1, bc2, maximize=False, step_dev=None, lr_dev=None):
     """items: ctypes array of AdamWItem in host memory (device pointers inside).  step_dev: int64[CTR_COPIES] tensor of
     identical copies of the step count: bias corrections from the device counter, which the launch itself increments
