@@ -707,6 +707,75 @@ int mmvae_tsne_update(const mmvae_tsne_update_args* args, void* stream);
 int mmvae_tsne_update_work_bytes(int32_t N, int64_t* bytes);
 
 /* ---------------------------------------------------------------------------------------------
+ * The site classifier of the downstream task (classifier.hip): what SimpleMLP's training step (downstream_task.py:55-159; the
+ * directional script's MLP, downstream_task_directional.py, has no LayerNorm) needs beside the fp32 GEMMs.  fp32 in and out, a wave
+ * per row; no float atomics on anything a gradient is read from, every sum has one fixed order: the same arguments give the same bits.
+ *
+ * mmvae_ln_act_fwd: nn.LayerNorm(N) -> ReLU -> Dropout (downstream_task.py:58-66) in one pass over z [M][ldz], the row in registers.
+ *   mean_i = sum_j z_ij / N        var_i = sum_j (z_ij - mean_i)^2 / N   (biased, about the mean)        rstd_i = 1 / sqrt(var_i + eps)
+ *   y_ij = relu(xhat_ij gamma_j + beta_j) keep_ij inv_keep,   xhat_ij = (z_ij - mean_i) rstd_i;   mean [M] and rstd [M] are written.
+ *   mask: the uint8 keep mask of mmvae_noise ([M][ld_mask], bytes 0 or 1), inv_keep = 1 / (1 - p); NULL (eval mode, p = 0): no scaling.
+ *   layer_norm == 0: y = relu(z) keep inv_keep; gamma, beta, mean, rstd and eps are not read.
+ *   A lane adds its chunks' four elements pairwise, chunks 64 apart, then a 6-step butterfly: at most 2 + ceil(N / 256) + 6 additions deep.
+ *   Limits: M >= 1; N a multiple of 4, 4 <= N <= MMVAE_LN_MAXN (a lane holds N / 256 16-byte chunks); leading dimensions multiples of 4
+ *   and >= N; z, y, gamma, beta 16-byte aligned, the mask 4-byte aligned.
+ *   MMVAE_ERR_ARG (nothing enqueued): a null struct, null z / y, with layer_norm null gamma / beta / mean / rstd or eps <= 0, a size or
+ *   leading dimension outside the limits, a misaligned pointer, a mask with inv_keep < 1.
+ *
+ * mmvae_ln_act_bwd: from dy = dL/dy and the forward's z, mean, rstd, gamma, beta, mask:
+ *   g_ij = dy_ij keep_ij inv_keep [xhat_ij gamma_j + beta_j > 0]
+ *   dz_ij = rstd_i (g_ij gamma_j - mean_j(g gamma) - xhat_ij mean_j(g gamma xhat))        dgamma_j = sum_i g_ij xhat_ij        dbeta_j = sum_i g_ij
+ *   dgamma, dbeta [N] are WRITTEN.  A workgroup owns 32 consecutive rows: a wave adds its rows (w, w + 4, ...) in ascending order, the four
+ *   waves are added in order, and with more than one workgroup the partial sums go to `work` and a second small launch adds them in
+ *   ascending workgroup order; a launch of one workgroup (M <= 32, the training batch) writes dgamma / dbeta itself.
+ *   work: caller-owned, 8-byte aligned, at least mmvae_ln_act_bwd_work_bytes(M, N, layer_norm) = 8 N ceil(M / 32) bytes when layer_norm
+ *   and M > 32, else 0 (work may then be NULL).  layer_norm == 0: dz = dy keep inv_keep [z > 0], nothing else is read or written.
+ *   Limits and refusals as mmvae_ln_act_fwd, for dy / z / dz (16-byte aligned, leading dimensions multiples of 4); also null dgamma /
+ *   dbeta with layer_norm, a missing, misaligned or short workspace.
+ *
+ * mmvae_wce_mean: nn.CrossEntropyLoss(weight = w) with its mean reduction and torch.max(outputs, 1) (downstream_task.py:83,101,123).
+ *   logits [M][ld] fp32, 2 <= C <= MMVAE_WCE_MAXC, labels int64 [M], class_weights fp32 [C] or NULL (= 1).  A wave per row, a lane per class.
+ *   nll_i = max_i + log(sum_j exp(x_ij - max_i)) - x_{i,y_i}                  sums[0] += sum_i w_{y_i} nll_i,  sums[1] += sum_i w_{y_i}   (f64)
+ *   g_ij = w_{y_i} (softmax_ij - [j == y_i]) / W,   W = sum_i w_{y_i} over ALL M rows of the call: the gradient of sums[0] / sums[1].
+ *   W is formed by every workgroup from all M labels in one order (float64; thread t of 256 the labels t, t + 256, ..., a butterfly
+ *   per wave, the four waves in order; rounded to fp32): the same bits in every workgroup, no launch in front.  All weights zero: g is NaN,
+ *   as torch's.
+ *   pred [M] (int32): the argmax, the FIRST maximum on ties (a row holding NaN gives 0).  nll [M] (fp32, optional): the unweighted row
+ *   terms, from which the host forms the mean of per-batch means of one evaluation launch.  confusion [C][C] (int32, optional):
+ *   += 1 at [y_i][pred_i] (integer atomics: exact).
+ *   Labels as in mmvae_vae_loss: -100 is ignored (weight 0, not counted in confusion); any other label outside [0, C) is counted in
+ *   sums[2] and computed as class 0 (not counted in confusion) -- the caller raises.
+ *   Every one of sums (f64 [3], accumulated: zero it first), g (ldg >= C), pred, nll, confusion may be NULL, not all of them.
+ *   MMVAE_ERR_ARG (nothing enqueued): a null struct, null logits / labels, M < 1, C outside [2, MMVAE_WCE_MAXC], ld or ldg below C, a
+ *   pointer not aligned to its element, no output at all.
+ * ------------------------------------------------------------------------------------------- */
+#define MMVAE_LN_MAXN 1024
+#define MMVAE_WCE_MAXC 64
+typedef struct {
+    const float* z; const float* gamma; const float* beta; const uint8_t* mask;
+    float* y; float* mean; float* rstd;
+    int64_t ldz, ld_mask, ldy;
+    int32_t M, N, layer_norm; float eps, inv_keep; int32_t pad_;
+} mmvae_ln_act_fwd_args;
+int mmvae_ln_act_fwd(const mmvae_ln_act_fwd_args* args, void* stream);
+typedef struct {
+    const float* dy; const float* z; const float* mean; const float* rstd; const float* gamma; const float* beta; const uint8_t* mask;
+    float* dz; float* dgamma; float* dbeta; void* work;
+    int64_t lddy, ldz, ld_mask, lddz, work_bytes;
+    int32_t M, N, layer_norm; float inv_keep;
+} mmvae_ln_act_bwd_args;
+int mmvae_ln_act_bwd(const mmvae_ln_act_bwd_args* args, void* stream);
+/* needs no device; MMVAE_ERR_ARG for M < 1, an N outside the limits or a null result pointer */
+int mmvae_ln_act_bwd_work_bytes(int32_t M, int32_t N, int32_t layer_norm, int64_t* bytes);
+typedef struct {
+    const float* logits; const int64_t* labels; const float* class_weights;
+    double* sums; float* g; int32_t* pred; float* nll; int32_t* confusion;
+    int64_t ld, ldg;
+    int32_t M, C;
+} mmvae_wce_args;
+int mmvae_wce_mean(const mmvae_wce_args* args, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * AdamW (torch.optim.AdamW, constructed by the caller: optimize_hyperparameters.py:93-97,
  * train_dna2rna.py:185-189), all tensors in one launch per 64 tensors (every record is checked before the first launch).  `items_host` is an array in HOST memory
  * (device pointers inside); it is copied into the kernel arguments, so nothing is uploaded and the call is graph-capturable:
@@ -721,6 +790,14 @@ int mmvae_adamw_step(const mmvae_adamw_item* items_host, int32_t n_items, float 
  * the launch increments all of them itself (see mmvae_noise); otherwise advance the counter with mmvae_counter_add.
  * lr_dev != NULL: the learning rate is read from device memory (a captured graph follows ReduceLROnPlateau,
  * train_dna2rna.py:190-195,216, without re-capture). */
+
+/* Adam with the weight decay COUPLED into the gradient (torch.optim.Adam(lr, weight_decay), downstream_task.py:84): the same kernel
+ * source, items, by-value batch and step_dev / advance / lr_dev forms as mmvae_adamw_step, only the decay differs:
+ *   g' = g + wd*p ; m = b1*m+(1-b1)g' ; v = b2*v+(1-b2)g'^2 ; p -= lr/bc1 * m/(sqrt(v)/sqrt(bc2)+eps)
+ * (maximize negates g before the decay is added, as torch does). */
+int mmvae_adam_step(const mmvae_adamw_item* items_host, int32_t n_items, float lr, float beta1,
+                    float beta2, float eps, float weight_decay, float bias_corr1, float bias_corr2, int32_t maximize,
+                    uint64_t* step_dev, int32_t advance, const float* lr_dev, void* stream);
 
 #ifdef __cplusplus
 }

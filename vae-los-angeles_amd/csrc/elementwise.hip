@@ -786,6 +786,8 @@ __global__ __launch_bounds__(256) void rows_to_bf16_kernel(const ST* __restrict_
 // and a counter write (29 us for 30 MB of traffic).
 struct AdamWBatch { mmvae_adamw_item items[64]; int first[65]; int n; };      // passed BY VALUE (2.8 KiB of kernel arguments): no table
                                                         // upload, so the launch is hipGraph-capturable even when gradients move
+// COUPLED: torch.optim.Adam's decay, wd * p added to the gradient (mmvae_adam_step); otherwise AdamW's, p scaled by 1 - lr * wd
+template <bool COUPLED>
 __global__ __launch_bounds__(256) void adamw_kernel(const AdamWBatch batch, float lr, float b1, float b2,
                                                      float eps, float wd, float bc1, float rsqrt_bc2, int maximize,
                                                      uint64_t* step_dev, int copies, const float* lr_dev) {
@@ -818,8 +820,10 @@ __global__ __launch_bounds__(256) void adamw_kernel(const AdamWBatch batch, floa
         for (int u = 0; u < U; ++u) {
             const long i = i0 + u * stride;
             if (i >= it.n) break;
-            const float gg = maximize ? -g[u] : g[u];
-            float pp = p[u] * (1.f - lr * wd);
+            float gg = maximize ? -g[u] : g[u];
+            float pp = p[u];
+            if constexpr (COUPLED) gg += wd * pp;
+            else pp = p[u] * (1.f - lr * wd);
             const float mm_ = b1 * m[u] + (1.f - b1) * gg;
             const float vv = b2 * v[u] + (1.f - b2) * gg * gg;
             pp -= step * mm_ / (sqrtf(vv) * rsqrt_bc2 + eps);
@@ -1124,9 +1128,10 @@ extern "C" int mmvae_counter_add(uint64_t* counter_dev, uint64_t inc, void* stre
     return 0;
 }
 
-extern "C" int mmvae_adamw_step(const mmvae_adamw_item* items_host, int32_t n_items, float lr, float beta1,
-                                float beta2, float eps, float weight_decay, float bias_corr1, float bias_corr2, int32_t maximize,
-                                uint64_t* step_dev, int32_t advance, const float* lr_dev, void* stream) {
+template <bool COUPLED>
+static int adam_launch(const mmvae_adamw_item* items_host, int32_t n_items, float lr, float beta1,
+                       float beta2, float eps, float weight_decay, float bias_corr1, float bias_corr2, int32_t maximize,
+                       uint64_t* step_dev, int32_t advance, const float* lr_dev, void* stream) {
     if (!items_host || n_items <= 0 || (!step_dev && (bias_corr1 <= 0.f || bias_corr2 <= 0.f))) return MMVAE_ERR_ARG;
     if (advance && (!step_dev || n_items > 64)) return MMVAE_ERR_ARG;       // one launch = one tick of the counter
     if (step_dev) { bias_corr1 = 1.f; bias_corr2 = 1.f; }
@@ -1144,9 +1149,23 @@ extern "C" int mmvae_adamw_step(const mmvae_adamw_item* items_host, int32_t n_it
         if (advance && batch.first[n] > MMVAE_CTR_COPIES) return MMVAE_ERR_ARG;
     }
     for (const AdamWBatch& batch : batches) {
-        hipLaunchKernelGGL(adamw_kernel, dim3(batch.first[batch.n]), dim3(256), 0, (hipStream_t)stream, batch, lr, beta1, beta2, eps,
+        hipLaunchKernelGGL(adamw_kernel<COUPLED>, dim3(batch.first[batch.n]), dim3(256), 0, (hipStream_t)stream, batch, lr, beta1, beta2, eps,
                            weight_decay, bias_corr1, 1.0f / sqrtf(bias_corr2), maximize, step_dev, advance ? 1 : 0, lr_dev);
         MM_CHECK_LAUNCH();
     }
     return 0;
+}
+
+extern "C" int mmvae_adamw_step(const mmvae_adamw_item* items_host, int32_t n_items, float lr, float beta1,
+                                float beta2, float eps, float weight_decay, float bias_corr1, float bias_corr2, int32_t maximize,
+                                uint64_t* step_dev, int32_t advance, const float* lr_dev, void* stream) {
+    return adam_launch<false>(items_host, n_items, lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, maximize, step_dev, advance,
+                              lr_dev, stream);
+}
+
+extern "C" int mmvae_adam_step(const mmvae_adamw_item* items_host, int32_t n_items, float lr, float beta1,
+                               float beta2, float eps, float weight_decay, float bias_corr1, float bias_corr2, int32_t maximize,
+                               uint64_t* step_dev, int32_t advance, const float* lr_dev, void* stream) {
+    return adam_launch<true>(items_host, n_items, lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, maximize, step_dev, advance,
+                             lr_dev, stream);
 }

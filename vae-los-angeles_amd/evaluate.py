@@ -20,6 +20,12 @@ the share of the variance those components explain; the PCA runs on the device t
 --clustering-tsne adds its last part (its "t-SNE Silh | NH" columns, same lines): the same two numbers on TSNE(2, perplexity=min(30, n - 1),
 random_state=seed) of the standardised matrix, through a PCA(50) first when it has more than 50 columns, as the reference does; the
 t-SNE runs on the device as well (mmvae.tsne: exact repulsion, no tree).  --tsne-perplexity and --tsne-iters change its 30 and 1000.
+--downstream adds the reference's downstream task (downstream_task.py, downstream_task_directional.py): does a site classifier learn
+as well from the model's estimated modality as from the measured one?  On the validation rows whose site has at least two of them, the
+estimated modalities are drawn batch by batch, every scenario's features are standardised, split into --downstream-folds stratified
+folds, and a small MLP is trained per fold on the device (mmvae.downstream); one row per scenario with accuracy and weighted precision /
+recall / F1, each +- its std over the folds; --downstream-out FILE holds the per-class rows too.  MultiModalVAE: the eight scenarios of
+downstream_task.py:436-445; a directional model: the five its one route can fill.
 Routes: the directional models' one route; MultiModalVAE: a -> b, b -> a and the full (a, b, site) reconstruction.  The metrics
 are computed on the device (mmvae.metrics: one streaming launch per batch and route), nothing but 32 bytes per feature and the
 per-row vectors' aggregates reaches the host.  Evaluation runs in eval mode under no_grad; eps is still sampled (vae.py:73), so
@@ -67,6 +73,10 @@ def build_parser(kind):
                     help="with --clustering: add silhouette and neighbourhood hit of the 2-D t-SNE embedding (PCA(50) first beyond 50 features)")
     ap.add_argument("--tsne-perplexity", type=float, default=30.0, help="with --clustering-tsne: perplexity (capped at rows - 1)")
     ap.add_argument("--tsne-iters", type=int, default=1000, help="with --clustering-tsne: iterations (at least 250)")
+    ap.add_argument("--downstream", action="store_true", help="add the downstream task: site classification from original and estimated modalities")
+    ap.add_argument("--downstream-folds", type=int, default=5, help="with --downstream: stratified folds per scenario")
+    ap.add_argument("--downstream-epochs", type=int, default=100, help="with --downstream: most epochs per fold (early stopping may end sooner)")
+    ap.add_argument("--downstream-out", default=None, help="with --downstream: write the table, per-class rows included, as JSON here")
     return ap
 
 
@@ -158,6 +168,73 @@ def clustering_table(entries, va, dims, B, pca_k=0, tsne=None):
             del y
         del z
     return rows
+
+
+DOWNSTREAM_COLUMNS = (("Accuracy", None), ("Precision", "precision"), ("Recall", "recall"), ("F1", "f1-score"))
+
+
+def downstream_scenarios(kind, orig, est):
+    """{scenario name: [feature blocks]}: downstream_task.py:436-445 for the MultiModalVAE; for a directional model the five scenarios
+    its one route can fill.  orig / est: {'a': RNA, 'b': DNA} matrices (est holds the estimated target only for a directional kind)."""
+    if kind == "multimodal":
+        return {"Orig. RNA": [orig["a"]], "Orig. DNA": [orig["b"]], "Orig. RNA + Est. DNA": [orig["a"], est["b"]],
+                "Orig. DNA + Est. RNA": [orig["b"], est["a"]], "Orig. RNA + Orig. DNA": [orig["a"], orig["b"]], "Est. DNA": [est["b"]],
+                "Est. RNA": [est["a"]], "Est. RNA + Est. DNA": [est["a"], est["b"]]}
+    src, tgt = ("a", "b") if kind == "rna2dna" else ("b", "a")
+    n = {"a": "RNA", "b": "DNA"}
+    return {f"Orig. {n[src]}": [orig[src]], f"Orig. {n[tgt]}": [orig[tgt]], f"Orig. {n[src]} + Est. {n[tgt]}": [orig[src], est[tgt]],
+            f"Est. {n[tgt]}": [est[tgt]], f"Orig. {n[src]} + Orig. {n[tgt]}": [orig[src], orig[tgt]]}
+
+
+def downstream_table(kind, model, va, B, folds, epochs, seed):
+    """{scenario: the aggregated report of run_classification_scenario}, or {} with a message when the validation split cannot carry the
+    task.  Classes with fewer than 2 validation rows are dropped and the labels re-encoded contiguously (downstream_task.py:417-424)."""
+    from mmvae import downstream
+    from mmvae._lib import WCE_MAXC
+    site = va[2]
+    ids, inverse, counts = torch.unique(site, return_inverse=True, return_counts=True)
+    keep_class = counts >= 2
+    rows = keep_class[inverse].nonzero().squeeze(1)
+    kept = ids[keep_class]
+    if not 2 <= kept.numel() <= WCE_MAXC or folds < 2 or rows.numel() < folds or int(counts[keep_class].max()) < folds:
+        print(f"downstream table skipped: {kept.numel()} sites with at least 2 of the {site.numel()} validation rows (need 2 .. {WCE_MAXC}), "
+              f"{rows.numel()} rows for {folds} folds")
+        return {}
+    recode = torch.full((int(ids.max()) + 1,), -1, dtype=torch.int64, device=site.device)
+    recode[kept] = torch.arange(kept.numel(), device=site.device)
+    labels = recode[site[rows]]
+    names = [str(int(i)) for i in kept]
+    from mmvae import to_bf16_rows
+    # the kept rows in the inputs' storage (bf16 inputs keep their padded rows: the model reads them as it does above)
+    fa, fb = (to_bf16_rows(t[rows]) if t.dtype == torch.bfloat16 else t[rows].contiguous() for t in va[:2])
+    fs = site[rows].contiguous()
+    orig = {"a": fa.float().contiguous(), "b": fb.float().contiguous()}
+    est = {}
+    with torch.no_grad():
+        want = {"multimodal": (("b", lambda a, b, s: model(a=a)[1]), ("a", lambda a, b, s: model(b=b)[0])),
+                "rna2dna": (("b", lambda a, b, s: model(rna=a, site=s)[0]),),
+                "dna2rna": (("a", lambda a, b, s: model(dna=b, site=s)[0]),)}[kind]
+        for tgt, fwd in want:
+            out = torch.empty_like(orig[tgt])
+            for i in range(0, rows.numel(), B):
+                out[i:i + B].copy_(fwd(fa[i:i + B], fb[i:i + B], fs[i:i + B]))
+            est[tgt] = out
+    arch = dict(hidden=(256, 128), layer_norm=True, dropout=(0.3, 0.2)) if kind == "multimodal" else dict(hidden=(128,), layer_norm=False, dropout=(0.2,))
+    table = {}
+    for name, blocks in downstream_scenarios(kind, orig, est).items():
+        feats = blocks[0] if len(blocks) == 1 else torch.cat(blocks, dim=1)
+        table[name] = downstream.cross_validate(feats, labels, names, folds, epochs=epochs, seed=seed, **arch)
+        del feats
+    return table
+
+
+def print_downstream_table(table):
+    head = f"{'Scenario':<26}" + "".join(f"{c:>20}" for c, _ in DOWNSTREAM_COLUMNS)
+    print(head)
+    print("-" * len(head))
+    for name, r in table.items():
+        cells = [(r["accuracy"], r["accuracy_std"])] + [(r["weighted avg"][k], r["weighted avg"][k + "_std"]) for _, k in DOWNSTREAM_COLUMNS[1:]]
+        print(f"{name:<26}" + "".join(f"{f'{m:.4f} +- {sd:.4f}':>20}" for m, sd in cells))
 
 
 def run(kind, argv=None, return_clustering=False):
@@ -269,32 +346,46 @@ def run(kind, argv=None, return_clustering=False):
     if args.out:
         with open(args.out, "w") as f:
             json.dump(rows, f, indent=1)
-    if not args.clustering:
-        return (rows, []) if return_clustering else rows
-    # the clustering table: after the metrics, so that the table above does not depend on the flag (eps is drawn per forward)
-    entries = [("a|b", "original", None, None)]
-    with torch.no_grad():
-        for name, kwargs, outs in plan:
-            if len(outs) != 1:                               # the full reconstruction is not an imputation
-                continue
-            j, tgt = outs[0]
-            entries.append((name, title, tgt, lambda i, kwargs=kwargs, j=j: model(**kwargs(va[0][i:i + B], va[1][i:i + B], va[2][i:i + B]))[j]))
-            entries.append((name, "MeanImputation", tgt, lambda i, tgt=tgt: means[tgt].expand(min(B, n_val - i), -1)))
-            for route, model_name, reg, by_site, src_i, rtgt in knn_regs:
-                if rtgt == tgt:
-                    entries.append((route, model_name, tgt, lambda i, reg=reg, by_site=by_site, src_i=src_i:
-                                    reg.predict(va[src_i][i:i + B], va[2][i:i + B]) if by_site else reg.predict(va[src_i][i:i + B])))
-        crows = clustering_table(entries, va, dims, B, args.clustering_pca,
-                                 (args.tsne_perplexity, args.tsne_iters, args.seed) if args.clustering_tsne else None)
-    if crows:
-        print(f"clustering by site: standardised [a | b] features, silhouette and neighbourhood hit (k={NH_K})"
-              + (f"; PCA columns: the same on the first {args.clustering_pca} principal components" if args.clustering_pca else "")
-              + (f"; TSNE columns: the same on the 2-D t-SNE embedding (perplexity {min(args.tsne_perplexity, n_val - 1):g}, "
-                 f"{args.tsne_iters} iterations)" if args.clustering_tsne else ""))
-        print_clustering_table(crows)
-    if args.clustering_out:
-        with open(args.clustering_out, "w") as f:
-            json.dump(crows, f, indent=1)
+    if args.downstream_out and not args.downstream:
+        raise SystemExit("--downstream-out needs --downstream")
+    if args.downstream and (args.downstream_folds < 2 or args.downstream_epochs < 1):
+        raise SystemExit("--downstream-folds must be at least 2 and --downstream-epochs at least 1")
+    crows = []
+    if args.clustering:
+        # the clustering table: after the metrics, so that the table above does not depend on the flag (eps is drawn per forward)
+        entries = [("a|b", "original", None, None)]
+        with torch.no_grad():
+            for name, kwargs, outs in plan:
+                if len(outs) != 1:                               # the full reconstruction is not an imputation
+                    continue
+                j, tgt = outs[0]
+                entries.append((name, title, tgt, lambda i, kwargs=kwargs, j=j: model(**kwargs(va[0][i:i + B], va[1][i:i + B], va[2][i:i + B]))[j]))
+                entries.append((name, "MeanImputation", tgt, lambda i, tgt=tgt: means[tgt].expand(min(B, n_val - i), -1)))
+                for route, model_name, reg, by_site, src_i, rtgt in knn_regs:
+                    if rtgt == tgt:
+                        entries.append((route, model_name, tgt, lambda i, reg=reg, by_site=by_site, src_i=src_i:
+                                        reg.predict(va[src_i][i:i + B], va[2][i:i + B]) if by_site else reg.predict(va[src_i][i:i + B])))
+            crows = clustering_table(entries, va, dims, B, args.clustering_pca,
+                                     (args.tsne_perplexity, args.tsne_iters, args.seed) if args.clustering_tsne else None)
+        if crows:
+            print(f"clustering by site: standardised [a | b] features, silhouette and neighbourhood hit (k={NH_K})"
+                  + (f"; PCA columns: the same on the first {args.clustering_pca} principal components" if args.clustering_pca else "")
+                  + (f"; TSNE columns: the same on the 2-D t-SNE embedding (perplexity {min(args.tsne_perplexity, n_val - 1):g}, "
+                     f"{args.tsne_iters} iterations)" if args.clustering_tsne else ""))
+            print_clustering_table(crows)
+        if args.clustering_out:
+            with open(args.clustering_out, "w") as f:
+                json.dump(crows, f, indent=1)
+    if args.downstream:
+        # the downstream task: after both tables, so that neither depends on the flag
+        table = downstream_table(kind, model, va, B, args.downstream_folds, args.downstream_epochs, args.seed)
+        if table:
+            print(f"downstream task: site classification, {args.downstream_folds} stratified folds, at most {args.downstream_epochs} epochs; "
+                  "accuracy and weighted averages, mean +- std over the folds")
+            print_downstream_table(table)
+        if args.downstream_out:
+            with open(args.downstream_out, "w") as f:
+                json.dump(table, f, indent=1)
     return (rows, crows) if return_clustering else rows
 
 

@@ -22,6 +22,8 @@ TN_GROUP_MAX = 8        # MMVAE_TN_GROUP_MAX
 KNN_MAXK = 96           # MMVAE_KNN_MAXK
 SIL_MAXC = 64           # MMVAE_SIL_MAXC
 PCA_MAXK = 64           # MMVAE_PCA_MAXK
+LN_MAXN = 1024          # MMVAE_LN_MAXN
+WCE_MAXC = 64           # MMVAE_WCE_MAXC
 CTR_COPIES = 16384      # MMVAE_CTR_COPIES: self-advancing device counters are stored as this many identical int64 copies
 
 i32, i64, f32, vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
@@ -185,6 +187,25 @@ class TsneUpdateArgs(C.Structure):
                 ("N", i32), ("momentum", f32), ("learning_rate", f32), ("pad_", i32)]
 
 
+class LnActFwdArgs(C.Structure):
+    _fields_ = [("z", vp), ("gamma", vp), ("beta", vp), ("mask", vp), ("y", vp), ("mean", vp), ("rstd", vp),
+                ("ldz", i64), ("ld_mask", i64), ("ldy", i64),
+                ("M", i32), ("N", i32), ("layer_norm", i32), ("eps", f32), ("inv_keep", f32), ("pad_", i32)]
+
+
+class LnActBwdArgs(C.Structure):
+    _fields_ = [("dy", vp), ("z", vp), ("mean", vp), ("rstd", vp), ("gamma", vp), ("beta", vp), ("mask", vp),
+                ("dz", vp), ("dgamma", vp), ("dbeta", vp), ("work", vp),
+                ("lddy", i64), ("ldz", i64), ("ld_mask", i64), ("lddz", i64), ("work_bytes", i64),
+                ("M", i32), ("N", i32), ("layer_norm", i32), ("inv_keep", f32)]
+
+
+class WceArgs(C.Structure):
+    _fields_ = [("logits", vp), ("labels", vp), ("class_weights", vp), ("sums", vp), ("g", vp), ("pred", vp), ("nll", vp), ("confusion", vp),
+                ("ld", i64), ("ldg", i64),
+                ("M", i32), ("C", i32)]
+
+
 class GatherItem(C.Structure):
     _fields_ = [("src", vp), ("dst", vp), ("src_row_stride", i64), ("dst_row_stride", i64), ("row_bytes", i32), ("pad_", i32)]
 
@@ -232,6 +253,10 @@ _SIGNATURES = {
     "mmvae_tsne_gradient_work_bytes": [i32, i32, C.POINTER(i64)],
     "mmvae_tsne_update": [C.POINTER(TsneUpdateArgs), vp],
     "mmvae_tsne_update_work_bytes": [i32, C.POINTER(i64)],
+    "mmvae_ln_act_fwd": [C.POINTER(LnActFwdArgs), vp],
+    "mmvae_ln_act_bwd": [C.POINTER(LnActBwdArgs), vp],
+    "mmvae_ln_act_bwd_work_bytes": [i32, i32, i32, C.POINTER(i64)],
+    "mmvae_wce_mean": [C.POINTER(WceArgs), vp],
     "mmvae_gather_rows": [vp, i32, vp, i32, i64, vp],
     "mmvae_rows_to_bf16": [vp, i32, i64, vp, i64, i32, i32, vp],
     "mmvae_sigmoid_bwd": [i32, i32, vp, i64, vp, i64, vp, i32, i64, vp],
@@ -240,6 +265,7 @@ _SIGNATURES = {
     "mmvae_noise": [vp, i64, f32, vp, i64, C.c_uint64, C.c_uint64, vp, i32, vp],
     "mmvae_counter_add": [vp, C.c_uint64, vp],
     "mmvae_adamw_step": [vp, i32, f32, f32, f32, f32, f32, f32, f32, i32, vp, i32, vp, vp],
+    "mmvae_adam_step": [vp, i32, f32, f32, f32, f32, f32, f32, f32, i32, vp, i32, vp, vp],
 }
 EXPORTED = ["mmvae_abi_version"] + sorted(_SIGNATURES)
 

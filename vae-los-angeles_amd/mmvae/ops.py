@@ -1058,15 +1058,153 @@ def tsne_update(y, update, gains, grad, momentum, learning_rate, *, grad_norm=Fa
     return gn
 
 
+# --------------------------------------------------------------------------------------------
+# The site classifier of the downstream task (include/mmvae_hip.h: mmvae_ln_act_fwd, mmvae_ln_act_bwd, mmvae_wce_mean)
+# --------------------------------------------------------------------------------------------
+def _ln_operand(t, name, what, rows, cols, dev):
+    """t, an fp32 (rows, cols) device matrix whose rows the kernels read as 16-byte chunks"""
+    t = _f32_matrix(t, name, what, cols)
+    if t.shape[0] != rows or t.device != dev or _ld(t) % 4 or t.data_ptr() % 16:
+        raise ValueError(f"{what}: {name} must be an fp32 ({rows}, {cols}) tensor on the operand's device, 16-byte aligned, row stride a multiple of 4")
+    return t
+
+
+def _ln_mask(mask, p, what, M, N, dev):
+    """(mask, inv_keep): the uint8 keep mask of ops.noise for dropout probability p, or (None, 1) in eval mode / at p = 0"""
+    if mask is None:
+        return None, 1.0
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"{what}: dropout probability {p} outside [0, 1)")
+    if not isinstance(mask, torch.Tensor) or not mask.is_cuda or mask.dtype != torch.uint8 or tuple(mask.shape) != (M, N) or mask.stride(1) != 1 \
+            or _ld(mask) % 4 or mask.data_ptr() % 4 or mask.device != dev:
+        raise ValueError(f"{what}: mask must be a uint8 ({M}, {N}) tensor on the operand's device, 4-byte aligned, row stride a multiple of 4")
+    return mask, 1.0 / (1.0 - p)
+
+
+def _ln_width(N, what):
+    if N % 4 or not 4 <= N <= L.LN_MAXN:
+        raise ValueError(f"{what}: width {N} must be a multiple of 4 in [4, {L.LN_MAXN}]")
+
+
+def ln_act_fwd(z, gamma=None, beta=None, mask=None, p=0.0, eps=1e-5, *, y_out=None, mean_out=None, rstd_out=None):
+    """(y, mean, rstd): Dropout(ReLU(LayerNorm(z))) of z fp32 (M, N) in one launch (mmvae_ln_act_fwd).  mask: the uint8 keep mask of
+    ops.noise for dropout probability p, None = no dropout.  gamma = beta = None: no LayerNorm, y = relu(z) keep / (1 - p) and mean,
+    rstd are None."""
+    what = "ln_act_fwd"
+    z = _f32_matrix(z, "z", what)
+    M, N = z.shape
+    dev = z.device
+    _ln_width(N, what)
+    z = _ln_operand(z, "z", what, M, N, dev)
+    ln = gamma is not None
+    if ln != (beta is not None):
+        raise ValueError(f"{what}: gamma and beta come together")
+    y = _ln_operand(torch.empty(M, N, dtype=torch.float32, device=dev) if y_out is None else y_out, "y_out", what, M, N, dev)
+    mean = rstd = None
+    if ln:
+        for t, name in ((gamma, "gamma"), (beta, "beta")):
+            if _vector(t, name, what, torch.float32, N, dev).data_ptr() % 16:
+                raise ValueError(f"{what}: {name} must be 16-byte aligned")
+        mean = _vector(torch.empty(M, dtype=torch.float32, device=dev) if mean_out is None else mean_out, "mean_out", what, torch.float32, M, dev)
+        rstd = _vector(torch.empty(M, dtype=torch.float32, device=dev) if rstd_out is None else rstd_out, "rstd_out", what, torch.float32, M, dev)
+    mask, inv_keep = _ln_mask(mask, p, what, M, N, dev)
+    a = L.LnActFwdArgs(z.data_ptr(), _p(gamma), _p(beta), _p(mask), y.data_ptr(), _p(mean), _p(rstd), _ld(z), _ld(mask) if mask is not None else 0,
+                       _ld(y), M, N, int(ln), float(eps), inv_keep, 0)
+    with stream_span(what, 9 * M * N):
+        L.check(L.load().mmvae_ln_act_fwd(C.byref(a), _stream()), "mmvae_ln_act_fwd")
+    return y, mean, rstd
+
+
+def ln_act_bwd_work_bytes(M, N, layer_norm=True):
+    return _plan("mmvae_ln_act_bwd_work_bytes", M, N, int(layer_norm), outs=(C.c_int64,))
+
+
+def ln_act_bwd(dy, z, mean=None, rstd=None, gamma=None, beta=None, mask=None, p=0.0, *, dz_out=None, dgamma_out=None, dbeta_out=None, work=None):
+    """(dz, dgamma, dbeta): the backward of ln_act_fwd from dy = dL/dy and the forward's operands (mmvae_ln_act_bwd); dgamma and dbeta
+    are written, bit-identical from run to run.  gamma = None: the form without LayerNorm, dz = dy keep / (1 - p) [z > 0]."""
+    what = "ln_act_bwd"
+    z = _f32_matrix(z, "z", what)
+    M, N = z.shape
+    dev = z.device
+    _ln_width(N, what)
+    z = _ln_operand(z, "z", what, M, N, dev)
+    dy = _ln_operand(dy, "dy", what, M, N, dev)
+    dz = _ln_operand(torch.empty(M, N, dtype=torch.float32, device=dev) if dz_out is None else dz_out, "dz_out", what, M, N, dev)
+    ln = gamma is not None
+    dgamma = dbeta = None
+    if ln:
+        for t, name in ((gamma, "gamma"), (beta, "beta")):
+            if _vector(t, name, what, torch.float32, N, dev).data_ptr() % 16:
+                raise ValueError(f"{what}: {name} must be 16-byte aligned")
+        _vector(mean, "mean", what, torch.float32, M, dev)
+        _vector(rstd, "rstd", what, torch.float32, M, dev)
+        dgamma = _vector(torch.empty(N, dtype=torch.float32, device=dev) if dgamma_out is None else dgamma_out, "dgamma_out", what, torch.float32, N, dev)
+        dbeta = _vector(torch.empty(N, dtype=torch.float32, device=dev) if dbeta_out is None else dbeta_out, "dbeta_out", what, torch.float32, N, dev)
+    mask, inv_keep = _ln_mask(mask, p, what, M, N, dev)
+    nbytes = ln_act_bwd_work_bytes(M, N, ln)
+    if work is None:
+        work = _workspace(nbytes, dev)
+    elif not isinstance(work, torch.Tensor) or work.dtype != torch.int64 or not work.is_contiguous() or work.numel() * 8 < nbytes or work.device != dev:
+        raise ValueError(f"{what}: work must be a contiguous int64 tensor of at least {nbytes} bytes on z's device")
+    a = L.LnActBwdArgs(dy.data_ptr(), z.data_ptr(), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(mask), dz.data_ptr(), _p(dgamma), _p(dbeta), _p(work),
+                       _ld(dy), _ld(z), _ld(mask) if mask is not None else 0, _ld(dz), work.numel() * 8 if work is not None else 0, M, N, int(ln),
+                       inv_keep)
+    with stream_span(what, 13 * M * N):
+        L.check(L.load().mmvae_ln_act_bwd(C.byref(a), _stream()), "mmvae_ln_act_bwd")
+    return dz, dgamma, dbeta
+
+
+def wce_mean(logits, labels, class_weights=None, *, sums=None, grad=False, pred=False, nll=False, confusion=None, grad_out=None, pred_out=None):
+    """(g, pred, nll) of nn.CrossEntropyLoss(weight=class_weights) with its mean reduction over logits fp32 (M, C) and labels int64 (M,)
+    (mmvae_wce_mean).  sums: a float64 (3,) device tensor that is ADDED to: sum w nll, sum w, labels out of range (the loss is
+    sums[0] / sums[1]; a non-zero sums[2] is the caller's to raise on).  g fp32 (M, C): the gradient of that mean w.r.t. the logits;
+    pred int32 (M,): the argmax, the first maximum on ties; nll fp32 (M,): the unweighted row terms; confusion: an int32 (C, C) device
+    tensor whose [label][prediction] counts are incremented.  Outputs that are not asked for are None."""
+    what = "wce_mean"
+    x = _f32_matrix(logits, "logits", what)
+    M, Cn = x.shape
+    dev = x.device
+    if not 2 <= Cn <= L.WCE_MAXC:
+        raise ValueError(f"{what}: {Cn} classes outside [2, {L.WCE_MAXC}]")
+    _vector(labels, "labels", what, torch.int64, M, dev)
+    if class_weights is not None:
+        _vector(class_weights, "class_weights", what, torch.float32, Cn, dev)
+    if sums is not None:
+        _vector(sums, "sums", what, torch.float64, 3, dev)
+    g = _out_view(grad_out, "grad_out", what, torch.float32, M, Cn, dev) if grad or grad_out is not None else None
+    pr = _vector(torch.empty(M, dtype=torch.int32, device=dev) if pred_out is None else pred_out, "pred_out", what, torch.int32, M, dev) \
+        if pred or pred_out is not None else None
+    nl = torch.empty(M, dtype=torch.float32, device=dev) if nll else None
+    if confusion is not None and (not isinstance(confusion, torch.Tensor) or not confusion.is_cuda or confusion.dtype != torch.int32
+                                  or tuple(confusion.shape) != (Cn, Cn) or not confusion.is_contiguous() or confusion.device != dev):
+        raise ValueError(f"{what}: confusion must be a contiguous int32 ({Cn}, {Cn}) tensor on the operand's device")
+    if sums is None and g is None and pr is None and nl is None and confusion is None:
+        raise ValueError(f"{what}: no output asked for")
+    a = L.WceArgs(x.data_ptr(), labels.data_ptr(), _p(class_weights), _p(sums), _p(g), _p(pr), _p(nl), _p(confusion), _ld(x),
+                  _ld(g) if g is not None else 0, M, Cn)
+    with stream_span(what, 8 * M * Cn):
+        L.check(L.load().mmvae_wce_mean(C.byref(a), _stream()), "mmvae_wce_mean")
+    return g, pr, nl
+
+
+def _adam_launch(symbol, span, items, lr, b1, b2, eps, wd, bc1, bc2, maximize, step_dev, lr_dev):
+    tick = step_dev is not None and len(items) <= 64
+    if step_dev is not None:
+        assert step_dev.numel() == L.CTR_COPIES and step_dev.dtype == torch.int64
+    with stream_span(span, lambda: 28 * sum(it.n for it in items)):
+        L.check(getattr(L.load(), symbol)(C.cast(items, C.c_void_p), len(items), lr, b1, b2, eps, wd, bc1, bc2, int(maximize),
+                                          _p(step_dev), int(tick), _p(lr_dev), _stream()), symbol)
+    if step_dev is not None and not tick:
+        step_dev.add_(1)
+
+
 def adamw_step(items, lr, b1, b2, eps, wd, bc1, bc2, maximize=False, step_dev=None, lr_dev=None):
     """items: ctypes array of AdamWItem in host memory (device pointers inside).  step_dev: int64[CTR_COPIES] tensor of
     identical copies of the step count: bias corrections from the device counter, which the launch itself increments
     (<= 64 tensors; beyond that the copies are advanced by a fill after the launches)."""
-    tick = step_dev is not None and len(items) <= 64
-    if step_dev is not None:
-        assert step_dev.numel() == L.CTR_COPIES and step_dev.dtype == torch.int64
-    with stream_span("adamw", lambda: 28 * sum(it.n for it in items)):
-        L.check(L.load().mmvae_adamw_step(C.cast(items, C.c_void_p), len(items), lr, b1, b2, eps, wd, bc1, bc2, int(maximize),
-                                          _p(step_dev), int(tick), _p(lr_dev), _stream()), "mmvae_adamw_step")
-    if step_dev is not None and not tick:
-        step_dev.add_(1)
+    _adam_launch("mmvae_adamw_step", "adamw", items, lr, b1, b2, eps, wd, bc1, bc2, maximize, step_dev, lr_dev)
+
+
+def adam_step(items, lr, b1, b2, eps, wd, bc1, bc2, maximize=False, step_dev=None, lr_dev=None):
+    """adamw_step with torch.optim.Adam's decay: wd * p joins the gradient instead of scaling p (mmvae_adam_step)."""
+    _adam_launch("mmvae_adam_step", "adam", items, lr, b1, b2, eps, wd, bc1, bc2, maximize, step_dev, lr_dev)
