@@ -508,6 +508,22 @@ int mmvae_knn_work_bytes(int32_t Mq, int32_t Nt, int32_t k, int64_t* bytes);
  * launch. */
 int mmvae_knn_splits(int32_t Mq, int32_t Nt, int32_t* splits, int32_t* rows_per_split);
 
+/* The manhattan (L1) search: the k nearest training rows of every query row under sum_c |q_ic - t_jc|, for the tuned k-NN baseline of
+ * the reference (src/knn_comparison/run_comparison.py:56-94, metric='manhattan').  Takes mmvae_knn_args unchanged; q, t, idx, the
+ * order (key, j) ascending with the smaller training index first among equal keys, NaN after +inf, the limits, the decomposition
+ * (mmvae_knn_splits), the merge and the refusals are those of mmvae_knn_search.  What differs:
+ *   shift must be NULL (MMVAE_ERR_ARG otherwise): differences are formed directly, there is nothing to condition.
+ *   key = sum_{c = 0 .. F-1} |fl(q_ic - t_jc)| in fp32, bf16 widened exactly: ONE chain of plain adds in ascending column order,
+ *   starting from +0 -- ((|d_0| + |d_1|) + |d_2|) + ..., never reassociated.  The key of a pair depends only on the two rows' values
+ *   and F (not on position, Mq, Nt, k or the split), duplicate training rows tie bit for bit, and a sequential float32 loop on the
+ *   host gives the same bits.  Columns beyond F that a chunk pads with zeros add +0.
+ *   dist2 (optional) receives the L1 distance ITSELF, which is the key: it is NOT squared in this entry.
+ *   work holds only the split lists: mmvae_knn_l1_work_bytes = 8 Mq k splits bytes when split, else 0; work may then be NULL.  There
+ *   is no norms launch.
+ * The distances are VALU work (a subtract and an add with |.| per pair and column), not a GEMM. */
+int mmvae_knn_search_l1(const mmvae_knn_args* args, void* stream);
+int mmvae_knn_l1_work_bytes(int32_t Mq, int32_t Nt, int32_t k, int64_t* bytes);
+
 /* Uniform k-NN regression from the indices of mmvae_knn_search:  out[i][:] = (sum_{n<k} y[idx[i][n]][:]) / k, in fp32, summed in
  * ascending n (deterministic; what KNeighborsRegressor.predict with uniform weights computes, conditioned_knn.py:84-91).
  * y [Ny][Fy]: MMVAE_F32 or MMVAE_BF16 rows (ld_y >= Fy), out [Mq][Fy] fp32 (ld_out >= Fy), idx [Mq][k] int32 (ld_idx >= k); indices
@@ -516,6 +532,18 @@ int mmvae_knn_splits(int32_t Mq, int32_t Nt, int32_t* splits, int32_t* rows_per_
  * MMVAE_ERR_DTYPE: another y_dtype. */
 int mmvae_knn_mean_rows(const int32_t* idx, int64_t ld_idx, const void* y, int32_t y_dtype, int64_t ld_y, float* out, int64_t ld_out,
                         int32_t Mq, int32_t k, int32_t Ny, int32_t Fy, void* stream);
+
+/* Inverse-distance k-NN regression (sklearn's weights='distance', sklearn.neighbors._base._get_weights) from the indices and distances
+ * of a search:  d_n = dist[i][n], or with dist_is_squared = 1 (the euclidean dist2) its correctly rounded square root.  If any d_n == 0
+ * in the row, w_n = 1 where d_n == 0 and 0 elsewhere; otherwise w_n = 1 / d_n (correctly rounded).  Then
+ *   out[i][:] = (sum_n w_n y[idx[i][n]][:]) / (sum_n w_n)   in fp32, both sums in ascending n (each product rounded, then added), one
+ * correctly rounded division.  A NaN or negative distance in a row gives a NaN row, no fault.
+ * idx [Mq][k] int32 and dist [Mq][k] fp32 with ld_idx, ld_dist >= k: the first k columns of a wider search can be passed in place.
+ * y, out, the index clamp, the limits and the refusals are those of mmvae_knn_mean_rows; also MMVAE_ERR_ARG: a null or misaligned
+ * dist, ld_dist < k, dist_is_squared outside {0, 1}.  A streaming gather: a row's k weights are computed once per workgroup. */
+int mmvae_knn_weighted_rows(const int32_t* idx, int64_t ld_idx, const float* dist, int64_t ld_dist, int32_t dist_is_squared,
+                            const void* y, int32_t y_dtype, int64_t ld_y, float* out, int64_t ld_out,
+                            int32_t Mq, int32_t k, int32_t Ny, int32_t Fy, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Silhouette coefficient of every row (sklearn.metrics.silhouette_samples, euclidean) as a distance GEMM whose epilogue is a square

@@ -18,18 +18,20 @@
 // Split: grid.y workgroups per query block take consecutive runs of tiles; their lists go to the workspace and knn_merge_kernel ranks
 // every entry among all lists of its row (own position + binary searches in the others): fixed order, no atomics.
 // The squared norms |q_i - c|^2, |t_j - c|^2 come from one streaming launch (rt_norms_launch: a wave per row) into the workspace.
+// The manhattan search (mmvae_knn_search_l1) is the same kernel with another inner loop (L1 = true): l1_chunk accumulates |q - t| on
+// the VALU in the accumulator layout of the MFMA, one fp32 chain per pair in ascending column order; no norms, no shift.  The
+// selection (knn_select.h) is shared.  mmvae_knn_weighted_rows is the inverse-distance sibling of mmvae_knn_mean_rows.
 #include "common.h"
 #include "wave_slab.h"
 #include "row_tile.h"
+#include "knn_select.h"
 
 namespace mm {
 
-constexpr int KNN_BM = 128, KNN_BN = 128;       // query rows of a workgroup, training rows of a tile
 constexpr int KNN_TILE_BYTES = (KNN_BM + KNN_BN) * RT_LDR * 4;
 constexpr int knn_max_lds(int slots) { return KNN_TILE_BYTES + KNN_BM * 16 * slots * 8; }   // operand tile + 128 lists of 16 slots entries
 constexpr int KNN_TARGET_WG = 4 * NUM_CU;      // below this many query blocks the training rows are split
 constexpr int KNN_MAX_SPLITS = 64;
-constexpr unsigned long long KNN_EMPTY = ~0ull;
 constexpr int KNN_SLOTS = MMVAE_KNN_MAXK / 16;  // list positions a lane of a row group rewrites at most
 static_assert(MMVAE_KNN_MAXK % 16 == 0 && KNN_SLOTS * 16 == MMVAE_KNN_MAXK, "knn_insert: 16 lanes x KNN_SLOTS positions");
 static_assert(knn_max_lds(KNN_SLOTS) <= 160 * 1024, "knn_kernel: operand tile + 128 lists of MMVAE_KNN_MAXK entries in one workgroup's LDS");
@@ -44,53 +46,40 @@ struct KnnP {
     int* idx; long ldi; float* dist2; long ldd;
 };
 
-// fp32 key -> unsigned with the same order; -0 = +0, every NaN one value above +inf
-__device__ __forceinline__ unsigned knn_order(float key) {
-    key += 0.f;
-    unsigned b = __float_as_uint(key);
-    if (key != key) b = 0x7FC00000u;
-    return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-__device__ __forceinline__ float knn_key(unsigned u) { return __uint_as_float((u >> 31) ? (u ^ 0x80000000u) : ~u); }
-
-// The 16 lanes of a row group (lane >> 4) insert their passing candidates into the group's list, one at a time; the wave's four groups
-// in lock step.  L: this lane's group's list (k sorted entries).  S: positions per lane, 16 S >= k.  The kernel is instantiated for
-// S = 4 (k <= 64: the code of every search before MMVAE_KNN_MAXK grew, instruction for instruction) and for S = KNN_SLOTS beyond; one
-// kernel holding both inserts at its 64 call sites ran the k = 50 search a third slower.
-template <int S>
-__device__ __forceinline__ void knn_insert(unsigned long long* L, bool pass, unsigned long long cand, int lane, int k) {
-    const int li = lane & 15, g0 = lane & 48;
-    unsigned long long pend = __ballot(pass);
-    while (pend) {
-        const unsigned gm = (unsigned)(pend >> g0) & 0xFFFFu;
-        const bool act = gm != 0;
-        const int src = g0 + (act ? __ffs(gm) - 1 : 0);
-        const unsigned long long c = __shfl(cand, src, WAVE);
-        unsigned long long nv[S];
-        bool wr[S];
+// The manhattan search's sibling of mma_chunk: acc[mi][ni][r] += sum over the chunk's columns of |q_row[c] - t_col[c]|, every element ONE
+// chain of plain fp32 adds in ascending column order (a subtract, then an add whose source takes the abs modifier), a lane owning the
+// 64 (row, column) pairs it owns in the MFMA accumulator layout so that the selection applies unchanged.  Per 4 columns a lane reads
+// 16 q fragments (4 addresses per wave: broadcasts) and 4 t fragments (16 rows, 36 floats apart: conflict free) for 512 VALU operations.
+__device__ __forceinline__ void l1_chunk(f32x4 (&acc)[4][4], const float* sQ, int row0, const float* sT, int col0, const RtMap& m) {
+#pragma unroll 2
+    for (int g = 0; g < RT_BK / 4; ++g) {
+        f32x4 ft[4];
 #pragma unroll
-        for (int s = 0; s < S; ++s) {
-            const int p = li + 16 * s;
-            wr[s] = false;
-            nv[s] = 0;
-            if (act && p < k) {
-                const unsigned long long e = L[p];
-                const unsigned long long prev = p ? L[p - 1] : 0ull;
-                wr[s] = e > c;
-                nv[s] = prev > c ? prev : c;
+        for (int ni = 0; ni < 4; ++ni) ft[ni] = *(const f32x4*)(sT + (col0 + 16 * ni + m.li) * RT_LDR + 4 * g);
+#pragma unroll
+        for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const f32x4 fq = *(const f32x4*)(sQ + (row0 + 16 * mi + 4 * m.lg + r) * RT_LDR + 4 * g);
+#pragma unroll
+                for (int ni = 0; ni < 4; ++ni)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) acc[mi][ni][r] += __builtin_fabsf(fq[j] - ft[ni][j]);
             }
-        }
-        wave_lds_sync();                                   // every position is read before any is rewritten
-#pragma unroll
-        for (int s = 0; s < S; ++s)
-            if (wr[s]) L[li + 16 * s] = nv[s];
-        wave_lds_sync();
-        if (lane == src) pass = false;
-        pend = __ballot(pass);
     }
 }
 
-template <typename TQ, typename TT, int S>
+// L1 = false: the euclidean search (keys from the MFMA dot products and the training norms).  L1 = true: the manhattan search
+// (mmvae_knn_search_l1): the same pipeline, lists, split and merge; the accumulator is the key and the distance.
+// what dist2 receives for a list entry: key + |q_i - c|^2 clamped at 0, or (L1) the key, which is the distance
+template <bool L1>
+__device__ __forceinline__ float knn_dist(unsigned long long e, const float* qn, long row) {
+    const float key = knn_key((unsigned)(e >> 32));
+    if constexpr (L1) return key;
+    else { const float d = key + qn[row]; return d < 0.f ? 0.f : d; }
+}
+
+template <typename TQ, typename TT, int S, bool L1>
 __global__ __launch_bounds__(RT_THREADS) void knn_kernel(KnnP a) {
     extern __shared__ __align__(16) unsigned char knn_smem[];
     float* sQ = (float*)knn_smem;                          // [KNN_BM][RT_LDR]
@@ -144,37 +133,44 @@ __global__ __launch_bounds__(RT_THREADS) void knn_kernel(KnnP a) {
         int ntile = tile, nchk = ch + 1;
         if (nchk == nch) { nchk = 0; ++ntile; }
         if (s + 1 < nsteps) issue(ntile, nchk);
-        mma_chunk(acc, sQ, m.wr * 64, sT, wc * 64, m);
+        if constexpr (L1) l1_chunk(acc, sQ, m.wr * 64, sT, wc * 64, m);
+        else mma_chunk(acc, sQ, m.wr * 64, sT, wc * 64, m);
         if (nchk == 0) {
-            // the tile is complete: acc[mi][ni][r] = (q_row - c).(t_j - c), row = acc_row, j = tile*128 + acc_col
-            for (int phase = 0; phase < 2; ++phase) {
-                if (wc == phase) {
-                    float tnv[4];
-                    bool jok[4];
-                    unsigned jlo[4];
+            // the tile is complete: acc[mi][ni][r] = (q_row - c).(t_j - c) or |q_row - t_j|_1, row = acc_row, j = tile*128 + acc_col
+            // The euclidean kernel keeps the selection written out here, as it always was: calling the shared knn_select_tile instead
+            // compiled to 15 more integer multiplies per tile and measured 0.15 - 0.18 % slower, outside the spread of repeats.
+            if constexpr (L1) {
+                knn_select_tile<S>(acc, sL, m, tile, a.Nt, nr, k, kp);
+            } else {
+                for (int phase = 0; phase < 2; ++phase) {
+                    if (wc == phase) {
+                        float tnv[4];
+                        bool jok[4];
+                        unsigned jlo[4];
 #pragma unroll
-                    for (int ni = 0; ni < 4; ++ni) {
-                        const long j = (long)tile * KNN_BN + m.acc_col(wc * 64, ni);
-                        jok[ni] = j < a.Nt;
-                        jlo[ni] = (unsigned)j;
-                        tnv[ni] = jok[ni] ? a.tn[j] : 0.f;
-                    }
-#pragma unroll
-                    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const int row = m.acc_row(m.wr * 64, mi, r);
-                            unsigned long long* L = sL + row * kp;
-                            const unsigned thr = (unsigned)(L[k - 1] >> 32);
-#pragma unroll
-                            for (int ni = 0; ni < 4; ++ni) {
-                                const unsigned u = knn_order(tnv[ni] - 2.f * acc[mi][ni][r]);
-                                const bool pass = jok[ni] && row < nr && u <= thr;
-                                if (__any(pass)) knn_insert<S>(L, pass, ((unsigned long long)u << 32) | jlo[ni], lane, k);
-                            }
+                        for (int ni = 0; ni < 4; ++ni) {
+                            const long j = (long)tile * KNN_BN + m.acc_col(wc * 64, ni);
+                            jok[ni] = j < a.Nt;
+                            jlo[ni] = (unsigned)j;
+                            tnv[ni] = jok[ni] ? a.tn[j] : 0.f;
                         }
+#pragma unroll
+                        for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) {
+                                const int row = m.acc_row(m.wr * 64, mi, r);
+                                unsigned long long* L = sL + row * kp;
+                                const unsigned thr = (unsigned)(L[k - 1] >> 32);
+#pragma unroll
+                                for (int ni = 0; ni < 4; ++ni) {
+                                    const unsigned u = knn_order(tnv[ni] - 2.f * acc[mi][ni][r]);
+                                    const bool pass = jok[ni] && row < nr && u <= thr;
+                                    if (__any(pass)) knn_insert<S>(L, pass, ((unsigned long long)u << 32) | jlo[ni], lane, k);
+                                }
+                            }
+                    }
+                    __syncthreads();
                 }
-                __syncthreads();
             }
             zero_acc(acc);
         }
@@ -187,13 +183,14 @@ __global__ __launch_bounds__(RT_THREADS) void knn_kernel(KnnP a) {
         if (a.part) a.part[((q0 + row) * a.nsplit + split) * k + n] = e;
         else {
             a.idx[(q0 + row) * a.ldi + n] = (int)(unsigned)e;
-            if (a.dist2) { const float d = knn_key((unsigned)(e >> 32)) + a.qn[q0 + row]; a.dist2[(q0 + row) * a.ldd + n] = d < 0.f ? 0.f : d; }
+            if (a.dist2) a.dist2[(q0 + row) * a.ldd + n] = knn_dist<L1>(e, a.qn, q0 + row);
         }
     }
 }
 
 // One wave per query row: the rank of an entry among all lists of the row is its own position plus its lower bounds in the others
 // (the entries of a row are distinct: every j is in one split).  Empty slots (a split with fewer than k rows) rank last and are skipped.
+template <bool L1>
 __global__ __launch_bounds__(WAVE) void knn_merge_kernel(KnnP a) {
     const long row = blockIdx.x;
     const int k = a.k, ns = a.nsplit;
@@ -212,7 +209,7 @@ __global__ __launch_bounds__(WAVE) void knn_merge_kernel(KnnP a) {
         }
         if (rank < k) {
             a.idx[row * a.ldi + rank] = (int)(unsigned)v;
-            if (a.dist2) { const float d = knn_key((unsigned)(v >> 32)) + a.qn[row]; a.dist2[row * a.ldd + rank] = d < 0.f ? 0.f : d; }
+            if (a.dist2) a.dist2[row * a.ldd + rank] = knn_dist<L1>(v, a.qn, row);
         }
     }
 }
@@ -233,14 +230,54 @@ __global__ __launch_bounds__(KNN_MEAN_THREADS) void knn_mean_kernel(const int* i
     out[row * ldo + c] = s / (float)k;
 }
 
-template <int S>
+// Inverse-distance k-NN regression (mmvae_knn_weighted_rows): a workgroup owns one query row and 256 output columns.  The row's k
+// weights (sklearn's _get_weights: 1 / d, or the indicator of d == 0 when any distance is 0) and clamped indices are computed once, into
+// LDS; then every thread streams its column of the k neighbour rows: numerator and weight sum in ascending n, one division.
+template <typename T>
+__global__ __launch_bounds__(KNN_MEAN_THREADS) void knn_weighted_kernel(const int* idx, long ldi, const float* dist, long ldd, int squared,
+                                                                   const T* y, long ldy, float* out, long ldo, int k, int Ny, int Fy) {
+    __shared__ float sW[MMVAE_KNN_MAXK];
+    __shared__ long sJ[MMVAE_KNN_MAXK];
+    __shared__ int sFlag[2];                               // [0]: some distance is 0, [1]: some distance is NaN or negative
+    const long row = blockIdx.x;
+    const int tid = threadIdx.x;
+    if (tid < 2) sFlag[tid] = 0;
+    __syncthreads();
+    float d = 1.f;
+    if (tid < k) {
+        d = dist[row * ldd + tid];
+        if (squared) d = __fsqrt_rn(d);
+        if (d == 0.f) sFlag[0] = 1;                        // every writer stores the same value
+        if (!(d >= 0.f)) sFlag[1] = 1;
+        long j = idx[row * ldi + tid];
+        sJ[tid] = j < 0 ? 0 : (j >= Ny ? (long)Ny - 1 : j);
+    }
+    __syncthreads();
+    if (tid < k) {
+        float w = sFlag[0] ? (d == 0.f ? 1.f : 0.f) : __fdiv_rn(1.f, d);
+        if (sFlag[1]) w = __uint_as_float(0x7FC00000u);
+        sW[tid] = w;
+    }
+    __syncthreads();
+    const int c = blockIdx.y * KNN_MEAN_THREADS + tid;
+    if (c >= Fy) return;
+    float s = 0.f, ws = 0.f;
+    for (int n = 0; n < k; ++n) {
+        const float w = sW[n];
+        s = __fadd_rn(s, __fmul_rn(w, to_f32(y[sJ[n] * ldy + c])));
+        ws += w;
+    }
+    out[row * ldo + c] = __fdiv_rn(s, ws);
+}
+
+template <int S, bool L1>
 static int knn_launch(int q_dtype, int t_dtype, const KnnP& p, dim3 grid, int lds, hipStream_t st) {
     constexpr int MAX_LDS = knn_max_lds(S);
     if (q_dtype == MMVAE_F32)
-        return t_dtype == MMVAE_F32 ? rt_launch_dyn_lds<knn_kernel<float, float, S>, MAX_LDS>(p, grid, lds, st)
-                                    : rt_launch_dyn_lds<knn_kernel<float, bf16, S>, MAX_LDS>(p, grid, lds, st);
-    return t_dtype == MMVAE_F32 ? rt_launch_dyn_lds<knn_kernel<bf16, float, S>, MAX_LDS>(p, grid, lds, st)
-                                : rt_launch_dyn_lds<knn_kernel<bf16, bf16, S>, MAX_LDS>(p, grid, lds, st);
+        return t_dtype == MMVAE_F32 ? rt_launch_dyn_lds<knn_kernel<float, float, S, L1>, MAX_LDS>(p, grid, lds, st)
+                                    : rt_launch_dyn_lds<knn_kernel<float, bf16, S, L1>, MAX_LDS>(p, grid, lds, st);
+    return t_dtype == MMVAE_F32 ? rt_launch_dyn_lds<knn_kernel<bf16, float, S, L1>, MAX_LDS>(p, grid, lds, st)
+                                : rt_launch_dyn_lds<knn_kernel<bf16, bf16, S, L1>, MAX_LDS>(p, grid, lds, st);
 }
 
 static bool knn_sizes_ok(int Mq, int Nt, int k) { return Mq >= 1 && Nt >= 1 && k >= 1 && k <= Nt && k <= MMVAE_KNN_MAXK; }
@@ -276,9 +313,21 @@ extern "C" int mmvae_knn_splits(int32_t Mq, int32_t Nt, int32_t* splits, int32_t
     return MMVAE_OK;
 }
 
-extern "C" int mmvae_knn_search(const mmvae_knn_args* a, void* stream) {
+extern "C" int mmvae_knn_l1_work_bytes(int32_t Mq, int32_t Nt, int32_t k, int64_t* bytes) {
     using namespace mm;
-    if (!a || !a->q || !a->t || !a->idx || !a->work) return MMVAE_ERR_ARG;
+    if (!bytes || !knn_sizes_ok(Mq, Nt, k)) return MMVAE_ERR_ARG;
+    int nsplit, tps;
+    knn_plan(Mq, Nt, &nsplit, &tps);
+    *bytes = nsplit > 1 ? 8L * Mq * nsplit * k : 0L;
+    return MMVAE_OK;
+}
+
+namespace mm {
+// both searches: the checks, the plan, (euclidean) the norms launch, the search and the merge
+template <bool L1>
+static int knn_search_impl(const mmvae_knn_args* a, void* stream) {
+    if (!a || !a->q || !a->t || !a->idx) return MMVAE_ERR_ARG;
+    if (L1 ? a->shift != nullptr : !a->work) return MMVAE_ERR_ARG;
     if (a->F < 1 || !knn_sizes_ok(a->Mq, a->Nt, a->k)) return MMVAE_ERR_ARG;
     RtOperand oq, ot;
     const int rq = rt_operand(a->q, a->q_dtype, a->ld_q, a->F, &oq), rt = rt_operand(a->t, a->t_dtype, a->ld_t, a->F, &ot);
@@ -286,7 +335,8 @@ extern "C" int mmvae_knn_search(const mmvae_knn_args* a, void* stream) {
     if (rq || rt || a->ld_idx < a->k || (a->dist2 && a->ld_dist2 < a->k)) return MMVAE_ERR_ARG;
     if ((uintptr_t)a->shift % 4 || (uintptr_t)a->idx % 4 || (uintptr_t)a->dist2 % 4 || (uintptr_t)a->work % 8) return MMVAE_ERR_ARG;
     int64_t need;
-    if (mmvae_knn_work_bytes(a->Mq, a->Nt, a->k, &need) != MMVAE_OK || a->work_bytes < need) return MMVAE_ERR_ARG;
+    if ((L1 ? mmvae_knn_l1_work_bytes(a->Mq, a->Nt, a->k, &need) : mmvae_knn_work_bytes(a->Mq, a->Nt, a->k, &need)) != MMVAE_OK) return MMVAE_ERR_ARG;
+    if (need > 0 && (!a->work || a->work_bytes < need)) return MMVAE_ERR_ARG;
 
     KnnP p;
     p.q = a->q; p.t = a->t; p.shift = a->shift;
@@ -294,25 +344,31 @@ extern "C" int mmvae_knn_search(const mmvae_knn_args* a, void* stream) {
     p.vq = oq.vec; p.vt = ot.vec;
     p.Mq = a->Mq; p.Nt = a->Nt; p.F = a->F; p.k = a->k; p.kp = (a->k + 15) & ~15;
     knn_plan(a->Mq, a->Nt, &p.nsplit, &p.tps);
-    float* norms = (float*)a->work;
-    p.qn = norms; p.tn = norms + a->Mq;
-    p.part = p.nsplit > 1 ? (unsigned long long*)((char*)a->work + knn_norm_bytes(a->Mq, a->Nt)) : nullptr;
+    float* norms = L1 ? nullptr : (float*)a->work;
+    p.qn = norms; p.tn = L1 ? nullptr : norms + a->Mq;
+    const long lists_at = L1 ? 0 : knn_norm_bytes(a->Mq, a->Nt);
+    p.part = p.nsplit > 1 ? (unsigned long long*)((char*)a->work + lists_at) : nullptr;
     p.idx = a->idx; p.ldi = a->ld_idx; p.dist2 = a->dist2; p.ldd = a->ld_dist2;
     hipStream_t st = (hipStream_t)stream;
 
-    int rc = rt_norms_launch({a->q, a->ld_q, a->q_dtype, a->Mq, nullptr}, {a->t, a->ld_t, a->t_dtype, a->Nt, nullptr}, a->F, a->shift, norms, st);
+    int rc = 0;
+    if (!L1) rc = rt_norms_launch({a->q, a->ld_q, a->q_dtype, a->Mq, nullptr}, {a->t, a->ld_t, a->t_dtype, a->Nt, nullptr}, a->F, a->shift, norms, st);
     if (rc) return rc;
 
     const dim3 grid((unsigned)(((long)a->Mq + KNN_BM - 1) / KNN_BM), (unsigned)p.nsplit);
     const int lds = KNN_TILE_BYTES + KNN_BM * p.kp * 8;
-    rc = p.kp <= 64 ? knn_launch<4>(a->q_dtype, a->t_dtype, p, grid, lds, st) : knn_launch<KNN_SLOTS>(a->q_dtype, a->t_dtype, p, grid, lds, st);
+    rc = p.kp <= 64 ? knn_launch<4, L1>(a->q_dtype, a->t_dtype, p, grid, lds, st) : knn_launch<KNN_SLOTS, L1>(a->q_dtype, a->t_dtype, p, grid, lds, st);
     if (rc) return rc;
     if (p.nsplit > 1) {
-        hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)a->Mq), dim3(WAVE), 0, st, p);
+        hipLaunchKernelGGL(knn_merge_kernel<L1>, dim3((unsigned)a->Mq), dim3(WAVE), 0, st, p);
         MM_CHECK_LAUNCH();
     }
     return MMVAE_OK;
 }
+}  // namespace mm
+
+extern "C" int mmvae_knn_search(const mmvae_knn_args* a, void* stream) { return mm::knn_search_impl<false>(a, stream); }
+extern "C" int mmvae_knn_search_l1(const mmvae_knn_args* a, void* stream) { return mm::knn_search_impl<true>(a, stream); }
 
 extern "C" int mmvae_knn_mean_rows(const int32_t* idx, int64_t ld_idx, const void* y, int32_t y_dtype, int64_t ld_y, float* out, int64_t ld_out,
                                    int32_t Mq, int32_t k, int32_t Ny, int32_t Fy, void* stream) {
@@ -329,6 +385,29 @@ extern "C" int mmvae_knn_mean_rows(const int32_t* idx, int64_t ld_idx, const voi
         hipLaunchKernelGGL((knn_mean_kernel<float>), grid, dim3(KNN_MEAN_THREADS), 0, st, idx, (long)ld_idx, (const float*)y, (long)ld_y, out, (long)ld_out, k, Ny, Fy);
     else
         hipLaunchKernelGGL((knn_mean_kernel<bf16>), grid, dim3(KNN_MEAN_THREADS), 0, st, idx, (long)ld_idx, (const bf16*)y, (long)ld_y, out, (long)ld_out, k, Ny, Fy);
+    MM_CHECK_LAUNCH();
+    return MMVAE_OK;
+}
+
+extern "C" int mmvae_knn_weighted_rows(const int32_t* idx, int64_t ld_idx, const float* dist, int64_t ld_dist, int32_t dist_is_squared,
+                                       const void* y, int32_t y_dtype, int64_t ld_y, float* out, int64_t ld_out,
+                                       int32_t Mq, int32_t k, int32_t Ny, int32_t Fy, void* stream) {
+    using namespace mm;
+    if (!idx || !dist || !y || !out || Mq < 1 || k < 1 || k > MMVAE_KNN_MAXK || Ny < 1 || Fy < 1) return MMVAE_ERR_ARG;
+    RtOperand oy;
+    if (const int rc = rt_operand(y, y_dtype, ld_y, Fy, &oy)) return rc;
+    if (ld_idx < k || ld_dist < k || ld_out < Fy || (dist_is_squared != 0 && dist_is_squared != 1)) return MMVAE_ERR_ARG;
+    if ((uintptr_t)idx % 4 || (uintptr_t)dist % 4 || (uintptr_t)out % 4) return MMVAE_ERR_ARG;
+    const long ct = ((long)Fy + KNN_MEAN_THREADS - 1) / KNN_MEAN_THREADS;
+    if (ct > 65535) return MMVAE_ERR_ARG;
+    const dim3 grid((unsigned)Mq, (unsigned)ct);
+    hipStream_t st = (hipStream_t)stream;
+    if (y_dtype == MMVAE_F32)
+        hipLaunchKernelGGL((knn_weighted_kernel<float>), grid, dim3(KNN_MEAN_THREADS), 0, st, idx, (long)ld_idx, dist, (long)ld_dist, dist_is_squared,
+                           (const float*)y, (long)ld_y, out, (long)ld_out, k, Ny, Fy);
+    else
+        hipLaunchKernelGGL((knn_weighted_kernel<bf16>), grid, dim3(KNN_MEAN_THREADS), 0, st, idx, (long)ld_idx, dist, (long)ld_dist, dist_is_squared,
+                           (const bf16*)y, (long)ld_y, out, (long)ld_out, k, Ny, Fy);
     MM_CHECK_LAUNCH();
     return MMVAE_OK;
 }

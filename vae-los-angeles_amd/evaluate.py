@@ -10,6 +10,12 @@ beside every target modality the mean-imputation baseline (training-set column m
 --knn K adds the reference's second baseline, KNeighborsRegressor(n_neighbors=K) from the other modality fitted on the training rows
 (compare_directional_imputation.py:235-254), --knn-by-site its per-site form (src/models/conditioned_knn.py); both search on the
 device (mmvae.knn).
+--knn-tune adds the reference's tuned baseline (src/knn_comparison/run_comparison.py:56-94, optimize_knn): per target modality the
+16-point grid n_neighbors {5, 10, 20, 50} x weights {uniform, distance} x metric {euclidean, manhattan} is fitted on the training rows
+and scored on the validation rows, the winner becomes the row kNN-tuned(k=..,w=..,m=..) (with --knn-by-site also kNN-site-tuned(..), the
+conditioned regressor's own grid) -- two searches per route serve all 16 points (mmvae.knn.optimize_knn).  --knn-tune-out FILE holds
+per route the grid, the winner and the per-sample MSE summary (min, quartiles, max, mean: the reference's box plots) of the winner
+beside the model's.
 --clustering adds the reference's clustering table (src/clustering_evaluation/cluster_imputation_methods.py:478-504): silhouette score
 and neighbourhood hit (k = 5) of the standardised features [a | b] against the validation sites -- for the true features and, per
 single-target imputation route, with the target part replaced by the model's, the mean's and (with --knn) the k-NN imputations; both
@@ -63,7 +69,9 @@ def build_parser(kind):
     ap.add_argument("--checkpoint-dir", default=Config.CHECKPOINT_DIR)
     ap.add_argument("--seed", type=int, default=Config.RANDOM_SEED, help="Philox stream of eps")
     ap.add_argument("--knn", type=int, default=0, metavar="K", help="add a kNN(k=K) imputation row per target modality (0 = off)")
-    ap.add_argument("--knn-by-site", action="store_true", help="with --knn: add the per-site (conditioned) k-NN rows as well")
+    ap.add_argument("--knn-by-site", action="store_true", help="with --knn / --knn-tune: add the per-site (conditioned) k-NN rows as well")
+    ap.add_argument("--knn-tune", action="store_true", help="add the tuned k-NN row per target modality: the winner of the reference's 16-point grid")
+    ap.add_argument("--knn-tune-out", default=None, help="with --knn-tune: write the grids, the winners and the per-sample MSE summaries as JSON here")
     ap.add_argument("--out", default=None, help="write the table rows as JSON here")
     ap.add_argument("--clustering", action="store_true", help="add the clustering table: silhouette and neighbourhood hit (k=5) by site")
     ap.add_argument("--clustering-out", default=None, help="with --clustering: write that table's rows as JSON here")
@@ -91,6 +99,15 @@ def routes(kind):
             ("a+b+site->a,b", lambda a, b, s: dict(a=a, b=b, site=s), [(0, "a"), (1, "b")])]
 
 
+TUNE_GRID = {"n_neighbors": [5, 10, 20, 50], "weights": ["uniform", "distance"], "metric": ["euclidean", "manhattan"]}   # run_comparison.py:63-67
+
+
+def _summary(v):
+    """min, quartiles, max and mean of a float64 device vector: what a box plot draws"""
+    q = torch.quantile(v, torch.tensor([0.25, 0.5, 0.75], dtype=v.dtype, device=v.device))
+    return {"min": float(v.min()), "q1": float(q[0]), "median": float(q[1]), "q3": float(q[2]), "max": float(v.max()), "mean": float(v.mean())}
+
+
 def _row(route, modality, model_name, result):
     row = {"Route": route, "Modality": modality, "Model": model_name}
     row.update({k: result[k] for k in COLUMNS})
@@ -98,11 +115,12 @@ def _row(route, modality, model_name, result):
 
 
 def print_table(rows):
-    head = f"{'Route':<16}{'Modality':<9}{'Model':<16}" + "".join(f"{c:>17}" for c in COLUMNS)
+    w = max([16] + [len(r["Model"]) + 1 for r in rows])          # the tuned k-NN rows carry their parameters in the name
+    head = f"{'Route':<16}{'Modality':<9}{'Model':<{w}}" + "".join(f"{c:>17}" for c in COLUMNS)
     print(head)
     print("-" * len(head))
     for r in rows:
-        print(f"{r['Route']:<16}{r['Modality']:<9}{r['Model']:<16}"
+        print(f"{r['Route']:<16}{r['Modality']:<9}{r['Model']:<{w}}"
               + "".join(f"{r[c]:>17d}" if c == "PearsonValid" else f"{r[c]:>17.6f}" for c in COLUMNS))
 
 
@@ -301,19 +319,33 @@ def run(kind, argv=None, return_clustering=False):
                     acc[(name, tgt)].update(truth[tgt], res[j])
             for tgt in targets:
                 base[tgt].update(truth[tgt], means[tgt])
-    knn_rows, knn_regs = [], []
-    if args.knn > 0:
-        from mmvae.knn import ConditionedKNeighborsRegressor, KNeighborsRegressor
+    knn_rows, knn_regs, tuned = [], [], []
+    if args.knn_tune_out and not args.knn_tune:
+        raise SystemExit("--knn-tune-out needs --knn-tune")
+    if args.knn > 0 or args.knn_tune:
+        from mmvae.knn import ConditionedKNeighborsRegressor, KNeighborsRegressor, optimize_knn
         tr = [t[train_idx].to(dev).contiguous() for t in (tpm, beta_v, site)]
         if args.input_dtype == "bf16":
             tr[:2] = [to_bf16_rows(t) for t in tr[:2]]
         mod = {"a": 0, "b": 1}
         for tgt in targets:
             src = "b" if tgt == "a" else "a"
-            regs = [(f"{src}->{tgt}", f"kNN(k={args.knn})", KNeighborsRegressor(args.knn).fit(tr[mod[src]], tr[mod[tgt]]), False)]
-            if args.knn_by_site:
+            regs = []
+            if args.knn > 0:
+                regs.append((f"{src}->{tgt}", f"kNN(k={args.knn})", KNeighborsRegressor(args.knn).fit(tr[mod[src]], tr[mod[tgt]]), False))
+            if args.knn > 0 and args.knn_by_site:
                 regs.append((f"{src}+site->{tgt}", f"kNN-site(k={args.knn})",
                              ConditionedKNeighborsRegressor(args.knn).fit(tr[mod[src]], tr[mod[tgt]], tr[2]), True))
+            for by_site in ([False, True] if args.knn_by_site else [False]) if args.knn_tune else []:
+                # the grid's k reaches 50: with fewer training rows the plain grid keeps the k that fit (the per-site form clips k itself)
+                params = dict(TUNE_GRID, n_neighbors=[k for k in TUNE_GRID["n_neighbors"] if by_site or k <= tr[0].shape[0]])
+                best, p, grid = optimize_knn(tr[mod[src]], tr[mod[tgt]], va[mod[src]], va[mod[tgt]], tr[2] if by_site else None,
+                                             va[2] if by_site else None, params=params, conditioned=by_site)
+                route = f"{src}+site->{tgt}" if by_site else f"{src}->{tgt}"
+                name = f"kNN-{'site-' if by_site else ''}tuned(k={p['n_neighbors']},w={p['weights']},m={p['metric']})"
+                regs.append((route, name, best, by_site))
+                tuned.append({"Route": route, "Modality": names[tgt], "Model": name, "conditioned": by_site, "best": p,
+                              "best_mse": min(m for _, m in grid), "grid": [dict(q, mse=m) for q, m in grid]})
             for route, model_name, reg, by_site in regs:
                 m = ImputationMetrics(dims[tgt], dev)
                 for i in range(0, n_val, B):
@@ -322,7 +354,7 @@ def run(kind, argv=None, return_clustering=False):
                 knn_rows.append(_row(route, names[tgt], model_name, m.compute()))
                 knn_regs.append((route, model_name, reg, by_site, mod[src], tgt))
     elif args.knn_by_site:
-        raise SystemExit("--knn-by-site needs --knn K")
+        raise SystemExit("--knn-by-site needs --knn K or --knn-tune")
     if args.clustering_out and not args.clustering:
         raise SystemExit("--clustering-out needs --clustering")
     if args.clustering_pca and not args.clustering:
@@ -386,6 +418,25 @@ def run(kind, argv=None, return_clustering=False):
         if args.downstream_out:
             with open(args.downstream_out, "w") as f:
                 json.dump(table, f, indent=1)
+    if args.knn_tune_out:
+        # the box-plot numbers: after every table, so that none of them depends on the flag (the model draws eps per forward)
+        tuned_regs = {(r[0], r[1]): r for r in knn_regs}
+        with torch.no_grad():
+            for t in tuned:
+                _, _, reg, by_site, src_i, tgt = tuned_regs[(t["Route"], t["Model"])]
+                route_fw = [(kwargs, outs[0][0]) for _, kwargs, outs in plan if len(outs) == 1 and outs[0][1] == tgt]
+                per = {t["Model"]: [], title: []}
+                for i in range(0, n_val, B):
+                    a, b, s = va[0][i:i + B], va[1][i:i + B], va[2][i:i + B]
+                    y = (a, b)[1 - src_i].double()
+                    x = (a, b)[src_i]
+                    per[t["Model"]].append(((reg.predict(x, s) if by_site else reg.predict(x)).double() - y).pow(2).mean(dim=1))
+                    if route_fw:
+                        kwargs, j = route_fw[0]
+                        per[title].append((model(**kwargs(a, b, s))[j].double() - y).pow(2).mean(dim=1))
+                t["per_sample_mse"] = {k: _summary(torch.cat(v)) for k, v in per.items() if v}
+        with open(args.knn_tune_out, "w") as f:
+            json.dump(tuned, f, indent=1)
     return (rows, crows) if return_clustering else rows
 
 

@@ -240,6 +240,9 @@ _SIGNATURES = {
     "mmvae_knn_work_bytes": [i32, i32, i32, C.POINTER(i64)],
     "mmvae_knn_splits": [i32, i32, C.POINTER(i32), C.POINTER(i32)],
     "mmvae_knn_mean_rows": [vp, i64, vp, i32, i64, vp, i64, i32, i32, i32, i32, vp],
+    "mmvae_knn_search_l1": [C.POINTER(KnnArgs), vp],
+    "mmvae_knn_l1_work_bytes": [i32, i32, i32, C.POINTER(i64)],
+    "mmvae_knn_weighted_rows": [vp, i64, vp, i64, i32, vp, i32, i64, vp, i64, i32, i32, i32, i32, vp],
     "mmvae_silhouette_samples": [C.POINTER(SilhouetteArgs), vp],
     "mmvae_silhouette_work_bytes": [i32, i32, i32, C.POINTER(i64)],
     "mmvae_silhouette_splits": [i32, i32, i32, C.POINTER(i32)],

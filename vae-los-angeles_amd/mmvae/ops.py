@@ -866,6 +866,54 @@ def knn_mean_rows(idx, y, out=None):
     return out
 
 
+def knn_l1_work_bytes(Mq, Nt, k):
+    return _plan("mmvae_knn_l1_work_bytes", Mq, Nt, k, outs=(C.c_int64,))
+
+
+def knn_search_l1(q, t, k, dist=True, *, idx_out=None, dist_out=None):
+    """The k nearest training rows of every query row under the manhattan distance (mmvae_knn_search_l1): idx int32 (Mq, k) ascending
+    by (distance, training index), and the L1 distances themselves -- not squared -- fp32 (Mq, k) unless dist is False (then None).
+    Every distance is one fp32 chain of |q - t| over the columns in ascending order.  Operands as knn_search; there is no shift."""
+    q_ptr, q_dt, q_ld = _rows_operand(q, "q", "knn_search_l1")
+    Mq, F = q.shape
+    t_ptr, t_dt, t_ld = _rows_operand(t, "t", "knn_search_l1", F)
+    Nt = t.shape[0]
+    k = int(k)
+    if not 1 <= k <= min(Nt, L.KNN_MAXK):
+        raise ValueError(f"knn_search_l1: k = {k} outside [1, min({Nt} training rows, {L.KNN_MAXK})]")
+    if t.device != q.device:
+        raise ValueError("knn_search_l1: all operands must live on one device")
+    idx = _out_view(idx_out, "idx_out", "knn_search_l1", torch.int32, Mq, k, q.device)
+    d = _out_view(dist_out, "dist_out", "knn_search_l1", torch.float32, Mq, k, q.device) if dist else None
+    work = _workspace(knn_l1_work_bytes(Mq, Nt, k), q.device)
+    a = L.KnnArgs(q_ptr, t_ptr, None, idx.data_ptr(), _p(d), _p(work), q_ld, t_ld, _ld(idx), _ld(d) if d is not None else 0,
+                  work.numel() * 8 if work is not None else 0, Mq, Nt, F, k, q_dt, t_dt)
+    with probe_span("knn_search_l1", lambda: dict(kind="valu", flops=2.0 * Mq * Nt * F, M=Mq, N=Nt, K=F)):
+        L.check(L.load().mmvae_knn_search_l1(C.byref(a), _stream()), "mmvae_knn_search_l1")
+    return idx, d
+
+
+def knn_weighted_rows(idx, dist, y, squared, out=None):
+    """out[i] = sum_n w_n y[idx[i][n]] / sum_n w_n in fp32 with sklearn's weights='distance' (mmvae_knn_weighted_rows): w = 1 / d, or
+    the indicator of d == 0 where a row has zero distances; d = dist, or sqrt(dist) when `squared` (the dist2 of knn_search).
+    idx int32 (Mq, k) and dist fp32 (Mq, k) may be the first k columns of a wider search; y (Ny, Fy) fp32 or bf16, out fp32 (Mq, Fy)."""
+    y_ptr, y_dt, y_ld = _rows_operand(y, "y", "knn_weighted_rows")
+    if not isinstance(idx, torch.Tensor) or not idx.is_cuda or idx.dtype != torch.int32 or idx.dim() != 2 or idx.stride(1) != 1 or idx.shape[0] < 1 \
+            or not 1 <= idx.shape[1] <= L.KNN_MAXK:
+        raise ValueError(f"knn_weighted_rows: idx must be an int32 (Mq, 1 <= k <= {L.KNN_MAXK}) device tensor with unit inner stride")
+    Mq, k = idx.shape
+    if not isinstance(dist, torch.Tensor) or not dist.is_cuda or dist.dtype != torch.float32 or tuple(dist.shape) != (Mq, k) or dist.stride(1) != 1:
+        raise ValueError(f"knn_weighted_rows: dist must be a float32 ({Mq}, {k}) device tensor with unit inner stride")
+    Ny, Fy = y.shape
+    if idx.device != y.device or dist.device != y.device:
+        raise ValueError("knn_weighted_rows: all operands must live on one device")
+    out = _out_view(out, "out", "knn_weighted_rows", torch.float32, Mq, Fy, y.device)
+    with stream_span("knn_weighted_rows", Mq * k * (8 + Fy * y.element_size()) + 4 * Mq * Fy):
+        L.check(L.load().mmvae_knn_weighted_rows(idx.data_ptr(), _ld(idx), dist.data_ptr(), _ld(dist), 1 if squared else 0, y_ptr, y_dt, y_ld,
+                                                 out.data_ptr(), _ld(out), Mq, k, Ny, Fy, _stream()), "mmvae_knn_weighted_rows")
+    return out
+
+
 # --------------------------------------------------------------------------------------------
 # silhouette coefficient (include/mmvae_hip.h: mmvae_silhouette_samples)
 # --------------------------------------------------------------------------------------------
