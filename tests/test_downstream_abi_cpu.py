@@ -1,33 +1,20 @@
 """Layout of the site classifier's argument structs as gcc lays include/mmvae_hip.h out == the ctypes mirror (the pattern of
 tests/test_tsne_abi_cpu.py), the entries in the binding, and what they and the Python layer refuse or answer without a device."""
 import ctypes as C
-import os
-import subprocess
 
 import pytest
 import torch
 
+from abi_util import header_facts
 from mmvae import _lib, downstream, ops
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STRUCTS = {"mmvae_ln_act_fwd_args": _lib.LnActFwdArgs, "mmvae_ln_act_bwd_args": _lib.LnActBwdArgs, "mmvae_wce_args": _lib.WceArgs,
            "mmvae_adamw_item": _lib.AdamWItem}
 ENTRIES = ("mmvae_ln_act_fwd", "mmvae_ln_act_bwd", "mmvae_ln_act_bwd_work_bytes", "mmvae_wce_mean", "mmvae_adam_step", "mmvae_adamw_step")
 
 
 def test_structs_match_c_layout(tmp_path):
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "mmvae_hip.h"', "int main(void) {",
-             'printf("MAXN %d\\n", MMVAE_LN_MAXN);', 'printf("MAXC %d\\n", MMVAE_WCE_MAXC);']
-    for cname, cls in STRUCTS.items():
-        lines.append(f'printf("{cname} %zu\\n", sizeof({cname}));')
-        for fname, _ in cls._fields_:
-            lines.append(f'printf("{cname}.{fname} %zu\\n", offsetof({cname}, {fname}));')
-    lines.append("return 0; }")
-    src = tmp_path / "abi.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "abi"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = dict(l.split() for l in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
+    got = header_facts(tmp_path, structs=STRUCTS, values={"MAXN": "MMVAE_LN_MAXN", "MAXC": "MMVAE_WCE_MAXC"})
     for cname, cls in STRUCTS.items():
         assert int(got[cname]) == C.sizeof(cls), cname
         for fname, _ in cls._fields_:

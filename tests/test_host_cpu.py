@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import np_oracle as O
+from abi_util import header_facts
 from mmvae import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -59,22 +60,11 @@ def test_check_separates_argument_refusals_from_hip_errors():
 def test_ctypes_structs_match_c_layout(tmp_path):
     """sizeof/offsetof of every args struct as gcc lays the header out == the ctypes mirror."""
     import ctypes as C
-    import subprocess
     pairs = {"mmvae_prep_item": _lib.PrepItem, "mmvae_gemm_nt_args": _lib.GemmNtArgs, "mmvae_gemm_tn_args": _lib.GemmTnArgs,
              "mmvae_bn_finalize_args": _lib.BnFinalizeArgs, "mmvae_bn_bwd_finalize_args": _lib.BnBwdFinalizeArgs,
              "mmvae_fuse_fwd_args": _lib.FuseFwdArgs, "mmvae_fuse_bwd_args": _lib.FuseBwdArgs, "mmvae_loss_args": _lib.LossArgs,
              "mmvae_adamw_item": _lib.AdamWItem, "mmvae_gather_item": _lib.GatherItem}
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "mmvae_hip.h"', "int main(void) {"]
-    for cname, cls in pairs.items():
-        lines.append(f'printf("{cname} %zu\\n", sizeof({cname}));')
-        for fname, _ in cls._fields_:
-            lines.append(f'printf("{cname}.{fname} %zu\\n", offsetof({cname}, {fname}));')
-    lines.append("return 0; }")
-    src = tmp_path / "abi.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "abi"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = dict(l.split() for l in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
+    got = header_facts(tmp_path, structs=pairs)
     for cname, cls in pairs.items():
         assert int(got[cname]) == C.sizeof(cls), cname
         for fname, _ in cls._fields_:
@@ -83,20 +73,12 @@ def test_ctypes_structs_match_c_layout(tmp_path):
 
 def test_binding_constants_match_the_header(tmp_path):
     """Enumerators and macros of include/mmvae_hip.h as gcc sees them == the constants of the ctypes binding."""
-    import subprocess
     names = {"MMVAE_EPI_STORE": _lib.EPI_STORE, "MMVAE_EPI_RELU_MASK": _lib.EPI_RELU_MASK, "MMVAE_EPI_BN_BWD": _lib.EPI_BN_BWD,
              "MMVAE_EPI_LOSS_MSE": _lib.EPI_LOSS_MSE, "MMVAE_EPI_LOSS_BCE_LOGIT": _lib.EPI_LOSS_BCE_LOGIT,
              "MMVAE_CTR_COPIES": _lib.CTR_COPIES, "MMVAE_TN_GROUP_MAX": _lib.TN_GROUP_MAX, "MMVAE_TABLE_COPIES": _lib.TABLE_COPIES,
              "MMVAE_PRO_NONE": _lib.PRO_NONE, "MMVAE_PRO_BN_RELU_DROP": _lib.PRO_BN_RELU_DROP, "MMVAE_PRO_BN_BWD_APPLY": _lib.PRO_BN_BWD_APPLY,
              "MMVAE_F32": _lib.F32, "MMVAE_BF16": _lib.BF16, "MMVAE_PREC_F32": _lib.PREC_F32, "MMVAE_PREC_BF16": _lib.PREC_BF16}
-    lines = ['#include <stdio.h>', '#include "mmvae_hip.h"', "int main(void) {"]
-    lines += [f'printf("{n} %ld\\n", (long)({n}));' for n in names]
-    lines.append("return 0; }")
-    src = tmp_path / "consts.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "consts"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = dict(l.split() for l in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
+    got = header_facts(tmp_path, values={n: n for n in names})
     for n, v in names.items():
         assert int(got[n]) == v, n
 

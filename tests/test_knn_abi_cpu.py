@@ -1,26 +1,14 @@
 """Layout of mmvae_knn_args as gcc lays include/mmvae_hip.h out == the ctypes mirror (the pattern of tests/test_class_tail_abi_cpu.py),
 the k-NN entries in the binding, and what they refuse or answer without a device."""
 import ctypes as C
-import os
-import subprocess
 
+from abi_util import header_facts
 from mmvae import _lib, ops
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_knn_struct_matches_c_layout(tmp_path):
     cname, cls = "mmvae_knn_args", _lib.KnnArgs
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "mmvae_hip.h"', "int main(void) {",
-             f'printf("{cname} %zu\\n", sizeof({cname}));', 'printf("MAXK %d\\n", MMVAE_KNN_MAXK);']
-    for fname, _ in cls._fields_:
-        lines.append(f'printf("{cname}.{fname} %zu\\n", offsetof({cname}, {fname}));')
-    lines.append("return 0; }")
-    src = tmp_path / "abi.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "abi"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = dict(l.split() for l in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
+    got = header_facts(tmp_path, structs={cname: cls}, values={"MAXK": "MMVAE_KNN_MAXK"})
     assert int(got[cname]) == C.sizeof(cls)
     for fname, _ in cls._fields_:
         assert int(got[f"{cname}.{fname}"]) == getattr(cls, fname).offset, fname

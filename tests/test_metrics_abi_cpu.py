@@ -2,28 +2,16 @@
 test_latent_abi_cpu.py), the symbol is exported under the unchanged ABI version, and every refusal the header lists returns
 MMVAE_ERR_ARG before anything is launched (so these run without a GPU: no pointer is ever dereferenced)."""
 import ctypes as C
-import os
-import subprocess
 
 import pytest
 
+from abi_util import header_facts
 from mmvae import _lib
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_metrics_struct_matches_c_layout(tmp_path):
     cname, cls = "mmvae_metrics_args", _lib.MetricsArgs
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "mmvae_hip.h"', "int main(void) {",
-             f'printf("{cname} %zu\\n", sizeof({cname}));']
-    for fname, _ in cls._fields_:
-        lines.append(f'printf("{cname}.{fname} %zu\\n", offsetof({cname}, {fname}));')
-    lines.append("return 0; }")
-    src = tmp_path / "abi.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "abi"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = dict(l.split() for l in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
+    got = header_facts(tmp_path, structs={cname: cls})
     assert int(got[cname]) == C.sizeof(cls)
     for fname, _ in cls._fields_:
         assert int(got[f"{cname}.{fname}"]) == getattr(cls, fname).offset, fname

@@ -2,31 +2,19 @@
 tests/test_silhouette_abi_cpu.py), the PCA entries in the binding, and what they, the Python wrappers and mmvae.pca.PCA refuse or
 answer without a device."""
 import ctypes as C
-import os
-import subprocess
 
 import pytest
 import torch
 
 import pca_ref as PR
+from abi_util import header_facts
 from mmvae import _lib, clustering, ops, pca
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STRUCTS = (("mmvae_pca_scatter_args", _lib.PcaScatterArgs), ("mmvae_pca_project_args", _lib.PcaProjectArgs))
 
 
 def test_pca_structs_match_c_layout(tmp_path):
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "mmvae_hip.h"', "int main(void) {", 'printf("MAXK %d\\n", MMVAE_PCA_MAXK);']
-    for cname, cls in STRUCTS:
-        lines.append(f'printf("{cname} %zu\\n", sizeof({cname}));')
-        for fname, _ in cls._fields_:
-            lines.append(f'printf("{cname}.{fname} %zu\\n", offsetof({cname}, {fname}));')
-    lines.append("return 0; }")
-    src = tmp_path / "abi.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "abi"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = dict(l.split() for l in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
+    got = header_facts(tmp_path, structs=dict(STRUCTS), values={"MAXK": "MMVAE_PCA_MAXK"})
     for cname, cls in STRUCTS:
         assert int(got[cname]) == C.sizeof(cls)
         for fname, _ in cls._fields_:

@@ -1,30 +1,18 @@
 """Layout of mmvae_silhouette_args as gcc lays include/mmvae_hip.h out == the ctypes mirror (the pattern of tests/test_knn_abi_cpu.py),
 the silhouette entries in the binding, and what they and the Python wrappers refuse or answer without a device."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+from abi_util import header_facts
 from mmvae import _lib, clustering, ops
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_silhouette_struct_matches_c_layout(tmp_path):
     cname, cls = "mmvae_silhouette_args", _lib.SilhouetteArgs
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "mmvae_hip.h"', "int main(void) {",
-             f'printf("{cname} %zu\\n", sizeof({cname}));', 'printf("MAXC %d\\n", MMVAE_SIL_MAXC);']
-    for fname, _ in cls._fields_:
-        lines.append(f'printf("{cname}.{fname} %zu\\n", offsetof({cname}, {fname}));')
-    lines.append("return 0; }")
-    src = tmp_path / "abi.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "abi"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = dict(l.split() for l in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
+    got = header_facts(tmp_path, structs={cname: cls}, values={"MAXC": "MMVAE_SIL_MAXC"})
     assert int(got[cname]) == C.sizeof(cls)
     for fname, _ in cls._fields_:
         assert int(got[f"{cname}.{fname}"]) == getattr(cls, fname).offset, fname

@@ -1,15 +1,13 @@
 """Layout of the three t-SNE argument structs as gcc lays include/mmvae_hip.h out == the ctypes mirror (the pattern of
 tests/test_knn_abi_cpu.py), the entries in the binding, and what they and the Python wrappers refuse or answer without a device."""
 import ctypes as C
-import os
-import subprocess
 
 import pytest
 import torch
 
+from abi_util import header_facts
 from mmvae import _lib, clustering, ops, tsne
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STRUCTS = {"mmvae_tsne_affinities_args": _lib.TsneAffinitiesArgs, "mmvae_tsne_gradient_args": _lib.TsneGradientArgs,
            "mmvae_tsne_update_args": _lib.TsneUpdateArgs}
 ENTRIES = ("mmvae_tsne_affinities", "mmvae_tsne_gradient", "mmvae_tsne_gradient_splits", "mmvae_tsne_gradient_work_bytes", "mmvae_tsne_update",
@@ -17,17 +15,7 @@ ENTRIES = ("mmvae_tsne_affinities", "mmvae_tsne_gradient", "mmvae_tsne_gradient_
 
 
 def test_tsne_structs_match_c_layout(tmp_path):
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "mmvae_hip.h"', "int main(void) {", 'printf("MAXK %d\\n", MMVAE_KNN_MAXK);']
-    for cname, cls in STRUCTS.items():
-        lines.append(f'printf("{cname} %zu\\n", sizeof({cname}));')
-        for fname, _ in cls._fields_:
-            lines.append(f'printf("{cname}.{fname} %zu\\n", offsetof({cname}, {fname}));')
-    lines.append("return 0; }")
-    src = tmp_path / "abi.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "abi"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = dict(l.split() for l in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
+    got = header_facts(tmp_path, structs=STRUCTS, values={"MAXK": "MMVAE_KNN_MAXK"})
     for cname, cls in STRUCTS.items():
         assert int(got[cname]) == C.sizeof(cls), cname
         for fname, _ in cls._fields_:

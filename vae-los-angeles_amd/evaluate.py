@@ -40,6 +40,8 @@ import argparse
 import json
 import os
 import sys
+from collections import namedtuple
+from functools import partial
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 if HERE not in sys.path:
@@ -47,6 +49,9 @@ if HERE not in sys.path:
 
 import torch  # noqa: E402
 
+from mmvae import to_bf16_rows  # noqa: E402
+from mmvae._lib import PCA_MAXK, SIL_MAXC, WCE_MAXC  # noqa: E402
+from mmvae.knn import GRID as TUNE_GRID  # noqa: E402  (the reference's 16-point grid, run_comparison.py:63-67)
 from mmvae.metrics import ImputationMetrics  # noqa: E402
 from src.config import Config  # noqa: E402
 from trainer import KINDS, load_pickled_dataset, make_model, split_indices, synthetic_dataset  # noqa: E402
@@ -99,7 +104,19 @@ def routes(kind):
             ("a+b+site->a,b", lambda a, b, s: dict(a=a, b=b, site=s), [(0, "a"), (1, "b")])]
 
 
-TUNE_GRID = {"n_neighbors": [5, 10, 20, 50], "weights": ["uniform", "distance"], "metric": ["euclidean", "manhattan"]}   # run_comparison.py:63-67
+MOD, NAMES = {"a": 0, "b": 1}, {"a": "RNA", "b": "DNA"}         # a modality's place in a batch (a, b, s), and its name in the tables
+KnnBaseline = namedtuple("KnnBaseline", "route name regressor by_site source target")      # source, target: 'a' | 'b'
+
+
+def batches(va, B):
+    """(i, a, b, s): rows i .. i + B of the split (a, b, s), in order"""
+    for i in range(0, va[0].shape[0], B):
+        yield i, va[0][i:i + B], va[1][i:i + B], va[2][i:i + B]
+
+
+def knn_predict(kb, a, b, s):
+    x = (a, b)[MOD[kb.source]]
+    return kb.regressor.predict(x, s) if kb.by_site else kb.regressor.predict(x)
 
 
 def _summary(v):
@@ -109,9 +126,7 @@ def _summary(v):
 
 
 def _row(route, modality, model_name, result):
-    row = {"Route": route, "Modality": modality, "Model": model_name}
-    row.update({k: result[k] for k in COLUMNS})
-    return row
+    return {"Route": route, "Modality": modality, "Model": model_name, **{k: result[k] for k in COLUMNS}}
 
 
 def print_table(rows):
@@ -150,12 +165,11 @@ def tsne_embedding(z, perplexity, iters, seed):
 
 
 def clustering_table(entries, va, dims, B, pca_k=0, tsne=None):
-    """[(features, model name, fill)] -> table rows.  fill(i, tgt) gives the imputed rows i .. i + B of its target modality, or is None
+    """[(features, model name, target, fill)] -> table rows.  fill(a, b, s) gives the imputed target modality of that batch, or is None
     for the true features.  ONE (rows, A + D) fp32 matrix is filled batch by batch, standardised, judged and reused.  pca_k > 0: the
     same two numbers on the standardised matrix's projection onto its first pca_k principal components as well.  tsne = (perplexity,
     iterations, seed): and on its t-SNE embedding."""
     from mmvae import clustering
-    from mmvae._lib import SIL_MAXC
     n_val, labels = va[0].shape[0], va[2]
     n_labels = int(torch.unique(labels).numel())
     if not 2 <= n_labels <= min(n_val - 1, SIL_MAXC):
@@ -165,25 +179,21 @@ def clustering_table(entries, va, dims, B, pca_k=0, tsne=None):
     feats = torch.empty(n_val, dims["a"] + dims["b"], dtype=torch.float32, device=labels.device)
     part = {"a": feats[:, :dims["a"]], "b": feats[:, dims["a"]:]}
     rows = []
+
+    def judged(y):
+        return clustering.silhouette_score(y, labels), clustering.neighborhood_hit(y, labels, k=NH_K)
+
     for features, model_name, tgt, fill in entries:
-        for i in range(0, n_val, B):
-            for m, j in (("a", 0), ("b", 1)):
-                part[m][i:i + B].copy_(fill(i) if m == tgt else va[j][i:i + B])
+        for i, a, b, s in batches(va, B):
+            for m, true in (("a", a), ("b", b)):
+                part[m][i:i + B].copy_(fill(a, b, s) if m == tgt else true)
         z = clustering.standardize(feats)
-        rows.append({"Features": features, "Model": model_name, "Silhouette": clustering.silhouette_score(z, labels),
-                     "NeighborhoodHit": clustering.neighborhood_hit(z, labels, k=NH_K)})
+        rows.append({"Features": features, "Model": model_name, **dict(zip(CLUSTERING_COLUMNS, judged(z)))})
         if pca_k > 0:
             pca = clustering.PCA(pca_k)
-            y = pca.fit_transform(z)
-            rows[-1].update({"PCASilhouette": clustering.silhouette_score(y, labels),
-                             "PCANeighborhoodHit": clustering.neighborhood_hit(y, labels, k=NH_K),
-                             "PCAExplained": float(pca.explained_variance_ratio_.sum())})
-            del y
+            rows[-1].update(zip(PCA_COLUMNS, judged(pca.fit_transform(z)) + (float(pca.explained_variance_ratio_.sum()),)))
         if tsne is not None:
-            y = tsne_embedding(z, *tsne)
-            rows[-1].update({"TSNESilhouette": clustering.silhouette_score(y, labels),
-                             "TSNENeighborhoodHit": clustering.neighborhood_hit(y, labels, k=NH_K)})
-            del y
+            rows[-1].update(zip(TSNE_COLUMNS, judged(tsne_embedding(z, *tsne))))
         del z
     return rows
 
@@ -198,8 +208,7 @@ def downstream_scenarios(kind, orig, est):
         return {"Orig. RNA": [orig["a"]], "Orig. DNA": [orig["b"]], "Orig. RNA + Est. DNA": [orig["a"], est["b"]],
                 "Orig. DNA + Est. RNA": [orig["b"], est["a"]], "Orig. RNA + Orig. DNA": [orig["a"], orig["b"]], "Est. DNA": [est["b"]],
                 "Est. RNA": [est["a"]], "Est. RNA + Est. DNA": [est["a"], est["b"]]}
-    src, tgt = ("a", "b") if kind == "rna2dna" else ("b", "a")
-    n = {"a": "RNA", "b": "DNA"}
+    (src, tgt), n = ("a", "b") if kind == "rna2dna" else ("b", "a"), NAMES
     return {f"Orig. {n[src]}": [orig[src]], f"Orig. {n[tgt]}": [orig[tgt]], f"Orig. {n[src]} + Est. {n[tgt]}": [orig[src], est[tgt]],
             f"Est. {n[tgt]}": [est[tgt]], f"Orig. {n[src]} + Orig. {n[tgt]}": [orig[src], orig[tgt]]}
 
@@ -208,7 +217,6 @@ def downstream_table(kind, model, va, B, folds, epochs, seed):
     """{scenario: the aggregated report of run_classification_scenario}, or {} with a message when the validation split cannot carry the
     task.  Classes with fewer than 2 validation rows are dropped and the labels re-encoded contiguously (downstream_task.py:417-424)."""
     from mmvae import downstream
-    from mmvae._lib import WCE_MAXC
     site = va[2]
     ids, inverse, counts = torch.unique(site, return_inverse=True, return_counts=True)
     keep_class = counts >= 2
@@ -222,28 +230,22 @@ def downstream_table(kind, model, va, B, folds, epochs, seed):
     recode[kept] = torch.arange(kept.numel(), device=site.device)
     labels = recode[site[rows]]
     names = [str(int(i)) for i in kept]
-    from mmvae import to_bf16_rows
     # the kept rows in the inputs' storage (bf16 inputs keep their padded rows: the model reads them as it does above)
     fa, fb = (to_bf16_rows(t[rows]) if t.dtype == torch.bfloat16 else t[rows].contiguous() for t in va[:2])
     fs = site[rows].contiguous()
     orig = {"a": fa.float().contiguous(), "b": fb.float().contiguous()}
     est = {}
     with torch.no_grad():
-        want = {"multimodal": (("b", lambda a, b, s: model(a=a)[1]), ("a", lambda a, b, s: model(b=b)[0])),
-                "rna2dna": (("b", lambda a, b, s: model(rna=a, site=s)[0]),),
-                "dna2rna": (("a", lambda a, b, s: model(dna=b, site=s)[0]),)}[kind]
-        for tgt, fwd in want:
-            out = torch.empty_like(orig[tgt])
-            for i in range(0, rows.numel(), B):
-                out[i:i + B].copy_(fwd(fa[i:i + B], fb[i:i + B], fs[i:i + B]))
-            est[tgt] = out
+        for _, kwargs, outs in routes(kind):
+            if len(outs) != 1:                                   # the single-target routes, in routes()' order: a -> b before b -> a
+                continue
+            j, tgt = outs[0]
+            est[tgt] = torch.empty_like(orig[tgt])
+            for i, a, b, s in batches((fa, fb, fs), B):
+                est[tgt][i:i + B].copy_(model(**kwargs(a, b, s))[j])
     arch = dict(hidden=(256, 128), layer_norm=True, dropout=(0.3, 0.2)) if kind == "multimodal" else dict(hidden=(128,), layer_norm=False, dropout=(0.2,))
-    table = {}
-    for name, blocks in downstream_scenarios(kind, orig, est).items():
-        feats = blocks[0] if len(blocks) == 1 else torch.cat(blocks, dim=1)
-        table[name] = downstream.cross_validate(feats, labels, names, folds, epochs=epochs, seed=seed, **arch)
-        del feats
-    return table
+    return {name: downstream.cross_validate(blocks[0] if len(blocks) == 1 else torch.cat(blocks, dim=1), labels, names, folds, epochs=epochs,
+                                            seed=seed, **arch) for name, blocks in downstream_scenarios(kind, orig, est).items()}
 
 
 def print_downstream_table(table):
@@ -255,12 +257,31 @@ def print_downstream_table(table):
         print(f"{name:<26}" + "".join(f"{f'{m:.4f} +- {sd:.4f}':>20}" for m, sd in cells))
 
 
-def run(kind, argv=None, return_clustering=False):
-    args = build_parser(kind).parse_args(argv)
-    tag, title = KINDS[kind]["tag"], KINDS[kind]["title"]
-    if not torch.cuda.is_available():
-        raise SystemExit("evaluate.py needs an MI355X: the product path has no CPU fallback")
-    dev = torch.device("cuda", torch.cuda.current_device())
+PCA_RANGE = f"--clustering-pca {{}} outside [0, min({PCA_MAXK}, validation rows, features)]"
+
+
+def check_args(args):
+    """Every flag combination and range the script refuses; needs neither data nor device (load_split holds --clustering-pca to the split's shape)."""
+    if args.knn_tune_out and not args.knn_tune:
+        raise SystemExit("--knn-tune-out needs --knn-tune")
+    if args.knn_by_site and not (args.knn > 0 or args.knn_tune):
+        raise SystemExit("--knn-by-site needs --knn K or --knn-tune")
+    for flag in ("clustering_out", "clustering_pca", "clustering_tsne"):
+        if getattr(args, flag) and not args.clustering:
+            raise SystemExit(f"--{flag.replace('_', '-')} needs --clustering")
+    if args.clustering_tsne and (not args.tsne_perplexity > 0 or args.tsne_iters < 250):
+        raise SystemExit("--tsne-perplexity must be positive and --tsne-iters at least 250")
+    if not 0 <= args.clustering_pca <= PCA_MAXK:
+        raise SystemExit(PCA_RANGE.format(args.clustering_pca))
+    if args.downstream_out and not args.downstream:
+        raise SystemExit("--downstream-out needs --downstream")
+    if args.downstream and (args.downstream_folds < 2 or args.downstream_epochs < 1):
+        raise SystemExit("--downstream-folds must be at least 2 and --downstream-epochs at least 1")
+
+
+def load_split(args, dev):
+    """((tpm, beta, site) on the host, training indices, the validation split on the device as the model reads it, the training column
+    means) of --data or of the synthetic set.  --data sets the dims and the site count of `args`."""
     if args.data:
         tpm, beta_v, site = load_pickled_dataset(args.data)
         args.input_dim_a, args.input_dim_b = tpm.shape[1], beta_v.shape[1]
@@ -273,13 +294,19 @@ def run(kind, argv=None, return_clustering=False):
     val_idx, train_idx = split_indices(tpm.shape[0])
     if val_idx.numel() == 0:
         raise SystemExit(f"{tpm.shape[0]} samples leave no validation rows")
+    if args.clustering_pca > min(val_idx.numel(), args.input_dim_a + args.input_dim_b):
+        raise SystemExit(PCA_RANGE.format(args.clustering_pca))
     va = [t[val_idx].to(dev).contiguous() for t in (tpm, beta_v, site)]
     # mean imputation: the column means of the TRAINING rows, one row for every validation sample
     means = {"a": tpm[train_idx].double().mean(dim=0).float().to(dev), "b": beta_v[train_idx].double().mean(dim=0).float().to(dev)}
     if args.input_dtype == "bf16":
-        from mmvae import to_bf16_rows
         va[:2] = [to_bf16_rows(t) for t in va[:2]]
+    return (tpm, beta_v, site), train_idx, va, means
 
+
+def load_model(kind, args, dev):
+    """(the model of --checkpoint, or of the run the trainer named last, in eval mode at --precision; the checkpoint's path)"""
+    tag, title = KINDS[kind]["tag"], KINDS[kind]["title"]
     path = args.checkpoint
     if path is None:
         id_file = f"latest_{tag}_run_id.txt"
@@ -299,105 +326,121 @@ def run(kind, argv=None, return_clustering=False):
         raise SystemExit(f"{path} is not a {title} of RNA {args.input_dim_a} / DNA {args.input_dim_b} / {args.n_sites} sites / latent "
                          f"{args.latent_dim}: " + "; ".join(bad[:4] + [f"missing {k}" for k in missing[:4]]))
     model.load_state_dict(state)
-    model.to(dev).set_precision(args.precision).eval()
-    torch.manual_seed(args.seed)
+    return model.to(dev).set_precision(args.precision).eval(), path
 
-    dims = {"a": args.input_dim_a, "b": args.input_dim_b}
-    names = {"a": "RNA", "b": "DNA"}
-    plan = routes(kind)
-    acc = {(name, tgt): ImputationMetrics(dims[tgt], dev) for name, _, outs in plan for _, tgt in outs}
-    targets = sorted({tgt for _, _, outs in plan for _, tgt in outs})
-    base = {tgt: ImputationMetrics(dims[tgt], dev) for tgt in targets}
-    B, n_val = args.batch_size, va[0].shape[0]
-    with torch.no_grad():
-        for i in range(0, n_val, B):
-            a, b, s = va[0][i:i + B], va[1][i:i + B], va[2][i:i + B]
-            truth = {"a": a, "b": b}
-            for name, kwargs, outs in plan:
-                res = model(**kwargs(a, b, s))
-                for j, tgt in outs:
-                    acc[(name, tgt)].update(truth[tgt], res[j])
-            for tgt in targets:
-                base[tgt].update(truth[tgt], means[tgt])
-    knn_rows, knn_regs, tuned = [], [], []
-    if args.knn_tune_out and not args.knn_tune:
-        raise SystemExit("--knn-tune-out needs --knn-tune")
-    if args.knn > 0 or args.knn_tune:
-        from mmvae.knn import ConditionedKNeighborsRegressor, KNeighborsRegressor, optimize_knn
-        tr = [t[train_idx].to(dev).contiguous() for t in (tpm, beta_v, site)]
-        if args.input_dtype == "bf16":
-            tr[:2] = [to_bf16_rows(t) for t in tr[:2]]
-        mod = {"a": 0, "b": 1}
+
+@torch.no_grad()
+def imputation_rows(model, title, plan, targets, va, means, dims, B):
+    """The model's row per (route, target) and the mean imputation's per target: one pass, every route's forward on every batch."""
+    acc = {(name, tgt): ImputationMetrics(dims[tgt], va[2].device) for name, _, outs in plan for _, tgt in outs}
+    base = {tgt: ImputationMetrics(dims[tgt], va[2].device) for tgt in targets}
+    for _, a, b, s in batches(va, B):
+        truth = {"a": a, "b": b}
+        for name, kwargs, outs in plan:
+            res = model(**kwargs(a, b, s))
+            for j, tgt in outs:
+                acc[(name, tgt)].update(truth[tgt], res[j])
         for tgt in targets:
-            src = "b" if tgt == "a" else "a"
-            regs = []
-            if args.knn > 0:
-                regs.append((f"{src}->{tgt}", f"kNN(k={args.knn})", KNeighborsRegressor(args.knn).fit(tr[mod[src]], tr[mod[tgt]]), False))
-            if args.knn > 0 and args.knn_by_site:
-                regs.append((f"{src}+site->{tgt}", f"kNN-site(k={args.knn})",
-                             ConditionedKNeighborsRegressor(args.knn).fit(tr[mod[src]], tr[mod[tgt]], tr[2]), True))
-            for by_site in ([False, True] if args.knn_by_site else [False]) if args.knn_tune else []:
-                # the grid's k reaches 50: with fewer training rows the plain grid keeps the k that fit (the per-site form clips k itself)
-                params = dict(TUNE_GRID, n_neighbors=[k for k in TUNE_GRID["n_neighbors"] if by_site or k <= tr[0].shape[0]])
-                best, p, grid = optimize_knn(tr[mod[src]], tr[mod[tgt]], va[mod[src]], va[mod[tgt]], tr[2] if by_site else None,
-                                             va[2] if by_site else None, params=params, conditioned=by_site)
-                route = f"{src}+site->{tgt}" if by_site else f"{src}->{tgt}"
-                name = f"kNN-{'site-' if by_site else ''}tuned(k={p['n_neighbors']},w={p['weights']},m={p['metric']})"
-                regs.append((route, name, best, by_site))
-                tuned.append({"Route": route, "Modality": names[tgt], "Model": name, "conditioned": by_site, "best": p,
-                              "best_mse": min(m for _, m in grid), "grid": [dict(q, mse=m) for q, m in grid]})
-            for route, model_name, reg, by_site in regs:
-                m = ImputationMetrics(dims[tgt], dev)
-                for i in range(0, n_val, B):
-                    xq = va[mod[src]][i:i + B]
-                    m.update(va[mod[tgt]][i:i + B], reg.predict(xq, va[2][i:i + B]) if by_site else reg.predict(xq))
-                knn_rows.append(_row(route, names[tgt], model_name, m.compute()))
-                knn_regs.append((route, model_name, reg, by_site, mod[src], tgt))
-    elif args.knn_by_site:
-        raise SystemExit("--knn-by-site needs --knn K or --knn-tune")
-    if args.clustering_out and not args.clustering:
-        raise SystemExit("--clustering-out needs --clustering")
-    if args.clustering_pca and not args.clustering:
-        raise SystemExit("--clustering-pca needs --clustering")
-    if args.clustering_tsne and not args.clustering:
-        raise SystemExit("--clustering-tsne needs --clustering")
-    if args.clustering_tsne and (not args.tsne_perplexity > 0 or args.tsne_iters < 250):
-        raise SystemExit("--tsne-perplexity must be positive and --tsne-iters at least 250")
-    from mmvae._lib import PCA_MAXK
-    if not 0 <= args.clustering_pca <= min(PCA_MAXK, va[0].shape[0], args.input_dim_a + args.input_dim_b):
-        raise SystemExit(f"--clustering-pca {args.clustering_pca} outside [0, min({PCA_MAXK}, validation rows, features)]")
-    rows = []
-    for name, _, outs in plan:
-        for _, tgt in outs:
-            rows.append(_row(name, names[tgt], title, acc[(name, tgt)].compute()))
+            base[tgt].update(truth[tgt], means[tgt])
+    return [_row(name, NAMES[tgt], title, acc[(name, tgt)].compute()) for name, _, outs in plan for _, tgt in outs] \
+        + [_row("train mean", NAMES[tgt], "MeanImputation", base[tgt].compute()) for tgt in targets]
+
+
+def knn_baselines(args, targets, host, train_idx, va, dims, B):
+    """(table rows, [KnnBaseline], what --knn-tune-out holds per tuned regressor): per target modality the plain, per-site and tuned k-NN
+    regressors the flags ask for, fitted on the training rows, and their rows on the validation split.  No model forward."""
+    if not (args.knn > 0 or args.knn_tune):
+        return [], [], []
+    from mmvae.knn import ConditionedKNeighborsRegressor, KNeighborsRegressor, optimize_knn
+    tr = [t[train_idx].to(va[2].device).contiguous() for t in host]
+    if args.input_dtype == "bf16":
+        tr[:2] = [to_bf16_rows(t) for t in tr[:2]]
+    rows, baselines, tuned = [], [], []
     for tgt in targets:
-        rows.append(_row("train mean", names[tgt], "MeanImputation", base[tgt].compute()))
+        src = "b" if tgt == "a" else "a"
+        x_tr, y_tr, x_va, y_va = tr[MOD[src]], tr[MOD[tgt]], va[MOD[src]], va[MOD[tgt]]
+        route = {False: f"{src}->{tgt}", True: f"{src}+site->{tgt}"}
+        found = []
+        if args.knn > 0:
+            found.append((f"kNN(k={args.knn})", KNeighborsRegressor(args.knn).fit(x_tr, y_tr), False))
+        if args.knn > 0 and args.knn_by_site:
+            found.append((f"kNN-site(k={args.knn})", ConditionedKNeighborsRegressor(args.knn).fit(x_tr, y_tr, tr[2]), True))
+        for by_site in ([False, True] if args.knn_by_site else [False]) if args.knn_tune else []:
+            # the grid's k reaches 50: with fewer training rows the plain grid keeps the k that fit (the per-site form clips k itself)
+            params = dict(TUNE_GRID, n_neighbors=[k for k in TUNE_GRID["n_neighbors"] if by_site or k <= tr[0].shape[0]])
+            best, p, grid = optimize_knn(x_tr, y_tr, x_va, y_va, tr[2] if by_site else None, va[2] if by_site else None, params=params,
+                                         conditioned=by_site)
+            found.append((f"kNN-{'site-' if by_site else ''}tuned(k={p['n_neighbors']},w={p['weights']},m={p['metric']})", best, by_site))
+            tuned.append({"Route": route[by_site], "Modality": NAMES[tgt], "Model": found[-1][0], "conditioned": by_site, "best": p,
+                          "best_mse": min(m for _, m in grid), "grid": [dict(q, mse=m) for q, m in grid]})
+        for kb in (KnnBaseline(route[by_site], name, reg, by_site, src, tgt) for name, reg, by_site in found):
+            m = ImputationMetrics(dims[tgt], va[2].device)
+            for _, a, b, s in batches(va, B):
+                m.update((a, b)[MOD[tgt]], knn_predict(kb, a, b, s))
+            rows.append(_row(kb.route, NAMES[tgt], kb.name, m.compute()))
+            baselines.append(kb)
+    return rows, baselines, tuned
+
+
+def clustering_entries(model, title, plan, means, baselines):
+    """clustering_table's entries: the true features, and per single-target route (the full reconstruction is not an imputation) its
+    target as the model, the training means and that target's k-NN baselines impute it.  Only the model's entries run forwards."""
+    def of_route(name, kwargs, j, tgt):                  # a scope of its own: the lambdas hold THIS route's kwargs, j and tgt
+        return [(name, title, tgt, lambda a, b, s: model(**kwargs(a, b, s))[j]),
+                (name, "MeanImputation", tgt, lambda a, b, s: means[tgt].expand(a.shape[0], -1))] \
+            + [(kb.route, kb.name, tgt, partial(knn_predict, kb)) for kb in baselines if kb.target == tgt]
+    return [("a|b", "original", None, None)] + [e for name, kwargs, outs in plan if len(outs) == 1 for e in of_route(name, kwargs, *outs[0])]
+
+
+@torch.no_grad()
+def tuned_summaries(tuned, model, title, plan, va, baselines, B):
+    """tuned[*]['per_sample_mse']: the box-plot numbers of every tuned regressor beside the model's on its route; one forward per batch each"""
+    by_name = {(kb.route, kb.name): kb for kb in baselines}
+    for t in tuned:
+        kb = by_name[(t["Route"], t["Model"])]
+        route_fw = [(kwargs, outs[0][0]) for _, kwargs, outs in plan if len(outs) == 1 and outs[0][1] == kb.target]
+        per = {t["Model"]: [], title: []}
+        for _, a, b, s in batches(va, B):
+            y = (a, b)[MOD[kb.target]].double()
+            per[t["Model"]].append((knn_predict(kb, a, b, s).double() - y).pow(2).mean(dim=1))
+            if route_fw:
+                kwargs, j = route_fw[0]
+                per[title].append((model(**kwargs(a, b, s))[j].double() - y).pow(2).mean(dim=1))
+        t["per_sample_mse"] = {k: _summary(torch.cat(v)) for k, v in per.items() if v}
+
+
+def _dump(obj, path):
+    if path:
+        with open(path, "w") as f:
+            json.dump(obj, f, indent=1)
+
+
+def run(kind, argv=None, return_clustering=False):
+    args = build_parser(kind).parse_args(argv)
+    check_args(args)
+    if not torch.cuda.is_available():
+        raise SystemExit("evaluate.py needs an MI355X: the product path has no CPU fallback")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    host, train_idx, va, means = load_split(args, dev)
+    model, path = load_model(kind, args, dev)
+    title, plan = KINDS[kind]["title"], routes(kind)
+    targets = sorted({tgt for _, _, outs in plan for _, tgt in outs})
+    dims = {"a": args.input_dim_a, "b": args.input_dim_b}
+    B, n_val = args.batch_size, va[0].shape[0]
+    torch.manual_seed(args.seed)
+    # The model draws eps from ONE Philox stream, per forward, so what a stage computes depends on every forward before it.  No table may
+    # depend on another table's flag, and THIS ORDER is what guarantees it: a stage behind a flag runs its forwards after every stage
+    # whose output that flag must not change.  (The k-NN stage runs no forward; where it stands does not matter.)
+    rows = imputation_rows(model, title, plan, targets, va, means, dims, B)                    # 1. always: every route on every batch
+    knn_rows, baselines, tuned = knn_baselines(args, targets, host, train_idx, va, dims, B)
     rows += knn_rows
     print(f"{title}: {path}  ({n_val} validation rows, batch {B}, {args.precision}, {args.input_dtype} inputs)")
     print_table(rows)
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(rows, f, indent=1)
-    if args.downstream_out and not args.downstream:
-        raise SystemExit("--downstream-out needs --downstream")
-    if args.downstream and (args.downstream_folds < 2 or args.downstream_epochs < 1):
-        raise SystemExit("--downstream-folds must be at least 2 and --downstream-epochs at least 1")
+    _dump(rows, args.out)
     crows = []
-    if args.clustering:
-        # the clustering table: after the metrics, so that the table above does not depend on the flag (eps is drawn per forward)
-        entries = [("a|b", "original", None, None)]
+    if args.clustering:                                                                         # 2. a forward per batch and single-target route
         with torch.no_grad():
-            for name, kwargs, outs in plan:
-                if len(outs) != 1:                               # the full reconstruction is not an imputation
-                    continue
-                j, tgt = outs[0]
-                entries.append((name, title, tgt, lambda i, kwargs=kwargs, j=j: model(**kwargs(va[0][i:i + B], va[1][i:i + B], va[2][i:i + B]))[j]))
-                entries.append((name, "MeanImputation", tgt, lambda i, tgt=tgt: means[tgt].expand(min(B, n_val - i), -1)))
-                for route, model_name, reg, by_site, src_i, rtgt in knn_regs:
-                    if rtgt == tgt:
-                        entries.append((route, model_name, tgt, lambda i, reg=reg, by_site=by_site, src_i=src_i:
-                                        reg.predict(va[src_i][i:i + B], va[2][i:i + B]) if by_site else reg.predict(va[src_i][i:i + B])))
-            crows = clustering_table(entries, va, dims, B, args.clustering_pca,
+            crows = clustering_table(clustering_entries(model, title, plan, means, baselines), va, dims, B, args.clustering_pca,
                                      (args.tsne_perplexity, args.tsne_iters, args.seed) if args.clustering_tsne else None)
         if crows:
             print(f"clustering by site: standardised [a | b] features, silhouette and neighbourhood hit (k={NH_K})"
@@ -405,38 +448,17 @@ def run(kind, argv=None, return_clustering=False):
                   + (f"; TSNE columns: the same on the 2-D t-SNE embedding (perplexity {min(args.tsne_perplexity, n_val - 1):g}, "
                      f"{args.tsne_iters} iterations)" if args.clustering_tsne else ""))
             print_clustering_table(crows)
-        if args.clustering_out:
-            with open(args.clustering_out, "w") as f:
-                json.dump(crows, f, indent=1)
-    if args.downstream:
-        # the downstream task: after both tables, so that neither depends on the flag
+        _dump(crows, args.clustering_out)
+    if args.downstream:                                                                         # 3. the estimated modalities, then the classifiers
         table = downstream_table(kind, model, va, B, args.downstream_folds, args.downstream_epochs, args.seed)
         if table:
             print(f"downstream task: site classification, {args.downstream_folds} stratified folds, at most {args.downstream_epochs} epochs; "
                   "accuracy and weighted averages, mean +- std over the folds")
             print_downstream_table(table)
-        if args.downstream_out:
-            with open(args.downstream_out, "w") as f:
-                json.dump(table, f, indent=1)
-    if args.knn_tune_out:
-        # the box-plot numbers: after every table, so that none of them depends on the flag (the model draws eps per forward)
-        tuned_regs = {(r[0], r[1]): r for r in knn_regs}
-        with torch.no_grad():
-            for t in tuned:
-                _, _, reg, by_site, src_i, tgt = tuned_regs[(t["Route"], t["Model"])]
-                route_fw = [(kwargs, outs[0][0]) for _, kwargs, outs in plan if len(outs) == 1 and outs[0][1] == tgt]
-                per = {t["Model"]: [], title: []}
-                for i in range(0, n_val, B):
-                    a, b, s = va[0][i:i + B], va[1][i:i + B], va[2][i:i + B]
-                    y = (a, b)[1 - src_i].double()
-                    x = (a, b)[src_i]
-                    per[t["Model"]].append(((reg.predict(x, s) if by_site else reg.predict(x)).double() - y).pow(2).mean(dim=1))
-                    if route_fw:
-                        kwargs, j = route_fw[0]
-                        per[title].append((model(**kwargs(a, b, s))[j].double() - y).pow(2).mean(dim=1))
-                t["per_sample_mse"] = {k: _summary(torch.cat(v)) for k, v in per.items() if v}
-        with open(args.knn_tune_out, "w") as f:
-            json.dump(tuned, f, indent=1)
+        _dump(table, args.downstream_out)
+    if args.knn_tune_out:                                                                       # 4. a forward per batch and tuned regressor
+        tuned_summaries(tuned, model, title, plan, va, baselines, B)
+        _dump(tuned, args.knn_tune_out)
     return (rows, crows) if return_clustering else rows
 
 

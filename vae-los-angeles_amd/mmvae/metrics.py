@@ -61,21 +61,13 @@ class ImputationMetrics:
         self.rows = 0
         self._pearson, self._cosine = [], []
 
-    @staticmethod
-    def _operand(t, name):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            dev = t.device if isinstance(t, torch.Tensor) else type(t).__name__
-            raise RuntimeError(f"ImputationMetrics: {name} must be a CUDA/HIP tensor (got {dev}); there is no CPU fallback")
-        if t.dtype not in (torch.float32, torch.bfloat16):
-            raise ValueError(f"ImputationMetrics: {name} must be fp32 or bf16, got {t.dtype}")
-        t = t.detach()
-        if t.stride(-1) != 1 or (t.dim() == 2 and t.shape[0] > 1 and t.stride(0) < t.shape[1]):      # e.g. an expanded row
-            t = t.contiguous()
-        return t
-
     def update(self, y_true, y_pred):
-        y_true, y_pred = self._operand(y_true, "y_true"), self._operand(y_pred, "y_pred")
-        if y_true.dim() != 2 or y_true.shape[1] != self.n_features:
+        one_row = isinstance(y_pred, torch.Tensor) and y_pred.dim() == 1          # (F,): the same prediction for every sample
+        y_true = ops._device_matrix(y_true, "y_true", "ImputationMetrics")
+        y_pred = ops._device_matrix(y_pred[None] if one_row else y_pred, "y_pred", "ImputationMetrics")     # copies e.g. an expanded row
+        if one_row:
+            y_pred = y_pred[0]
+        if y_true.shape[1] != self.n_features:
             raise ValueError(f"ImputationMetrics: y_true is {tuple(y_true.shape)}, need (rows, {self.n_features})")
         M = y_true.shape[0]
         if M == 0:

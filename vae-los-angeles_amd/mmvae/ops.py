@@ -128,10 +128,16 @@ def _ld(t):
     return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
 
 
-def _device_matrix(t, name, what):
-    """t as a 2-D fp32 / bf16 device matrix the kernels can read in place (a 1-D tensor is one column); `what` names the caller"""
+def _no_cpu(t, name, what):
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
         raise RuntimeError(f"{what}: {name} must be a CUDA/HIP tensor; there is no CPU fallback")
+
+
+def _device_matrix(t, name, what):
+    """ACCEPT AND NORMALISE what a user hands over: t, detached, as a 2-D fp32 / bf16 device matrix the kernels can read in place (a
+    1-D tensor is one column; copied to contiguous only where rows overlap or the inner stride is not 1); `what` names the caller.
+    The wrappers below do not normalise: they check with _operand and refuse."""
+    _no_cpu(t, name, what)
     if t.dim() == 1:
         t = t.unsqueeze(1)
     if t.dim() != 2 or t.dtype not in (torch.float32, torch.bfloat16):
@@ -178,13 +184,9 @@ def to_bf16_rows(x):
     """(N, F) fp32 or bf16 device tensor -> a NEW (N, F) bf16 view of an (N, ceil8(F)) buffer in the padded-row layout, pads zeroed,
     values rounded as x.to(torch.bfloat16).  Convert a dataset once and hand it to the model / GraphedTrainStep(dataset=...): the
     first-layer GEMMs, their dW GEMMs and the reconstruction losses then read 2 bytes per element instead of 4."""
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        dev = x.device if isinstance(x, torch.Tensor) else type(x).__name__
-        raise RuntimeError(f"to_bf16_rows: the MI355X path needs CUDA/HIP tensors (got {dev}); there is no CPU fallback")
-    if x.dim() != 2 or x.dtype not in (torch.float32, torch.bfloat16):
+    if isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 1:          # a vector has no padded rows; _device_matrix would make it a column
         raise ValueError(f"to_bf16_rows: need a 2-D fp32 or bf16 tensor, got {tuple(x.shape)} {x.dtype}")
-    if x.stride(1) != 1:
-        x = x.contiguous()
+    x = _device_matrix(x, "x", "to_bf16_rows")
     N, F = x.shape
     out = torch.empty(N, ceil_to(F, 8), dtype=torch.bfloat16, device=x.device)[:, :F]
     if N == 0 or F == 0:
@@ -709,14 +711,6 @@ def gather_rows(pairs, idx, src_rows):
         L.check(L.load().mmvae_gather_rows(C.cast(items, C.c_void_p), len(pairs), idx.data_ptr(), B, src_rows, _stream()), "mmvae_gather_rows")
 
 
-def _metrics_operand(t, name, N):
-    """(pointer, dtype, leading dimension) of a metrics operand: (M, N) with unit inner stride and any row stride >= N, fp32 or bf16."""
-    _mat(t, name)
-    if t.shape[1] != N or (t.shape[0] > 1 and t.stride(0) < N):
-        raise ValueError(f"recon_metrics: {name} is {tuple(t.shape)} / {t.stride()}, need (M, {N}) rows that do not overlap")
-    return t.data_ptr(), _dt(t), _ld(t)
-
-
 def recon_metrics(pred, target, col_shift, col_acc, row_pearson, row_cosine):
     """One streaming pass over (prediction, target) (mmvae_recon_metrics): row_pearson / row_cosine (fp32 (M,)) are written,
     col_acc (float64 (4, N): sum (y - c), sum (y - c)^2, sum (p - y)^2, sum |p - y| per column, c = col_shift or 0) is ACCUMULATED
@@ -726,16 +720,14 @@ def recon_metrics(pred, target, col_shift, col_acc, row_pearson, row_cosine):
     M, N = target.shape
     if M < 1 or N < 1:
         raise ValueError(f"recon_metrics: empty target {tuple(target.shape)}")
-    t_ptr, t_dt, t_ld = _metrics_operand(target, "target", N)
+    t_dt, t_ld = _dt(_operand(target, "target", "recon_metrics", dtypes=None)), _ld(target)
     if pred.dim() == 1:
         if not pred.is_cuda or pred.shape[0] != N or pred.stride(0) != 1:
             raise ValueError(f"recon_metrics: a broadcast prediction must be a contiguous ({N},) device tensor, got {tuple(pred.shape)}")
-        p_ptr, p_dt, p_ld, p_rows = pred.data_ptr(), _dt(pred), 0, 1
+        p_dt, p_ld, p_rows = _dt(pred), 0, 1
     else:
-        if pred.shape[0] != M:
-            raise ValueError(f"recon_metrics: prediction {tuple(pred.shape)} against target {tuple(target.shape)}")
-        p_ptr, p_dt, p_ld = _metrics_operand(pred, "pred", N)
-        p_rows = M
+        _mat(pred, "pred")                       # a host tensor is a ValueError here, as for the target
+        p_dt, p_ld, p_rows = _dt(_operand(pred, "pred", "recon_metrics", dtypes=None, rows=M, cols=N)), _ld(pred), M
     for t, name, dt, shape in ((col_shift, "col_shift", torch.float32, (N,)), (col_acc, "col_acc", torch.float64, (4, N)),
                                (row_pearson, "row_pearson", torch.float32, (M,)), (row_cosine, "row_cosine", torch.float32, (M,))):
         if t is None and name == "col_shift":
@@ -744,7 +736,7 @@ def recon_metrics(pred, target, col_shift, col_acc, row_pearson, row_cosine):
             raise ValueError(f"recon_metrics: {name} must be a contiguous {dt} device tensor of shape {shape}")
     if len({t.device for t in (pred, target, col_acc, row_pearson, row_cosine)} | ({col_shift.device} if col_shift is not None else set())) != 1:
         raise ValueError("recon_metrics: all operands must live on one device")
-    a = L.MetricsArgs(M, N, p_ptr, p_dt, p_ld, t_ptr, t_dt, t_ld, _p(col_shift), col_acc.data_ptr(), row_pearson.data_ptr(),
+    a = L.MetricsArgs(M, N, pred.data_ptr(), p_dt, p_ld, target.data_ptr(), t_dt, t_ld, _p(col_shift), col_acc.data_ptr(), row_pearson.data_ptr(),
                       row_cosine.data_ptr())
     nbytes = M * N * target.element_size() + p_rows * N * pred.element_size() + 8 * M + 2 * 32 * N + (4 * N if col_shift is not None else 0)
     with stream_span("recon_metrics", nbytes):
@@ -752,18 +744,26 @@ def recon_metrics(pred, target, col_shift, col_acc, row_pearson, row_cosine):
 
 
 # --------------------------------------------------------------------------------------------
-# what the wrappers of the row-tile kernels share (k-NN, silhouette, PCA below): operand, vector, output and workspace checks
+# what the evaluation wrappers (recon_metrics above, k-NN, silhouette, PCA, t-SNE and the site classifier below) share: ONE in-place
+# operand check, and the vector, output and workspace checks
 # --------------------------------------------------------------------------------------------
-def _rows_operand(t, name, what, F=None):
-    """(pointer, dtype, leading dimension) of a (rows, F) fp32 / bf16 device matrix with unit inner stride and rows that do not overlap."""
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"{what}: {name} must be a CUDA/HIP tensor; there is no CPU fallback")
-    _mat(t, name)
-    if t.dtype not in (torch.float32, torch.bfloat16):
-        raise ValueError(f"{what}: {name} must be fp32 or bf16, got {t.dtype}")
-    if t.shape[0] < 1 or t.shape[1] < 1 or (F is not None and t.shape[1] != F) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
-        raise ValueError(f"{what}: {name} is {tuple(t.shape)} / {t.stride()}, need (rows >= 1, {F if F is not None else 'F >= 1'}) rows that do not overlap")
-    return t.data_ptr(), _dt(t), _ld(t)
+def _operand(t, name, what, *, dtypes=(torch.float32, torch.bfloat16), rows=None, cols=None, dev=None, align=0, ld_multiple=0, contiguous=False):
+    """t, if it is a device matrix a kernel can read or write IN PLACE: 2-D, at least 1 x 1, unit inner stride, rows that do not overlap,
+    a dtype among `dtypes` (None: left to the caller's _dt and its TypeError), and as asked: exactly `rows` / `cols`, on `dev`, the base
+    address a multiple of `align` bytes, the row stride a multiple of `ld_multiple` elements, contiguous.  Anything else is refused; the
+    caller takes data_ptr(), _dt() and _ld() of what comes back."""
+    _no_cpu(t, name, what)
+    if (t.dim() != 2 or (dtypes is not None and t.dtype not in dtypes) or t.shape[0] < 1 or t.shape[1] < 1 or t.stride(1) != 1
+            or (t.shape[0] > 1 and t.stride(0) < t.shape[1]) or (rows is not None and t.shape[0] != rows)
+            or (cols is not None and t.shape[1] != cols) or (dev is not None and t.device != dev) or (align and t.data_ptr() % align)
+            or (ld_multiple and _ld(t) % ld_multiple) or (contiguous and not t.is_contiguous())):
+        need = [f"({'rows >= 1' if rows is None else rows}, {'cols >= 1' if cols is None else cols}) matrix"
+                + ("" if dtypes is None else " of " + " / ".join(str(d) for d in dtypes)),
+                "contiguous" if contiguous else "unit inner stride, rows that do not overlap"]
+        need += ["on the operands' device"] * (dev is not None) + [f"{align}-byte aligned"] * bool(align)
+        need += [f"row stride a multiple of {ld_multiple}"] * bool(ld_multiple)
+        raise ValueError(f"{what}: {name} must be a {', '.join(need)}; got {tuple(t.shape)} {t.dtype} / {t.stride()}")
+    return t
 
 
 def _vector(t, name, what, dt, n, dev, strided=False):
@@ -792,9 +792,27 @@ def _out_view(out, name, what, dt, rows, cols, dev):
     return out
 
 
+def _out_vector(out, name, what, dt, n, dev, strided=False):
+    """`out`, a `dt` (n,) tensor on `dev` as _vector checks it, or a new one"""
+    return torch.empty(n, dtype=dt, device=dev) if out is None else _vector(out, name, what, dt, n, dev, strided)
+
+
+def _ld0(t):
+    return 0 if t is None else _ld(t)
+
+
 def _workspace(nbytes, dev):
     """8-byte aligned device scratch of at least nbytes; None for 0"""
     return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev) if nbytes else None
+
+
+def _work(work, nbytes, what, dev):
+    """The caller's workspace if it is a contiguous int64 tensor of at least nbytes on `dev`, or a new one (None for 0 bytes)"""
+    if work is None:
+        return _workspace(nbytes, dev)
+    if not isinstance(work, torch.Tensor) or work.dtype != torch.int64 or not work.is_contiguous() or work.numel() * 8 < nbytes or work.device != dev:
+        raise ValueError(f"{what}: work must be a contiguous int64 tensor of at least {nbytes} bytes on the operand's device")
+    return work
 
 
 def _plan(symbol, *args, outs=(C.c_int32,)):
@@ -823,85 +841,77 @@ def knn_work_bytes(Mq, Nt, k):
     return _plan("mmvae_knn_work_bytes", Mq, Nt, k, outs=(C.c_int64,))
 
 
+def knn_l1_work_bytes(Mq, Nt, k):
+    return _plan("mmvae_knn_l1_work_bytes", Mq, Nt, k, outs=(C.c_int64,))
+
+
+def _knn_search(what, work_bytes, kind, q, t, k, shift, idx_out, dist_out, dist_name):
+    """The one body of knn_search and knn_search_l1: entry point mmvae_<what>, workspace size work_bytes(Mq, Nt, k), probe kind `kind`;
+    dist_out is False for no distances, else the caller's `dist_name` or None."""
+    _operand(q, "q", what)
+    Mq, F = q.shape
+    _operand(t, "t", what, cols=F)
+    Nt = t.shape[0]
+    k = int(k)
+    if not 1 <= k <= min(Nt, L.KNN_MAXK):
+        raise ValueError(f"{what}: k = {k} outside [1, min({Nt} training rows, {L.KNN_MAXK})]")
+    if t.device != q.device:
+        raise ValueError(f"{what}: all operands must live on one device")
+    shift = _shift(shift, what, F, q.device)
+    idx = _out_view(idx_out, "idx_out", what, torch.int32, Mq, k, q.device)
+    d = None if dist_out is False else _out_view(dist_out, dist_name, what, torch.float32, Mq, k, q.device)
+    work = _workspace(work_bytes(Mq, Nt, k), q.device)
+    a = L.KnnArgs(q.data_ptr(), t.data_ptr(), _p(shift), idx.data_ptr(), _p(d), _p(work), _ld(q), _ld(t), _ld(idx), _ld0(d),
+                  work.numel() * 8 if work is not None else 0, Mq, Nt, F, k, _dt(q), _dt(t))
+    with probe_span(what, lambda: dict(kind=kind, flops=2.0 * Mq * Nt * F, M=Mq, N=Nt, K=F)):
+        L.check(getattr(L.load(), "mmvae_" + what)(C.byref(a), _stream()), "mmvae_" + what)
+    return idx, d
+
+
 def knn_search(q, t, k, shift=None, dist2=True, *, idx_out=None, dist2_out=None):
     """The k nearest training rows (euclidean) of every query row (mmvae_knn_search): idx int32 (Mq, k) ascending by (distance key,
     training index), and the squared distances fp32 (Mq, k) unless dist2 is False (then None).  q (Mq, F), t (Nt, F): fp32 or bf16,
     unit inner stride, any row stride (padded bf16 rows included).  shift (F,) fp32 is subtracted from both operands on load (pass the
     training column means: the distances do not change, their rounding does).  idx_out / dist2_out: write into these (views allowed)."""
-    q_ptr, q_dt, q_ld = _rows_operand(q, "q", "knn_search")
-    Mq, F = q.shape
-    t_ptr, t_dt, t_ld = _rows_operand(t, "t", "knn_search", F)
-    Nt = t.shape[0]
-    k = int(k)
-    if not 1 <= k <= min(Nt, L.KNN_MAXK):
-        raise ValueError(f"knn_search: k = {k} outside [1, min({Nt} training rows, {L.KNN_MAXK})]")
-    if t.device != q.device:
-        raise ValueError("knn_search: all operands must live on one device")
-    shift = _shift(shift, "knn_search", F, q.device)
-    idx = _out_view(idx_out, "idx_out", "knn_search", torch.int32, Mq, k, q.device)
-    d2 = _out_view(dist2_out, "dist2_out", "knn_search", torch.float32, Mq, k, q.device) if dist2 else None
-    work = _workspace(knn_work_bytes(Mq, Nt, k), q.device)
-    a = L.KnnArgs(q_ptr, t_ptr, _p(shift), idx.data_ptr(), _p(d2), work.data_ptr(), q_ld, t_ld, _ld(idx), _ld(d2) if d2 is not None else 0,
-                  work.numel() * 8, Mq, Nt, F, k, q_dt, t_dt)
-    with probe_span("knn_search", lambda: dict(kind="gemm", flops=2.0 * Mq * Nt * F, M=Mq, N=Nt, K=F)):
-        L.check(L.load().mmvae_knn_search(C.byref(a), _stream()), "mmvae_knn_search")
-    return idx, d2
-
-
-def knn_mean_rows(idx, y, out=None):
-    """out[i] = mean over n of y[idx[i][n]] in fp32, summed in ascending n (mmvae_knn_mean_rows): uniform k-NN regression.
-    idx int32 (Mq, k), y (Ny, Fy) fp32 or bf16, out fp32 (Mq, Fy); indices outside [0, Ny) are clamped."""
-    y_ptr, y_dt, y_ld = _rows_operand(y, "y", "knn_mean_rows")
-    if not isinstance(idx, torch.Tensor) or not idx.is_cuda or idx.dtype != torch.int32 or idx.dim() != 2 or idx.stride(1) != 1 or idx.shape[0] < 1 \
-            or not 1 <= idx.shape[1] <= L.KNN_MAXK:
-        raise ValueError(f"knn_mean_rows: idx must be an int32 (Mq, 1 <= k <= {L.KNN_MAXK}) device tensor with unit inner stride")
-    Mq, k = idx.shape
-    Ny, Fy = y.shape
-    if idx.device != y.device:
-        raise ValueError("knn_mean_rows: all operands must live on one device")
-    out = _out_view(out, "out", "knn_mean_rows", torch.float32, Mq, Fy, y.device)
-    with stream_span("knn_mean_rows", Mq * k * (4 + Fy * y.element_size()) + 4 * Mq * Fy):
-        L.check(L.load().mmvae_knn_mean_rows(idx.data_ptr(), _ld(idx), y_ptr, y_dt, y_ld, out.data_ptr(), _ld(out), Mq, k, Ny, Fy, _stream()),
-                "mmvae_knn_mean_rows")
-    return out
-
-
-def knn_l1_work_bytes(Mq, Nt, k):
-    return _plan("mmvae_knn_l1_work_bytes", Mq, Nt, k, outs=(C.c_int64,))
+    return _knn_search("knn_search", knn_work_bytes, "gemm", q, t, k, shift, idx_out, dist2_out if dist2 else False, "dist2_out")
 
 
 def knn_search_l1(q, t, k, dist=True, *, idx_out=None, dist_out=None):
     """The k nearest training rows of every query row under the manhattan distance (mmvae_knn_search_l1): idx int32 (Mq, k) ascending
     by (distance, training index), and the L1 distances themselves -- not squared -- fp32 (Mq, k) unless dist is False (then None).
     Every distance is one fp32 chain of |q - t| over the columns in ascending order.  Operands as knn_search; there is no shift."""
-    q_ptr, q_dt, q_ld = _rows_operand(q, "q", "knn_search_l1")
-    Mq, F = q.shape
-    t_ptr, t_dt, t_ld = _rows_operand(t, "t", "knn_search_l1", F)
-    Nt = t.shape[0]
-    k = int(k)
-    if not 1 <= k <= min(Nt, L.KNN_MAXK):
-        raise ValueError(f"knn_search_l1: k = {k} outside [1, min({Nt} training rows, {L.KNN_MAXK})]")
-    if t.device != q.device:
-        raise ValueError("knn_search_l1: all operands must live on one device")
-    idx = _out_view(idx_out, "idx_out", "knn_search_l1", torch.int32, Mq, k, q.device)
-    d = _out_view(dist_out, "dist_out", "knn_search_l1", torch.float32, Mq, k, q.device) if dist else None
-    work = _workspace(knn_l1_work_bytes(Mq, Nt, k), q.device)
-    a = L.KnnArgs(q_ptr, t_ptr, None, idx.data_ptr(), _p(d), _p(work), q_ld, t_ld, _ld(idx), _ld(d) if d is not None else 0,
-                  work.numel() * 8 if work is not None else 0, Mq, Nt, F, k, q_dt, t_dt)
-    with probe_span("knn_search_l1", lambda: dict(kind="valu", flops=2.0 * Mq * Nt * F, M=Mq, N=Nt, K=F)):
-        L.check(L.load().mmvae_knn_search_l1(C.byref(a), _stream()), "mmvae_knn_search_l1")
-    return idx, d
+    return _knn_search("knn_search_l1", knn_l1_work_bytes, "valu", q, t, k, None, idx_out, dist_out if dist else False, "dist_out")
+
+
+def _knn_idx(idx, what):
+    """(Mq, k) of idx, the int32 (Mq, 1 <= k <= KNN_MAXK) neighbour lists of a search (the first k columns of a wider one are allowed)"""
+    if not isinstance(idx, torch.Tensor) or not idx.is_cuda or idx.dtype != torch.int32 or idx.dim() != 2 or idx.stride(1) != 1 or idx.shape[0] < 1 \
+            or not 1 <= idx.shape[1] <= L.KNN_MAXK:
+        raise ValueError(f"{what}: idx must be an int32 (Mq, 1 <= k <= {L.KNN_MAXK}) device tensor with unit inner stride")
+    return idx.shape
+
+
+def knn_mean_rows(idx, y, out=None):
+    """out[i] = mean over n of y[idx[i][n]] in fp32, summed in ascending n (mmvae_knn_mean_rows): uniform k-NN regression.
+    idx int32 (Mq, k), y (Ny, Fy) fp32 or bf16, out fp32 (Mq, Fy); indices outside [0, Ny) are clamped."""
+    _operand(y, "y", "knn_mean_rows")
+    Mq, k = _knn_idx(idx, "knn_mean_rows")
+    Ny, Fy = y.shape
+    if idx.device != y.device:
+        raise ValueError("knn_mean_rows: all operands must live on one device")
+    out = _out_view(out, "out", "knn_mean_rows", torch.float32, Mq, Fy, y.device)
+    with stream_span("knn_mean_rows", Mq * k * (4 + Fy * y.element_size()) + 4 * Mq * Fy):
+        L.check(L.load().mmvae_knn_mean_rows(idx.data_ptr(), _ld(idx), y.data_ptr(), _dt(y), _ld(y), out.data_ptr(), _ld(out), Mq, k, Ny, Fy,
+                                             _stream()), "mmvae_knn_mean_rows")
+    return out
 
 
 def knn_weighted_rows(idx, dist, y, squared, out=None):
     """out[i] = sum_n w_n y[idx[i][n]] / sum_n w_n in fp32 with sklearn's weights='distance' (mmvae_knn_weighted_rows): w = 1 / d, or
     the indicator of d == 0 where a row has zero distances; d = dist, or sqrt(dist) when `squared` (the dist2 of knn_search).
     idx int32 (Mq, k) and dist fp32 (Mq, k) may be the first k columns of a wider search; y (Ny, Fy) fp32 or bf16, out fp32 (Mq, Fy)."""
-    y_ptr, y_dt, y_ld = _rows_operand(y, "y", "knn_weighted_rows")
-    if not isinstance(idx, torch.Tensor) or not idx.is_cuda or idx.dtype != torch.int32 or idx.dim() != 2 or idx.stride(1) != 1 or idx.shape[0] < 1 \
-            or not 1 <= idx.shape[1] <= L.KNN_MAXK:
-        raise ValueError(f"knn_weighted_rows: idx must be an int32 (Mq, 1 <= k <= {L.KNN_MAXK}) device tensor with unit inner stride")
-    Mq, k = idx.shape
+    _operand(y, "y", "knn_weighted_rows")
+    Mq, k = _knn_idx(idx, "knn_weighted_rows")
     if not isinstance(dist, torch.Tensor) or not dist.is_cuda or dist.dtype != torch.float32 or tuple(dist.shape) != (Mq, k) or dist.stride(1) != 1:
         raise ValueError(f"knn_weighted_rows: dist must be a float32 ({Mq}, {k}) device tensor with unit inner stride")
     Ny, Fy = y.shape
@@ -909,8 +919,8 @@ def knn_weighted_rows(idx, dist, y, squared, out=None):
         raise ValueError("knn_weighted_rows: all operands must live on one device")
     out = _out_view(out, "out", "knn_weighted_rows", torch.float32, Mq, Fy, y.device)
     with stream_span("knn_weighted_rows", Mq * k * (8 + Fy * y.element_size()) + 4 * Mq * Fy):
-        L.check(L.load().mmvae_knn_weighted_rows(idx.data_ptr(), _ld(idx), dist.data_ptr(), _ld(dist), 1 if squared else 0, y_ptr, y_dt, y_ld,
-                                                 out.data_ptr(), _ld(out), Mq, k, Ny, Fy, _stream()), "mmvae_knn_weighted_rows")
+        L.check(L.load().mmvae_knn_weighted_rows(idx.data_ptr(), _ld(idx), dist.data_ptr(), _ld(dist), 1 if squared else 0, y.data_ptr(), _dt(y),
+                                                 _ld(y), out.data_ptr(), _ld(out), Mq, k, Ny, Fy, _stream()), "mmvae_knn_weighted_rows")
     return out
 
 
@@ -933,7 +943,7 @@ def silhouette_samples(x, order, class_start, shift=None, *, splits=0, s_out=Non
     class_start[c + 1]].  shift (F,) fp32 is subtracted from every element on load (pass the column means).  splits: 0 = the library's
     choice, 1 .. 64 forces that many column splits.  *_out: write into these (views allowed)."""
     what = "silhouette_samples"
-    x_ptr, x_dt, x_ld = _rows_operand(x, "x", what)
+    _operand(x, "x", what)
     N, F = x.shape
     dev = x.device
     if not isinstance(class_start, torch.Tensor) or class_start.dim() != 1:
@@ -946,11 +956,10 @@ def silhouette_samples(x, order, class_start, shift=None, *, splits=0, s_out=Non
         _vector(order, "order", what, torch.int32, N, dev)
     shift = _shift(shift, what, F, dev)
     splits = _splits_arg(splits, what)
-    outs = [_vector(torch.empty(N, dtype=torch.float32, device=dev) if o is None else o, name, what, torch.float32, N, dev, strided=True)
-            for o, name in ((s_out, "s_out"), (intra_out, "intra_out"), (inter_out, "inter_out"))]
+    outs = [_out_vector(o, name, what, torch.float32, N, dev, strided=True) for o, name in ((s_out, "s_out"), (intra_out, "intra_out"), (inter_out, "inter_out"))]
     work = _workspace(silhouette_work_bytes(N, nc, splits), dev)
-    a = L.SilhouetteArgs(x_ptr, _p(shift), _p(order), class_start.data_ptr(), outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(),
-                         work.data_ptr(), x_ld, work.numel() * 8, N, F, nc, splits, x_dt, 0)
+    a = L.SilhouetteArgs(x.data_ptr(), _p(shift), _p(order), class_start.data_ptr(), outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(),
+                         work.data_ptr(), _ld(x), work.numel() * 8, N, F, nc, splits, _dt(x), 0)
     with probe_span("silhouette_samples", lambda: dict(kind="gemm", flops=2.0 * N * N * F, M=N, N=N, K=F)):
         L.check(L.load().mmvae_silhouette_samples(C.byref(a), _stream()), "mmvae_silhouette_samples")
     return tuple(outs)
@@ -972,14 +981,14 @@ def pca_scatter(x, shift, splits=0, out=None):
     """S = (x - shift)^T (x - shift), fp32 (F, F), bitwise symmetric (mmvae_pca_scatter).  x (N, F): fp32 or bf16, unit inner stride, any
     row stride (padded bf16 rows included); shift (F,) fp32 or None is subtracted from every element on load (pass the column means).
     splits: 0 = the library's choice, 1 .. 64 forces that many row splits.  out: write into this (a view is allowed)."""
-    x_ptr, x_dt, x_ld = _rows_operand(x, "x", "pca_scatter")
+    _operand(x, "x", "pca_scatter")
     N, F = x.shape
     shift = _shift(shift, "pca_scatter", F, x.device)
     splits = _splits_arg(splits, "pca_scatter")
     s = _out_view(out, "out", "pca_scatter", torch.float32, F, F, x.device)
     nbytes = pca_scatter_work_bytes(N, F, splits)
     work = _workspace(nbytes, x.device)
-    a = L.PcaScatterArgs(x_ptr, _p(shift), s.data_ptr(), _p(work), x_ld, _ld(s), nbytes, N, F, splits, x_dt)
+    a = L.PcaScatterArgs(x.data_ptr(), _p(shift), s.data_ptr(), _p(work), _ld(x), _ld(s), nbytes, N, F, splits, _dt(x))
     with probe_span("pca_scatter", lambda: dict(kind="gemm", flops=1.0 * N * F * F, M=F, N=F, K=N)):
         L.check(L.load().mmvae_pca_scatter(C.byref(a), _stream()), "mmvae_pca_scatter")
     return s
@@ -988,15 +997,14 @@ def pca_scatter(x, shift, splits=0, out=None):
 def pca_project(x, shift, v, out=None):
     """y = (x - shift) v^T, fp32 (N, k) (mmvae_pca_project).  x, shift as pca_scatter; v (k, F) fp32 with unit inner stride,
     1 <= k <= PCA_MAXK.  A row of y depends on that row of x, shift and v alone."""
-    x_ptr, x_dt, x_ld = _rows_operand(x, "x", "pca_project")
+    _operand(x, "x", "pca_project")
     N, F = x.shape
     shift = _shift(shift, "pca_project", F, x.device)
-    v_ptr, v_dt, v_ld = _rows_operand(v, "v", "pca_project", F)
-    k = v.shape[0]
-    if v.dtype != torch.float32 or not 1 <= k <= L.PCA_MAXK or v.device != x.device:
-        raise ValueError(f"pca_project: v must be an fp32 (1 <= k <= {L.PCA_MAXK}, {F}) tensor on x's device, got {tuple(v.shape)} {v.dtype}")
+    k = _operand(v, "v", "pca_project", dtypes=(torch.float32,), cols=F, dev=x.device).shape[0]
+    if k > L.PCA_MAXK:
+        raise ValueError(f"pca_project: v has {k} rows, more than {L.PCA_MAXK}")
     y = _out_view(out, "out", "pca_project", torch.float32, N, k, x.device)
-    a = L.PcaProjectArgs(x_ptr, _p(shift), v_ptr, y.data_ptr(), x_ld, v_ld, _ld(y), N, F, k, x_dt)
+    a = L.PcaProjectArgs(x.data_ptr(), _p(shift), v.data_ptr(), y.data_ptr(), _ld(x), _ld(v), _ld(y), N, F, k, _dt(x))
     with probe_span("pca_project", lambda: dict(kind="gemm", flops=2.0 * N * F * k, M=N, N=k, K=F)):
         L.check(L.load().mmvae_pca_project(C.byref(a), _stream()), "mmvae_pca_project")
     return y
@@ -1005,28 +1013,17 @@ def pca_project(x, shift, v, out=None):
 # --------------------------------------------------------------------------------------------
 # t-SNE (include/mmvae_hip.h: mmvae_tsne_affinities, mmvae_tsne_gradient, mmvae_tsne_update)
 # --------------------------------------------------------------------------------------------
-def _f32_matrix(t, name, what, cols=None):
-    """t, an fp32 (rows >= 1, cols) device tensor with unit inner stride (a view is allowed)"""
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"{what}: {name} must be a CUDA/HIP tensor; there is no CPU fallback")
-    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1 or t.stride(1) != 1 \
-            or (t.shape[0] > 1 and t.stride(0) < t.shape[1]) or (cols is not None and t.shape[1] != cols):
-        raise ValueError(f"{what}: {name} must be an fp32 (rows, {cols or 'cols'}) tensor with unit inner stride, got {tuple(t.shape)} {t.dtype}")
-    return t
-
-
 def tsne_affinities(dist2, perplexity, *, p_out=None, beta_out=None):
     """(p, beta): the conditional p_{j|i} fp32 (N, k) of sklearn's _binary_search_perplexity on a row's k squared neighbour distances
     dist2 fp32 (N, k) (the row itself not among them), and the precision fp32 (N,) each row's search ended on (mmvae_tsne_affinities)."""
     what = "tsne_affinities"
-    d = _f32_matrix(dist2, "dist2", what)
+    d = _operand(dist2, "dist2", what, dtypes=(torch.float32,))
     N, k = d.shape
     perplexity = float(perplexity)
     if not 0.0 < perplexity < k:
         raise ValueError(f"{what}: perplexity = {perplexity} outside (0, k = {k})")
     p = _out_view(p_out, "p_out", what, torch.float32, N, k, d.device)
-    beta = _vector(torch.empty(N, dtype=torch.float32, device=d.device) if beta_out is None else beta_out, "beta_out", what, torch.float32, N,
-                   d.device, strided=True)
+    beta = _out_vector(beta_out, "beta_out", what, torch.float32, N, d.device, strided=True)
     a = L.TsneAffinitiesArgs(d.data_ptr(), p.data_ptr(), beta.data_ptr(), _ld(d), _ld(p), N, k, perplexity, 0)
     with stream_span(what, 8 * N * k):
         L.check(L.load().mmvae_tsne_affinities(C.byref(a), _stream()), "mmvae_tsne_affinities")
@@ -1048,11 +1045,9 @@ def tsne_gradient(y, row_ptr, col, val, exaggeration=1.0, *, error=False, z_row=
     err.double().sum() is the KL divergence over the stored entries.  splits: 0 = the library's choice, 1 .. 64 forces that many column
     splits.  work: a workspace from an earlier call's sizes (an int64 tensor of tsne_gradient_work_bytes(N, splits) / 8 elements)."""
     what = "tsne_gradient"
-    y = _f32_matrix(y, "y", what, 2)
-    N = y.shape[0]
-    dev = y.device
-    if N < 2 or not y.is_contiguous():
-        raise ValueError(f"{what}: y must be a contiguous (N >= 2, 2) tensor")
+    N, dev = _operand(y, "y", what, dtypes=(torch.float32,), cols=2, contiguous=True).shape[0], y.device
+    if N < 2:
+        raise ValueError(f"{what}: y must have at least 2 rows")
     _vector(row_ptr, "row_ptr", what, torch.int32, N + 1, dev)
     if not isinstance(col, torch.Tensor) or col.dim() != 1:
         raise ValueError(f"{what}: col must be an int32 (nnz,) device tensor")
@@ -1066,11 +1061,7 @@ def tsne_gradient(y, row_ptr, col, val, exaggeration=1.0, *, error=False, z_row=
     z = torch.empty(1, dtype=torch.float32, device=dev)
     err = torch.empty(N, dtype=torch.float32, device=dev) if error else None
     zr = torch.empty(N, dtype=torch.float32, device=dev) if z_row else None
-    nbytes = tsne_gradient_work_bytes(N, splits)
-    if work is None:
-        work = _workspace(nbytes, dev)
-    elif not isinstance(work, torch.Tensor) or work.dtype != torch.int64 or not work.is_contiguous() or work.numel() * 8 < nbytes or work.device != dev:
-        raise ValueError(f"{what}: work must be a contiguous int64 tensor of at least {nbytes} bytes on y's device")
+    work = _work(work, tsne_gradient_work_bytes(N, splits), what, dev)
     a = L.TsneGradientArgs(y.data_ptr(), row_ptr.data_ptr(), _p(col) if nnz else None, _p(val) if nnz else None, grad.data_ptr(), z.data_ptr(),
                            _p(err), _p(zr), work.data_ptr(), nnz, work.numel() * 8, N, splits, float(exaggeration), 0)
     with probe_span(what, lambda: dict(kind="valu", flops=10.0 * N * N, M=N, N=N, K=2)):
@@ -1086,19 +1077,12 @@ def tsne_update(y, update, gains, grad, momentum, learning_rate, *, grad_norm=Fa
     """One step of sklearn's _gradient_descent in place on y, update, gains (fp32 (N, 2), contiguous) from grad (mmvae_tsne_update).
     Returns |gains * grad|_2 as an fp32 (1,) device tensor when grad_norm is set, else None."""
     what = "tsne_update"
-    y = _f32_matrix(y, "y", what, 2)
-    N, dev = y.shape[0], y.device
-    for t, name in ((y, "y"), (update, "update"), (gains, "gains"), (grad, "grad")):
-        _f32_matrix(t, name, what, 2)
-        if t.shape[0] != N or not t.is_contiguous() or t.device != dev:
-            raise ValueError(f"{what}: {name} must be a contiguous fp32 ({N}, 2) tensor on y's device")
+    N, dev = _operand(y, "y", what, dtypes=(torch.float32,), cols=2, contiguous=True).shape[0], y.device
+    for t, name in ((update, "update"), (gains, "gains"), (grad, "grad")):
+        _operand(t, name, what, dtypes=(torch.float32,), rows=N, cols=2, dev=dev, contiguous=True)
     gn = torch.empty(1, dtype=torch.float32, device=dev) if grad_norm else None
-    nbytes = tsne_update_work_bytes(N)
-    if grad_norm and work is None:
-        work = _workspace(nbytes, dev)
-    if work is not None and (not isinstance(work, torch.Tensor) or work.dtype != torch.int64 or not work.is_contiguous()
-                             or work.numel() * 8 < nbytes or work.device != dev):
-        raise ValueError(f"{what}: work must be a contiguous int64 tensor of at least {nbytes} bytes on y's device")
+    if grad_norm or work is not None:
+        work = _work(work, tsne_update_work_bytes(N), what, dev)
     a = L.TsneUpdateArgs(y.data_ptr(), update.data_ptr(), gains.data_ptr(), grad.data_ptr(), _p(gn), _p(work),
                          work.numel() * 8 if work is not None else 0, N, float(momentum), float(learning_rate), 0)
     with stream_span(what, 7 * 8 * N):
@@ -1109,12 +1093,7 @@ def tsne_update(y, update, gains, grad, momentum, learning_rate, *, grad_norm=Fa
 # --------------------------------------------------------------------------------------------
 # The site classifier of the downstream task (include/mmvae_hip.h: mmvae_ln_act_fwd, mmvae_ln_act_bwd, mmvae_wce_mean)
 # --------------------------------------------------------------------------------------------
-def _ln_operand(t, name, what, rows, cols, dev):
-    """t, an fp32 (rows, cols) device matrix whose rows the kernels read as 16-byte chunks"""
-    t = _f32_matrix(t, name, what, cols)
-    if t.shape[0] != rows or t.device != dev or _ld(t) % 4 or t.data_ptr() % 16:
-        raise ValueError(f"{what}: {name} must be an fp32 ({rows}, {cols}) tensor on the operand's device, 16-byte aligned, row stride a multiple of 4")
-    return t
+_LN_ROWS = dict(dtypes=(torch.float32,), align=16, ld_multiple=4)        # _operand: fp32 rows the kernels read and write as 16-byte chunks
 
 
 def _ln_mask(mask, p, what, M, N, dev):
@@ -1134,30 +1113,30 @@ def _ln_width(N, what):
         raise ValueError(f"{what}: width {N} must be a multiple of 4 in [4, {L.LN_MAXN}]")
 
 
+def _ln_affine(gamma, beta, what, N, dev):
+    for t, name in ((gamma, "gamma"), (beta, "beta")):
+        if _vector(t, name, what, torch.float32, N, dev).data_ptr() % 16:
+            raise ValueError(f"{what}: {name} must be 16-byte aligned")
+
+
 def ln_act_fwd(z, gamma=None, beta=None, mask=None, p=0.0, eps=1e-5, *, y_out=None, mean_out=None, rstd_out=None):
     """(y, mean, rstd): Dropout(ReLU(LayerNorm(z))) of z fp32 (M, N) in one launch (mmvae_ln_act_fwd).  mask: the uint8 keep mask of
     ops.noise for dropout probability p, None = no dropout.  gamma = beta = None: no LayerNorm, y = relu(z) keep / (1 - p) and mean,
     rstd are None."""
     what = "ln_act_fwd"
-    z = _f32_matrix(z, "z", what)
-    M, N = z.shape
-    dev = z.device
+    (M, N), dev = _operand(z, "z", what, **_LN_ROWS).shape, z.device
     _ln_width(N, what)
-    z = _ln_operand(z, "z", what, M, N, dev)
     ln = gamma is not None
     if ln != (beta is not None):
         raise ValueError(f"{what}: gamma and beta come together")
-    y = _ln_operand(torch.empty(M, N, dtype=torch.float32, device=dev) if y_out is None else y_out, "y_out", what, M, N, dev)
+    y = torch.empty(M, N, dtype=torch.float32, device=dev) if y_out is None else _operand(y_out, "y_out", what, rows=M, cols=N, dev=dev, **_LN_ROWS)
     mean = rstd = None
     if ln:
-        for t, name in ((gamma, "gamma"), (beta, "beta")):
-            if _vector(t, name, what, torch.float32, N, dev).data_ptr() % 16:
-                raise ValueError(f"{what}: {name} must be 16-byte aligned")
-        mean = _vector(torch.empty(M, dtype=torch.float32, device=dev) if mean_out is None else mean_out, "mean_out", what, torch.float32, M, dev)
-        rstd = _vector(torch.empty(M, dtype=torch.float32, device=dev) if rstd_out is None else rstd_out, "rstd_out", what, torch.float32, M, dev)
+        _ln_affine(gamma, beta, what, N, dev)
+        mean = _out_vector(mean_out, "mean_out", what, torch.float32, M, dev)
+        rstd = _out_vector(rstd_out, "rstd_out", what, torch.float32, M, dev)
     mask, inv_keep = _ln_mask(mask, p, what, M, N, dev)
-    a = L.LnActFwdArgs(z.data_ptr(), _p(gamma), _p(beta), _p(mask), y.data_ptr(), _p(mean), _p(rstd), _ld(z), _ld(mask) if mask is not None else 0,
-                       _ld(y), M, N, int(ln), float(eps), inv_keep, 0)
+    a = L.LnActFwdArgs(z.data_ptr(), _p(gamma), _p(beta), _p(mask), y.data_ptr(), _p(mean), _p(rstd), _ld(z), _ld0(mask), _ld(y), M, N, int(ln), float(eps), inv_keep, 0)
     with stream_span(what, 9 * M * N):
         L.check(L.load().mmvae_ln_act_fwd(C.byref(a), _stream()), "mmvae_ln_act_fwd")
     return y, mean, rstd
@@ -1171,31 +1150,22 @@ def ln_act_bwd(dy, z, mean=None, rstd=None, gamma=None, beta=None, mask=None, p=
     """(dz, dgamma, dbeta): the backward of ln_act_fwd from dy = dL/dy and the forward's operands (mmvae_ln_act_bwd); dgamma and dbeta
     are written, bit-identical from run to run.  gamma = None: the form without LayerNorm, dz = dy keep / (1 - p) [z > 0]."""
     what = "ln_act_bwd"
-    z = _f32_matrix(z, "z", what)
-    M, N = z.shape
-    dev = z.device
+    (M, N), dev = _operand(z, "z", what, **_LN_ROWS).shape, z.device
     _ln_width(N, what)
-    z = _ln_operand(z, "z", what, M, N, dev)
-    dy = _ln_operand(dy, "dy", what, M, N, dev)
-    dz = _ln_operand(torch.empty(M, N, dtype=torch.float32, device=dev) if dz_out is None else dz_out, "dz_out", what, M, N, dev)
+    _operand(dy, "dy", what, rows=M, cols=N, dev=dev, **_LN_ROWS)
+    dz = torch.empty(M, N, dtype=torch.float32, device=dev) if dz_out is None else _operand(dz_out, "dz_out", what, rows=M, cols=N, dev=dev, **_LN_ROWS)
     ln = gamma is not None
     dgamma = dbeta = None
     if ln:
-        for t, name in ((gamma, "gamma"), (beta, "beta")):
-            if _vector(t, name, what, torch.float32, N, dev).data_ptr() % 16:
-                raise ValueError(f"{what}: {name} must be 16-byte aligned")
+        _ln_affine(gamma, beta, what, N, dev)
         _vector(mean, "mean", what, torch.float32, M, dev)
         _vector(rstd, "rstd", what, torch.float32, M, dev)
-        dgamma = _vector(torch.empty(N, dtype=torch.float32, device=dev) if dgamma_out is None else dgamma_out, "dgamma_out", what, torch.float32, N, dev)
-        dbeta = _vector(torch.empty(N, dtype=torch.float32, device=dev) if dbeta_out is None else dbeta_out, "dbeta_out", what, torch.float32, N, dev)
+        dgamma = _out_vector(dgamma_out, "dgamma_out", what, torch.float32, N, dev)
+        dbeta = _out_vector(dbeta_out, "dbeta_out", what, torch.float32, N, dev)
     mask, inv_keep = _ln_mask(mask, p, what, M, N, dev)
-    nbytes = ln_act_bwd_work_bytes(M, N, ln)
-    if work is None:
-        work = _workspace(nbytes, dev)
-    elif not isinstance(work, torch.Tensor) or work.dtype != torch.int64 or not work.is_contiguous() or work.numel() * 8 < nbytes or work.device != dev:
-        raise ValueError(f"{what}: work must be a contiguous int64 tensor of at least {nbytes} bytes on z's device")
+    work = _work(work, ln_act_bwd_work_bytes(M, N, ln), what, dev)
     a = L.LnActBwdArgs(dy.data_ptr(), z.data_ptr(), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(mask), dz.data_ptr(), _p(dgamma), _p(dbeta), _p(work),
-                       _ld(dy), _ld(z), _ld(mask) if mask is not None else 0, _ld(dz), work.numel() * 8 if work is not None else 0, M, N, int(ln),
+                       _ld(dy), _ld(z), _ld0(mask), _ld(dz), work.numel() * 8 if work is not None else 0, M, N, int(ln),
                        inv_keep)
     with stream_span(what, 13 * M * N):
         L.check(L.load().mmvae_ln_act_bwd(C.byref(a), _stream()), "mmvae_ln_act_bwd")
@@ -1209,9 +1179,8 @@ def wce_mean(logits, labels, class_weights=None, *, sums=None, grad=False, pred=
     pred int32 (M,): the argmax, the first maximum on ties; nll fp32 (M,): the unweighted row terms; confusion: an int32 (C, C) device
     tensor whose [label][prediction] counts are incremented.  Outputs that are not asked for are None."""
     what = "wce_mean"
-    x = _f32_matrix(logits, "logits", what)
-    M, Cn = x.shape
-    dev = x.device
+    x = _operand(logits, "logits", what, dtypes=(torch.float32,))
+    (M, Cn), dev = x.shape, x.device
     if not 2 <= Cn <= L.WCE_MAXC:
         raise ValueError(f"{what}: {Cn} classes outside [2, {L.WCE_MAXC}]")
     _vector(labels, "labels", what, torch.int64, M, dev)
@@ -1220,16 +1189,14 @@ def wce_mean(logits, labels, class_weights=None, *, sums=None, grad=False, pred=
     if sums is not None:
         _vector(sums, "sums", what, torch.float64, 3, dev)
     g = _out_view(grad_out, "grad_out", what, torch.float32, M, Cn, dev) if grad or grad_out is not None else None
-    pr = _vector(torch.empty(M, dtype=torch.int32, device=dev) if pred_out is None else pred_out, "pred_out", what, torch.int32, M, dev) \
-        if pred or pred_out is not None else None
+    pr = _out_vector(pred_out, "pred_out", what, torch.int32, M, dev) if pred or pred_out is not None else None
     nl = torch.empty(M, dtype=torch.float32, device=dev) if nll else None
     if confusion is not None and (not isinstance(confusion, torch.Tensor) or not confusion.is_cuda or confusion.dtype != torch.int32
                                   or tuple(confusion.shape) != (Cn, Cn) or not confusion.is_contiguous() or confusion.device != dev):
         raise ValueError(f"{what}: confusion must be a contiguous int32 ({Cn}, {Cn}) tensor on the operand's device")
     if sums is None and g is None and pr is None and nl is None and confusion is None:
         raise ValueError(f"{what}: no output asked for")
-    a = L.WceArgs(x.data_ptr(), labels.data_ptr(), _p(class_weights), _p(sums), _p(g), _p(pr), _p(nl), _p(confusion), _ld(x),
-                  _ld(g) if g is not None else 0, M, Cn)
+    a = L.WceArgs(x.data_ptr(), labels.data_ptr(), _p(class_weights), _p(sums), _p(g), _p(pr), _p(nl), _p(confusion), _ld(x), _ld0(g), M, Cn)
     with stream_span(what, 8 * M * Cn):
         L.check(L.load().mmvae_wce_mean(C.byref(a), _stream()), "mmvae_wce_mean")
     return g, pr, nl
