@@ -120,6 +120,48 @@ def row_blocks(M, row_bytes, log2_split):
     return blocks
 
 
+def tn_plan_rows(M, MT, ntiles, wg_target):
+    """plan_splits (csrc/common.h) for an automatic split -> (nsplit, rows per split)."""
+    nsplit = wg_target // ntiles
+    if nsplit >= 8:
+        nsplit &= ~7
+    nsplit = max(1, min(nsplit, -(-M // (4 * MT))))
+    rps = -(-(-(-M // nsplit)) // MT) * MT                  # ceil(M / nsplit), rounded up to whole MT-row steps
+    return -(-M // rps), rps
+
+
+def tn_wide_plan(M, N, K, pmode, q_kind, ldq=None, ldp=None, ldpy=None, q_aligned=True):
+    """What launch_tn_wide (csrc/gemm_tn_wide.hip) does with a bf16 P (pmode: BatchNorm-corrected from d and y, row strides ldp and
+    ldpy) and a Q of q_kind 'bf16' or 'f32' (row stride ldq, q_aligned: the first row on 16 bytes), given a slab that holds the
+    splits -> None (not taken) or (form, tile, ntiles, nsplit, rows per split); form 'dma' = LDS-DMA ring, 'reg' = register-staged,
+    tile = (256, 288) or (128, 448)."""
+    ldp = ops.ceil_to(N, 8) if ldp is None else ldp
+    ldpy = ldp if ldpy is None else ldpy
+    if M < 8192 or N < 128 or K < 256 or ldp % 8 or (pmode and (ldpy % 8 or N % 8)):
+        return None
+    if q_kind == "bf16":
+        ldq = ops.ceil_to(K, 8) if ldq is None else ldq
+        if ldq % 8 or pmode or M % 32 or N * K < 4 << 20:
+            return None
+        vec, tile = 8, (256, 288)
+    else:
+        ldq = K if ldq is None else ldq
+        vec = 4 if ldq % 4 == 0 and K % 4 == 0 and q_aligned else 2 if ldq % 2 == 0 and K % 2 == 0 else 1
+        if vec == 1 or (not pmode and (vec != 4 or M % 32)):
+            return None
+        padded = lambda nt, kt: -(-N // nt) * nt * (-(-K // kt) * kt)
+        tile = (128, 448) if N <= 128 or padded(128, 448) < padded(256, 288) else (256, 288)       # least padded output
+        if pmode and tile == (256, 288) and (vec != 4 or M % 32 or ldp != ldpy):
+            return None
+    ntiles = -(-K // tile[1]) * -(-N // tile[0])
+    if ntiles > (32 if pmode else 4096):
+        return None
+    nsplit, rps = tn_plan_rows(M, 32, ntiles, 256)
+    if pmode and nsplit < 2:
+        return None
+    return ("reg" if pmode and tile == (128, 448) else "dma"), tile, ntiles, nsplit, rps
+
+
 def within_blocks(got, ref, tol, blocks, what):
     """Block by block, so that a failure names the row block: an operand advanced by the wrong stride shows from the second block on."""
     for i, (r0, rows) in enumerate(blocks):

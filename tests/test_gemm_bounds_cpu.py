@@ -110,7 +110,7 @@ def fma32(a, b, c):
 
 
 def bn_bwd_p32(d, y, mean, rstd, sd, sdx, M, gamma, eval_mode, unzeroed=False):
-    """gemm_tn_wide.hip: tnw_coef + the four per-column constants + two fused multiply-adds, rounded to bf16."""
+    """gemm_src.h: BnBwdCols::column from the f64 sums (the four per-column constants) + bn_bwd_apply's two fused multiply-adds, rounded to bf16."""
     k0 = gamma * rstd
     k1 = np.zeros_like(k0) if eval_mode and not unzeroed else (np.asarray(sd, F64) / M).astype(F32)
     k2 = np.zeros_like(k0) if eval_mode else (np.asarray(sdx, F64) / M).astype(F32)

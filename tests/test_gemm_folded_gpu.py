@@ -320,29 +320,9 @@ def test_pro_finalize_refusals():
 # =============================================================================================
 # (b) the dW GEMM with mmvae_bn_bwd_finalize folded in
 # =============================================================================================
-def wide_plan(M, N, K, ldq, ldp, ldpy, q_aligned=True):
-    """What launch_tn_wide (gemm_tn_wide.hip) does with a BatchNorm-corrected bf16 P and an fp32 Q: -> (form, ntiles, nsplit), form
-    'A' = 256 x 288 LDS-DMA, 'B' = 128 x 448 register, None = not taken."""
-    if M < 8192 or N < 128 or K < 256 or ldp % 8 or ldpy % 8 or N % 8:
-        return None, 0, 0
-    vec = 4 if ldq % 4 == 0 and K % 4 == 0 and q_aligned else 2 if ldq % 2 == 0 and K % 2 == 0 else 1
-    if vec == 1:
-        return None, 0, 0
-    padded = lambda nt, kt: -(-N // nt) * nt * -(-K // kt) * kt
-    form = "B" if N <= 128 or padded(128, 448) < padded(256, 288) else "A"
-    if form == "A" and (vec != 4 or M % 32 or ldp != ldpy):
-        return None, 0, 0
-    nt, kt = (256, 288) if form == "A" else (128, 448)
-    ntiles = -(-K // kt) * -(-N // nt)
-    if ntiles > 32:
-        return None, 0, 0
-    nsplit = 256 // ntiles
-    if nsplit >= 8:
-        nsplit &= ~7
-    nsplit = max(1, min(nsplit, -(-M // 128)))
-    rps = -(-(-(-M // nsplit)) // 32) * 32                  # ceil(M / nsplit), rounded up to whole 32-row steps
-    nsplit = -(-M // rps)
-    return (form if nsplit >= 2 else None), ntiles, nsplit
+# launch_tn_wide's forms of a BatchNorm-corrected bf16 P and an fp32 Q, as gemm_gpu_util.tn_wide_plan names them (that module
+# imports this one, so the tests below import it when they run)
+WIDE_FORMS = {"A": ("dma", (256, 288)), "B": ("reg", (128, 448))}
 
 
 class BnDwCase:
@@ -395,8 +375,9 @@ BN_DW_CASES = [  # M, N, K, ldq, extra columns of d's row stride, eval mode, for
 @pytest.mark.parametrize("M,N,K,ldq,d_pad,eval_mode,form", BN_DW_CASES)
 def test_tn_bn_bwd_finalize_folded(M, N, K, ldq, d_pad, eval_mode, form):
     case = BnDwCase(M, N, K, ldq, d_pad, seed=M + N + K)
-    plan = wide_plan(M, N, K, ldq, N + d_pad, N, q_aligned=case.q.data_ptr() % 16 == 0)
-    assert plan[0] == form and plan[1] <= 32 and plan[2] >= 2 and plan[2] * N * K <= case.slab.numel(), plan
+    from gemm_gpu_util import tn_wide_plan
+    plan = tn_wide_plan(M, N, K, True, "f32", ldq, N + d_pad, N, q_aligned=case.q.data_ptr() % 16 == 0)
+    assert plan and plan[:2] == WIDE_FORMS[form] and plan[2] <= 32 and plan[3] >= 2 and plan[3] * N * K <= case.slab.numel(), plan
     tag = f"folded dW {form} M{M} N{N} K{K} {'eval' if eval_mode else 'train'}"
     a1, dg1, db1 = case.outputs()
     assert case.folded(a1, dg1, db1, eval_mode) == 0
@@ -426,7 +407,8 @@ def test_tn_bn_bwd_finalize_folded(M, N, K, ldq, d_pad, eval_mode, form):
 def test_tn_bn_bwd_finalize_folded_refusals():
     M, N, K = 8192, 128, 256
     case = BnDwCase(M, N, K, K, 0, seed=9)
-    assert wide_plan(M, N, K, K, N, N)[0] == "B"
+    from gemm_gpu_util import tn_wide_plan
+    assert tn_wide_plan(M, N, K, True, "f32", K, N, N)[:2] == WIDE_FORMS["B"]
     a, dg, db = case.outputs()
     watched = [a.buf, dg, db]
     before = [snapshot(x) for x in watched]

@@ -26,7 +26,7 @@ from mmvae import ops  # noqa: E402
 from mmvae.ops import PREC_BF16, PREC_F32  # noqa: E402
 import gemm_cases as GC  # noqa: E402
 from gemm_gpu_util import (NAN, NtCase, Out, a_operand, check_loss_epilogue, col_slice, dev, host, loss_target, prec_name, prep, row_blocks,  # noqa: E402
-                           status, tuning, within, within_blocks)
+                           status, tn_plan_rows, tn_wide_plan, tuning, within, within_blocks)
 from test_gemm_folded_gpu import Arena  # noqa: E402
 
 DEV = "cuda"
@@ -499,7 +499,8 @@ def test_tn_wide_tiles(M, N, K):
     p_, dp_ = G.operand_risk(E.bn_bwd_apply(_n(d[:, :N]), _n(y[:, :N]), mean.numpy(), rstd.numpy(), coef.numpy(), np.float64),
                              E.bn_bwd_apply_tol(_n(d[:, :N]), _n(y[:, :N]), mean.numpy(), rstd.numpy(), coef.numpy()), True)
     assert (dp_ > 0).mean() < 0.02
-    assert tnw_plan(M, N, K, True, False)[2] * N * K <= slab.numel()                 # launch_tn_wide takes it: >= 2 splits, all in the slab
+    plan = tn_wide_plan(M, N, K, True, "f32")
+    assert plan and plan[3] >= 2 and plan[3] * N * K <= slab.numel()                  # launch_tn_wide takes it: >= 2 splits, all in the slab
     for (dw, db), form in zip(res, ("wide tiles", "128 x 128")):       # both go through the slab
         _dw_within(dw, db, p_, _n(_round(Q, prec)), 0.0, False, f"test_tn_wide_tiles M{M} N{N} K{K} {form}", dp=dp_)
     tol = 3e-3 * np.sqrt(M) * float(ref.abs().max())                 # a bf16 rounding of a corrected P element may flip (see above)
@@ -611,7 +612,8 @@ def test_tn_wide_tiles_plain_p_fp32_q(M, N, K):
             res.append((dw.cpu().double(), db.cpu().double()))
     finally:
         lib.mmvae_set_tuning(4, 1)
-    assert tnw_plan(M, N, K, False, False)[2] * N * K <= slab.numel() and K % 4 == 0          # launch_tn_wide takes it: >= 2 splits, all in the slab
+    plan = tn_wide_plan(M, N, K, False, "f32")
+    assert plan and plan[3] >= 2 and plan[3] * N * K <= slab.numel() and K % 4 == 0   # launch_tn_wide takes it: >= 2 splits, all in the slab
     for (dw, db), form in zip(res, ("wide tiles", "128 x 128")):
         _dw_within(dw, db, _n(P), _n(_round(Q, PREC_BF16)), 0.0, False, f"test_tn_wide_tiles_plain_p_fp32_q M{M} N{N} K{K} {form}")
     for dw, db in res:
@@ -641,7 +643,8 @@ def test_tn_wide_tiles_bf16_operands_large_output():
             res.append((dw.cpu().double(), db.cpu().double()))
     finally:
         lib.mmvae_set_tuning(4, 1)
-    assert tnw_plan(M, N, K, False, True)[2] * N * K <= slab.numel()                 # launch_tn_wide takes it: >= 2 splits, all in the slab
+    plan = tn_wide_plan(M, N, K, False, "bf16")
+    assert plan and plan[3] >= 2 and plan[3] * N * K <= slab.numel()                  # launch_tn_wide takes it: >= 2 splits, all in the slab
     for (dw, db), form in zip(res, ("wide tiles", "128 x 128")):
         _dw_within(dw, db, _n(P[:, :N]), _n(Q[:, :K]), 0.0, False, f"test_tn_wide_tiles_bf16_operands_large_output {form}")
     for dw, db in res:
@@ -1228,35 +1231,6 @@ def test_ntp_prologue_per_element(masked):
 # ---------------------------------------------------------------------------------------------
 # the large-batch dW forms: two wave groups (gemm_tn.hip launch_tn) and wide tiles (gemm_tn_wide.hip launch_tn_wide)
 # ---------------------------------------------------------------------------------------------
-def tnw_plan(M, N, K, pmode, q_bf16):
-    """launch_tn_wide's tile shape and split (gemm_tn_wide.hip) -> (tile, ntiles, nsplit, rows per split); asserts that it takes the problem."""
-    assert M >= 8192 and N >= 128 and K >= 256
-    pad = lambda nt, kt: -(-N // nt) * nt * (-(-K // kt) * kt)
-    if q_bf16:
-        assert not pmode and M % 32 == 0 and N * K >= 4 << 20
-        cfg_a = True
-    else:
-        cfg_a = not (N <= 128 or pad(128, 448) < pad(256, 288))
-        assert pmode or M % 32 == 0
-        assert not (pmode and cfg_a) or M % 32 == 0
-    NT, KT = (256, 288) if cfg_a else (128, 448)
-    ntiles = -(-K // KT) * -(-N // NT)
-    assert ntiles <= (32 if pmode else 4096)
-    nsplit, rps = tn_plan_rows(M, 32, ntiles, 256)
-    assert nsplit >= 2
-    return (NT, KT), ntiles, nsplit, rps
-
-
-def tn_plan_rows(M, MT, ntiles, wg_target):
-    """plan_splits (csrc/common.h) for an automatic split -> (nsplit, rows per split)."""
-    nsplit = wg_target // ntiles
-    if nsplit >= 8:
-        nsplit &= ~7
-    nsplit = max(1, min(nsplit, -(-M // (4 * MT))))
-    rps = -(-(-(-M // nsplit)) // MT) * MT
-    return -(-M // rps), rps
-
-
 LARGE_DW = [("two wave groups", 8192, 512, 256), ("two wave groups", 8192, 782, 128), ("wide BN-corrected P x fp32 Q", 8192 + 96, 384, 300),
             ("wide plain P x fp32 Q", 8192, 512, 2000), ("wide bf16 x bf16", 8192, 4100, 1100)]
 
@@ -1279,7 +1253,9 @@ def test_tn_large_batch_forms_per_element(form, M, N, K):
         q_kind = "bf16"
     else:
         q_kind = "bf16" if form == "wide bf16 x bf16" else "f32"
-        _, ntiles, nsplit, rps = tnw_plan(M, N, K, pmode, q_kind == "bf16")
+        plan = tn_wide_plan(M, N, K, pmode, q_kind)
+        assert plan and plan[3] >= 2, "launch_tn_wide does not take it"
+        _, _, ntiles, nsplit, rps = plan
     assert nsplit > 1 and nsplit * N * K <= slab.numel()                         # tn_use_slab / launch_tn_wide: the partial tiles go to the slab
     tail = GC.dw_tail(M, rps)
     assert tail.start >= (nsplit - 1) * rps and 0 < M - tail.start <= 32
@@ -1320,3 +1296,62 @@ def test_tn_large_batch_forms_per_element(form, M, N, K):
     within(got, rw, tw, tag + " dW")
     within(host(a.views[1]), rb, tb, tag + " db")
     assert a.guards_unchanged(), "the gradient arena was written outside dw / db"
+
+
+SLAB_VIEWS = [("plain P x fp32 Q, slab on an odd float", 8192, 128, 256, 1, False, ("dma", (128, 448), 1, 64, 128)),
+              ("BN-corrected P x fp32 Q in 8-byte rows, slab on 8 bytes", 8192 + 96, 128, 258, 2, True, ("reg", (128, 448), 1, 65, 128))]
+
+
+@pytest.mark.parametrize("what,M,N,K,off,pmode,expect", SLAB_VIEWS, ids=[f"M{c[1]}-N{c[2]}-K{c[3]}-slab{c[4]}" for c in SLAB_VIEWS])
+def test_tn_wide_tiles_slab_view(what, M, N, K, off, pmode, expect):
+    """The wide-tile dW kernels choose the width of their slab stores from K AND the slab's alignment (tn_store_slab,
+    csrc/gemm_tn_tile.h): 16 bytes for K % 4 == 0 on a 16-byte aligned slab, 8 bytes for an even K on an 8-byte aligned one, single
+    floats otherwise.  The smallest problems launch_tn_wide takes, with the slab handed over as slab[1:] (4-byte aligned; K = 256) and
+    as slab[2:] (8-byte aligned; K = 258, whose fp32 rows of 8 bytes only the 128 x 448 register form takes): dW has the bits of the
+    same call on the 16-byte aligned slab (one fixed-order group of <= 128 splits either way), dW and db are inside dw_tol, and the
+    tail-only columns keep the rows of the plan's last 32-row step."""
+    prec = PREC_BF16
+    rng = np.random.default_rng(M + 3 * N + 7 * K)
+    ldq = K
+    plan = tn_wide_plan(M, N, K, pmode, "f32", ldq)
+    assert plan == expect, plan                                                  # the form taken and the split, by launch_tn_wide's own rules
+    _, _, ntiles, nsplit, rps = plan
+    elems = nsplit * N * K
+    assert nsplit <= 128 and (off != 1 or elems == 2097152)                      # one reduce group (TN_RG): a fixed-order sum
+    buf = torch.empty(elems + 4, device=DEV)
+    aligned, view = buf[:elems], buf[off:]
+    assert aligned.data_ptr() % 16 == 0 and view.data_ptr() % 16 == 4 * off and view.numel() >= elems
+    tail = GC.dw_tail(M, rps)
+    assert tail.start >= (nsplit - 1) * rps and 0 < M - tail.start <= 32
+    p, q = GC.dw_case(rng, M, N, K, tail)
+    pd, p_host = a_operand(p, prec, "bf16")
+    qd, q_host = a_operand(q, prec, "f32", ldq)
+    assert qd.stride(0) == ldq and qd.data_ptr() % 16 == 0 and (ldq * 4) % 16 == (0 if off == 1 else 8)
+    dp = pro = None
+    if pmode:
+        y = GC.rnd(rng, M, N, scale=2.0) + np.float32(0.3)
+        mean, rstd = GC.rnd(rng, N, scale=0.2), rng.uniform(0.5, 1.5, N).astype(np.float32)
+        coef = np.stack([rng.uniform(0.5, 1.5, N), rng.standard_normal(N) * 0.1, rng.standard_normal(N) * 0.1]).astype(np.float32)
+        yd, y_host = a_operand(y, prec, "bf16")
+        assert N % 8 == 0 and yd.stride(0) == pd.stride(0)
+        p_host, dp = G.operand_risk(E.bn_bwd_apply(p_host, y_host, mean, rstd, coef, np.float64), E.bn_bwd_apply_tol(p_host, y_host, mean, rstd, coef), True)
+        assert (dp > 0).mean() < 0.02
+        pro = ops.BnBwdApply(yd, dev(mean), dev(rstd), dev(coef).contiguous())
+    old_dw, old_db = GC.rnd(rng, N, K), GC.rnd(rng, N)
+    got = []
+    for slab in (aligned, view):
+        buf.fill_(NAN)                                                           # an element the kernel does not store reaches dW as NaN
+        a = Arena([(N, K), (N,)])
+        a.views[0].copy_(dev(old_dw)); a.views[1].copy_(dev(old_db))
+        with tuning(k4=1):
+            assert status(ops.gemm_tn, prec, pd, qd, a.views[0], a.views[1], N, K, slab=slab, **({"p_prologue": pro} if pro else {})) == 0
+            torch.cuda.synchronize()
+        assert a.guards_unchanged(), "the gradient arena was written outside dw / db"
+        got.append((a.views[0].clone(), host(a.views[1])))
+    assert torch.equal(got[0][0], got[1][0]), "dW depends on the slab's alignment"
+    rw, rb = G.dw_ref(p_host, q_host, old_dw, old_db)
+    tw, tb = G.dw_tol(p_host, q_host, old_dw, old_db, dp=dp)
+    tag = f"dW {what} M{M} N{N} K{K} ({nsplit} splits of {rps} rows)"
+    for (dw, db), name in zip(got, ("aligned slab", f"slab[{off}:]")):
+        within(host(dw), rw, tw, f"{tag} dW, {name}")
+        within(db, rb, tb, f"{tag} db, {name}")

@@ -79,15 +79,15 @@ template <> struct VLoad<bf16, 8> { static __device__ __forceinline__ void ld(co
 // One LDS-DMA wave-instruction (64 lanes x 16 bytes -> 1 KB of LDS at `lds_addr`, lane-linear) as inline assembly.  Through
 // __builtin_amdgcn_global_load_lds hipcc's wait-count pass treats later LDS reads as possibly reading the DMA's destination and, in
 // loops that wait with counted s_waitcnt vmcnt(N) of their own, drains every transfer in flight with an s_waitcnt vmcnt(0) right
-// behind the issue or in front of the next one -- a ring deeper than two slots then buys nothing (seen in the ISA of
-// gemm_tn_wide.hip and gemm_nt3.h).  Issued from assembly the transfers are invisible to that pass; the kernel's own counted waits
-// order them (vmcnt counts them in issue order like any other vector-memory operation).  m0 is written: kernels that use this
-// helper must not use the builtin form as well; the compiler's own value of m0 (it reserves the register and knows nothing of this
-// write: a clobber entry for it is only warned about) is saved and restored inside the statement.
+// behind the issue or in front of the next one -- the tile's whole trip from HBM then sits inside every step and a ring deeper than
+// two slots buys nothing (seen in the ISA of the rings of gemm_tn.hip and gemm_tn_wide.hip, the callers).  Issued from assembly the
+// transfers are invisible to that pass; the kernel's own counted waits order them (vmcnt counts them in issue order like any other
+// vector-memory operation).  PRECONDITION: m0 is written and not restored (the compiler reserves the register and knows nothing of
+// this write: a clobber entry for it is only warned about), so a kernel that uses this helper uses no builtin LDS-DMA and nothing
+// else that reads m0.  The form that saves and restores m0 around the transfer (two more scalar moves) was measured in both rings
+// and left the parent's spread on the two-wave-group kernels (profiles/tn_single_source_bench.json).
 __device__ __forceinline__ void lds_dma16(const void* g, unsigned lds_addr) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(lds_addr), "v"(g) : "memory");
+    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" :: "s"(lds_addr), "v"(g) : "memory");
 }
 __device__ __forceinline__ unsigned lds_addr_of(const void* p) {
     return (unsigned)(uintptr_t)(__attribute__((address_space(3))) const void*)p;

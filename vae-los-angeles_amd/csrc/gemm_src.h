@@ -202,7 +202,42 @@ struct SrcBnReluDrop {
 // P = c0 * (d - c1 - xhat * c2), xhat = (y - mean) * rstd: the BatchNorm-backward correction (mmvae_bn_bwd_apply) applied on
 // the operand load of the dW GEMM.  For a FIRST layer nothing else consumes dL/dy, so the element-wise pass over d (read d, y,
 // write d: 3 x 67 MB on the critical path of the step) disappears; d stays the raw epilogue output of the dX contraction.
-// Per-column constants of the workgroup's 128-column tile sit in LDS (aux: 5 x 128 floats, index = column & 127).
+// P = c0 d - ((y - mean) (c0 c2 rstd) + c0 c1): per element one subtraction and two fused multiply-adds on four per-column constants
+// (the difference y - mean is still formed first: no cancellation).  Every dW kernel that applies the correction (SrcBnBwdApply below,
+// both wide-tile kernels of gemm_tn_wide.hip) forms the constants and the element here, in this order of operations.
+// The constants are taken by reference and the operands as stored, so that a caller whose constants sit in LDS reads and converts
+// each at its use (read into a struct up front, the register-staged kernels needed 1-2 VGPRs more).
+template <typename T>
+__device__ __forceinline__ float bn_bwd_apply(T d, T y, const float& mean, const float& c0, const float& c2r, const float& c01) {
+    const float t = fmaf(to_f32(y) - mean, c2r, c01);
+    return fmaf(c0, to_f32(d), -t);
+}
+struct BnBwdConst {
+    float mean, c0, c2r, c01;          // mean, c0, c0 c2 rstd, c0 c1
+    // as four rows of `stride` floats: bn_bwd_apply(d, y, p[0], p[stride], p[2 * stride], p[3 * stride]), p = aux + i
+    __device__ __forceinline__ void store(float* aux, int stride, int i) const { aux[i] = mean; aux[stride + i] = c0; aux[2 * stride + i] = c2r; aux[3 * stride + i] = c01; }
+};
+// Where the constants of the N columns come from: coef = mmvae_bn_bwd_finalize's rows [3][N] (c0, c1, c2), or, with coef == nullptr,
+// that finalisation folded in: c0 = gamma rstd, c1 / c2 = the f64 column sums over the M batch rows (0 in eval mode).
+struct BnBwdCols {
+    const float* mean; const float* rstd; const float* coef; int N;
+    const double* sum_d = nullptr; const double* sum_dx = nullptr; const float* gamma = nullptr; int eval_mode = 0, M = 0;
+    // ok = false (a column past N): all zeros, so P is 0 there
+    __device__ __forceinline__ BnBwdConst column(int col, bool ok) const {
+        if (!ok) return {0.f, 0.f, 0.f, 0.f};
+        const float mu = mean[col], rs = rstd[col];         // requested ahead of the branch: one round trip with what it loads
+        float c0, c1, c2;
+        if (coef) { c0 = coef[col]; c1 = coef[N + col]; c2 = coef[2 * N + col]; }
+        else {
+            c0 = gamma[col] * rs;
+            c1 = eval_mode ? 0.f : (float)(sum_d[col] / M);
+            c2 = eval_mode ? 0.f : (float)(sum_dx[col] / M);
+        }
+        return {mu, c0, c0 * c2 * rs, c0 * c1};
+    }
+};
+
+// Per-column constants of the workgroup's 128-column tile sit in LDS (aux: 4 x 128 floats, index = column & 127).
 template <typename CT>
 struct SrcBnBwdApply {
     static constexpr int EPC = Mma<CT>::EPC;
@@ -212,15 +247,7 @@ struct SrcBnBwdApply {
     const float* mean; const float* rstd; const float* coef;          // coef: [3][K]
     struct Raw { RawVec<CT, EPC> d, y; };
     __device__ __forceinline__ void init(float* aux, int tid, int col0) const {
-        if (tid < TILE) {
-            const int c = col0 + tid;
-            const bool ok = c < K;
-            // P = c0 (d - c1 - (y - mean) rstd c2) = c0 d - ((y - mean) (c0 c2 rstd) + c0 c1): per element one subtraction and two
-            // fused multiply-adds on four per-column constants (the difference y - mean is still formed first: no cancellation)
-            const float c0 = ok ? coef[c] : 0.f;
-            aux[tid] = ok ? mean[c] : 0.f; aux[TILE + tid] = c0;
-            aux[2 * TILE + tid] = ok ? c0 * coef[2 * K + c] * rstd[c] : 0.f; aux[3 * TILE + tid] = ok ? c0 * coef[K + c] : 0.f;
-        }
+        if (tid < TILE) BnBwdCols{mean, rstd, coef, K}.column(col0 + tid, col0 + tid < K).store(aux, TILE, tid);
     }
     __device__ __forceinline__ void fetch(Raw& r, int row, int k) const {          // K % EPC == 0 (hidden widths), rows padded
         const unsigned rc = (unsigned)min(row, M - 1), kc = (unsigned)min(k, K - EPC);
@@ -240,8 +267,7 @@ struct SrcBnBwdApply {
         const int c = k & (TILE - 1);
 #pragma unroll
         for (int i = 0; i < EPC; ++i) {
-            const float t = fmaf(r.y.get(i) - aux[c + i], aux[2 * TILE + c + i], aux[3 * TILE + c + i]);
-            const float v = fmaf(aux[TILE + c + i], r.d.get(i), -t);
+            const float v = bn_bwd_apply(r.d.v[i], r.y.v[i], aux[c + i], aux[TILE + c + i], aux[2 * TILE + c + i], aux[3 * TILE + c + i]);
             o.set(i, ok ? v : 0.f);
         }
     }

@@ -4,9 +4,8 @@
 // (autograd mm + sum, reference caller optimize_hyperparameters.py:112; layers as listed in
 // gemm_nt.hip).  The reduction index is the batch row m, which is the SLOW index of both
 // operands in memory, so both MFMA operands need a transposed fragment:
-//   * bf16: tiles are staged row-major in LDS ([64 m][128 cols], 32-byte column chunks
-//     XOR-swizzled by row) and fragments are fetched with ds_read_b64_tr_b16, the gfx950
-//     hardware transpose read (two per 16x16x32 operand), bank-conflict free;
+//   * bf16: tiles are staged row-major in LDS ([64 m][128 cols]) in the swizzled layout of gemm_tn_tile.h
+//     and fragments are fetched with its hardware transpose read (two per 16x16x32 operand);
 //   * f32 : v_mfma_f32_16x16x4_f32 takes ONE element per lane, so plain ds_read_b32 of the
 //     row-major tile ([32 m][128 cols], 64-byte chunks swizzled by row parity) suffices.
 // Q may carry the BN-normalise + ReLU + Dropout prologue (it is then the previous layer's
@@ -15,24 +14,25 @@
 // batch step, steady-state loop without conditional fetches (see gemm_nt.hip for why).  tools/stamp.py tn
 // shows where a step goes: the global loads are never waited for; the registers -> LDS stage and the
 // transpose reads are what the MFMAs wait on.
-// The batch is split over `nsplit` workgroups per output tile; partial tiles are combined with
-// f32 global atomics (memory-side adds on gfx950; dW must be zeroed by the caller).  All tiles of
-// one batch split run on one XCD so that P / Q rows are fetched from HBM once and shared in L2.
+// The batch is split over `nsplit` workgroups per output tile (block mapping: tn_block, gemm_tn_tile.h); partial tiles go to the
+// slab workspace and are summed by the reduce kernels below, or, without a slab that holds them, are added with f32 global
+// atomics (memory-side adds on gfx950); dW and db are accumulated into.  This file: the 128 x 128 tile in its three forms
+// (register-staged, LDS-DMA, LDS-DMA in two wave groups), the grouped launch, the slab reduces and the entry points; the wide
+// tiles are gemm_tn_wide.hip's.  Out of this file on purpose: the tile geometry, the block mapping and the epilogues
+// (gemm_tn_tile.h), the LDS-DMA issue from assembly (common.h) and the BatchNorm-backward correction (gemm_src.h).
 #include "common.h"
 #include "mmvae_hip.h"
 #include "gemm_src.h"
+#include "gemm_tn_tile.h"
 
 namespace mm {
 
 constexpr int REDUCE_U = 16;      // loads a reduce thread keeps in flight (step at B = 65 536: 4 -> +8 us, 8 -> +2.5, 32 -> +8.5 against 16)
 
 template <typename CT> struct TnGeom;
-template <> struct TnGeom<bf16> {
+template <> struct TnGeom<bf16> {                   // one 256-byte panel of gemm_tn_tile.h's swizzled bf16 tile per row
     static constexpr int ROWB = 256, CPR = 16, MT = 64;
-    static __device__ __forceinline__ int f(int r) { return (r & 3) | (((r >> 3) & 1) << 2); }
-    // byte offset of 16-byte chunk ch of row r
-    static __device__ __forceinline__ int chunk_off(int r, int ch) { return r * ROWB + (((((ch >> 1) ^ f(r)) << 1) | (ch & 1)) << 4); }
-    static __device__ __forceinline__ int elem_off(int r, int col) { return r * ROWB + ((((col >> 4) ^ f(r))) << 5) + ((col & 15) << 1); }
+    static __device__ __forceinline__ int chunk_off(int r, int ch) { return tn_chunk_off(r, ch, ROWB); }      // byte offset of 16-byte chunk ch of row r
 };
 template <> struct TnGeom<float> {
     static constexpr int ROWB = 512, CPR = 32, MT = 32;
@@ -42,18 +42,7 @@ template <> struct TnGeom<float> {
 
 // transposed operand fragment for MFMA tile at columns [colbase, colbase+16), fragment step s
 __device__ __forceinline__ bf16x8 tn_frag(const unsigned char* tile, int colbase, int s, int lane, bf16*) {
-    typedef TnGeom<bf16> G;
-    const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
-    const int r = s * 32 + 8 * g + q;
-    const int c32 = colbase >> 4;
-    const int off0 = r * G::ROWB + ((c32 ^ G::f(r)) << 5) + (p << 3);
-    const int off1 = off0 + 4 * G::ROWB;            // rows +4: f() unchanged
-    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-    s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(tile + off0));
-    s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(tile + off1));
-    union { struct { s16x4 a, b; } s; bf16x8 v; } u;
-    u.s.a = lo; u.s.b = hi;
-    return u.v;
+    return tn_frag_bf16(tile, TnGeom<bf16>::ROWB, colbase, lane, s * 32);
 }
 __device__ __forceinline__ f32x4 tn_frag(const unsigned char* tile, int colbase, int s, int lane, float*) {
     typedef TnGeom<float> G;
@@ -89,10 +78,9 @@ void tn_body(const PSrc& ps, const QSrc& qs, float* __restrict__ dW, long ldw, f
     float* aux = (float*)(smem + 2 * BUF);                   // Q prologue: BN scale / shift
     float* auxp = aux + 1024;                                // P prologue: BN-backward constants of this tile's 128 columns
 
-    const int slot = L >> 3;
-    const int tile = slot % ntiles;
-    const int zz = (slot / ntiles) * 8 + (L & 7);
-    if (zz >= nsplit) return;
+    const TnBlock blk = tn_block(L, ntiles, nsplit, false);
+    const int tile = blk.tile, zz = blk.zz;
+    if (zz < 0) return;
     const int tn = tile / ntk, tk = tile % ntk;
     const int n0 = tn * TILE, k0 = tk * TILE;
     const int m_begin = zz * rows_per_split;
@@ -108,11 +96,8 @@ void tn_body(const PSrc& ps, const QSrc& qs, float* __restrict__ dW, long ldw, f
     if (QSrc::NEEDS_AUX || PSrc::NEEDS_AUX) __syncthreads();
 
     f32x4 acc[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float bsum[4] = {0.f, 0.f, 0.f, 0.f};
+    float bsum[4];
+    tn_zero(acc, bsum);
     const bool do_bias = (db != nullptr) && tk == 0 && wc == 0;     // wave-uniform
 
     // Same pipeline as the NT kernel (gemm_nt.hip): two global register sets, double-buffered LDS with ONE barrier per
@@ -162,12 +147,7 @@ void tn_body(const PSrc& ps, const QSrc& qs, float* __restrict__ dW, long ldw, f
         for (int a = 0; a < 4; ++a)
 #pragma unroll
             for (int b = 0; b < 4; ++b) Mma<CT>::mma(acc[a][b], bf[b], af[a]);     // swapped: a lane holds 4 consecutive k of one n (epilogue)
-        if (do_bias) {                      // column sums of P straight from the A fragments (VALU is idle here)
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-                for (int j = 0; j < Mma<CT>::EPC; ++j) bsum[a] += to_f32(af[a][j]);
-        }
+        if (do_bias) tn_db_add<CT>(bsum, af);
     };
     // one batch step: tile t is multiplied from LDS buffer `buf` while tile t+1 goes registers -> other buffer between the
     // two fragment steps and a later tile is fetched into the registers just freed; ONE barrier per step
@@ -210,7 +190,7 @@ void tn_body(const PSrc& ps, const QSrc& qs, float* __restrict__ dW, long ldw, f
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int p = wv + 4 * i, r = p * 4 + prow;
-                const int ch = (((ppos >> 1) ^ G::f(r)) << 1) | (ppos & 1);      // chunk whose swizzled position is ppos
+                const int ch = tn_swz(r, ppos);                  // chunk whose swizzled position is ppos
                 const unsigned rp_ = (unsigned)(m0 + r);
                 const bf16* gp = ps.p + (rp_ * (unsigned)ps.lda + (unsigned)min(n0 + ch * 8, ncap));
                 const bf16* gq = qs.p + (rp_ * (unsigned)qs.lda + (unsigned)min(k0 + ch * 8, kcap));
@@ -221,22 +201,19 @@ void tn_body(const PSrc& ps, const QSrc& qs, float* __restrict__ dW, long ldw, f
         if constexpr (NG == 2) {
             // One workgroup per CU: a ring of FOUR 64-row buffers, three steps under way while one is multiplied (with one step
             // ahead a lone workgroup had 32 KB in flight per CU and waited for the trip from HBM in every step).  Issued from
-            // inline assembly and waited for by counted vmcnt (see tnw_dma16 in gemm_tn_wide.hip for why not the builtin);
-            // the ring is unrolled so that every buffer is a compile-time offset.
-            const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) const void*)smem;
-            auto dma16 = [&](const void* g, unsigned lds_addr) {
-                asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" :: "s"(lds_addr), "v"(g) : "memory");     // nothing else here uses m0
-            };
+            // inline assembly and waited for by counted vmcnt (lds_dma16, common.h, says why not the builtin, which the two-buffer
+            // form above keeps: it waits with vmcnt(0) anyway); the ring is unrolled so that every buffer is a compile-time offset.
+            const unsigned lds0 = lds_addr_of(smem);
             auto issue4 = [&](int t, int slot) {
                 const unsigned sP = lds0 + slot * BUF, sQ = sP + G::MT * G::ROWB;
                 const int m0 = m_begin + t * G::MT;
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
                     const int p = wv + 8 * i, r = p * 4 + prow;
-                    const int ch = (((ppos >> 1) ^ G::f(r)) << 1) | (ppos & 1);
+                    const int ch = tn_swz(r, ppos);
                     const unsigned rp_ = (unsigned)(m0 + r);
-                    dma16(ps.p + (rp_ * (unsigned)ps.lda + (unsigned)min(n0 + ch * 8, ncap)), sP + p * 1024);
-                    dma16(qs.p + (rp_ * (unsigned)qs.lda + (unsigned)min(k0 + ch * 8, kcap)), sQ + p * 1024);
+                    lds_dma16(ps.p + (rp_ * (unsigned)ps.lda + (unsigned)min(n0 + ch * 8, ncap)), sP + p * 1024);
+                    lds_dma16(qs.p + (rp_ * (unsigned)qs.lda + (unsigned)min(k0 + ch * 8, kcap)), sQ + p * 1024);
                 }
             };
 #pragma unroll
@@ -331,42 +308,23 @@ void tn_body(const PSrc& ps, const QSrc& qs, float* __restrict__ dW, long ldw, f
         if (nt > 3) kstep(rp1, rq1, 3, 1, false, false, 0);
     }
 
-    // The MFMA operands are swapped (Q fragment as "A", P fragment as "B"), so accumulator (a, b) holds, in lane (li = lane & 15,
-    // lg = lane >> 4), dW[n = 16a + li][k = 16b + 4lg + j], j = 0..3: FOUR CONSECUTIVE k.  A split's partial tile goes to the slab
-    // as 16-byte stores (16 instead of 64 store instructions per lane: the scalar form cost 10-29 k cycles per workgroup, more
-    // than the 4 batch steps of a tiny-output GEMM).
-    const bool vec4 = slab != nullptr && (K & 3) == 0 && ((uintptr_t)slab & 15) == 0;
+    // this wave's 64 x 64 piece (accumulator layout: gemm_tn_tile.h): to the slab, or, without one, f32 atomics straight into dW
+    const int n_w = n0 + wr * 64, k_w = k0 + wc * 64;
+    if (slab) tn_store_slab(acc, slab, zz, n_w, k_w, N, K, lane);
+    else {
 #pragma unroll
-    for (int a = 0; a < 4; ++a) {
-        const int n = n0 + wr * 64 + a * 16 + (lane & 15);
-        if (n >= N) continue;
+        for (int a = 0; a < 4; ++a) {
+            const int n = n_w + a * 16 + (lane & 15);
+            if (n >= N) continue;
 #pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            const int k = k0 + wc * 64 + b * 16 + (lane >> 4) * 4;
-            if (k >= K) continue;
-            if (slab) {
-                // slab form: this split's partial tile is stored plainly into slab[zz] and summed by tn_reduce_kernel
-                float* sp = slab + ((long)zz * N + n) * K + k;
-                if (vec4 && k + 4 <= K) *(f32x4*)sp = acc[a][b];
-                else {
+            for (int b = 0; b < 4; ++b) {
+                const int k = k_w + b * 16 + (lane >> 4) * 4;
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) if (k + j < K) sp[j] = acc[a][b][j];
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) if (k + j < K) unsafeAtomicAdd(dW + (long)n * ldw + k + j, acc[a][b][j]);       // f32 atomics straight into dW
+                for (int j = 0; j < 4; ++j) if (k + j < K) unsafeAtomicAdd(dW + (long)n * ldw + k + j, acc[a][b][j]);
             }
         }
     }
-    if (do_bias) {
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            float v = bsum[a];
-            v += __shfl_xor(v, 16, 64); v += __shfl_xor(v, 32, 64);
-            const int n = n0 + wr * 64 + a * 16 + lane;
-            if (lane < 16 && n < N) unsafeAtomicAdd(db + n, v);
-        }
-    }
+    if (do_bias) tn_db_store(bsum, db, n_w, N, lane);
     STAMP_T(t_end);
     STAMP_ADD(5, 1); STAMP_ADD(6, t_end - t_begin); STAMP_ADD(9, t_end - t_last);
     STAMP_ONLY(if (tid == 0 && (blockIdx.x & 7) == 3) stamp_flush(stamps_tn, st_acc));
@@ -515,9 +473,8 @@ static TnPlan tn_plan(int M, int N, int K, int MT, int want, int wg_target = 512
 // one launch of a 128 x 128 tile form over the splits of plan p, then the slab reduce if the partial tiles went there
 template <auto Kernel, typename PSrc, typename QSrc>
 static int tn_go(const mmvae_gemm_tn_args* a, const PSrc& ps, const QSrc& qs, const TnPlan& p, int threads, int lds, hipStream_t st) {
-    const int grid = ((p.nsplit + 7) / 8) * 8 * p.ntiles;
     float* slab = tn_use_slab(a, p.nsplit) ? a->slab : nullptr;
-    const int rc = launch_lds<Kernel>(dim3(grid), dim3(threads), lds, st, ps, qs, a->dw, a->lddw, a->db, a->M, a->N, a->K,
+    const int rc = launch_lds<Kernel>(dim3(tn_grid(p.nsplit, p.ntiles)), dim3(threads), lds, st, ps, qs, a->dw, a->lddw, a->db, a->M, a->N, a->K,
                                       p.ntk, p.ntiles, p.nsplit, p.rps, slab);
     if (rc) return rc;
     return slab ? tn_reduce(a, p.nsplit, st) : 0;
@@ -631,7 +588,7 @@ static int launch_tn_group(const mmvae_gemm_tn_args* args, int n, hipStream_t st
         if ((long)r.nsplit * a->N * a->K > a->slab_elems) return MMVAE_ERR_ARG;
         r.M = a->M; r.N = a->N; r.K = a->K;
         r.dma = (r.combo == 1 && sizeof(CT) == 2 && tn_dma_ok(a->M, G::MT)) ? 1 : 0;
-        r.block0 = block; r.nblocks = ((r.nsplit + 7) / 8) * 8 * r.ntiles; block += r.nblocks;
+        r.block0 = block; r.nblocks = tn_grid(r.nsplit, r.ntiles); block += r.nblocks;
         r.dW = a->dw; r.ldw = a->lddw; r.db = a->db; r.slab = a->slab;
         r.p = a->p; r.ldp = a->ldp; r.q = a->q; r.ldq = a->ldq;
         r.pro_scale = a->pro_scale; r.pro_shift = a->pro_shift; r.pro_mask = a->pro_mask; r.ld_pro_mask = a->ld_pro_mask; r.pro_inv_keep = a->pro_inv_keep;

@@ -16,38 +16,33 @@
 // conversion -> LDS with one register set, double-buffered LDS, one barrier per step.  Plain bf16 x bf16 problems (the decoders'
 // gradients) were measured on these tiles too and stay with gemm_tn.hip's 128 x 128 LDS-DMA form (57-59 against 58 us, larger reduce).
 //
-// Layout: a batch step is 32 rows (one 16x16x32 MFMA reduction).  Tiles sit row-major in LDS, rows padded to a multiple of 256 bytes,
-// each 256-byte panel (128 columns) with gemm_tn.hip's XOR swizzle of its 32-byte units, so the transposed fragments come from
-// ds_read_b64_tr_b16 without bank conflicts.  Partial tiles of the batch splits go to the slab workspace and are summed by
+// Layout: a batch step is 32 rows (one 16x16x32 MFMA reduction).  bf16 tiles sit row-major in LDS in the swizzled layout of
+// gemm_tn_tile.h, rows padded to a multiple of 256 bytes (whole panels).  The block mapping and the epilogues are that header's too;
+// the BatchNorm-backward correction of P is gemm_src.h's (BnBwdCols / BnBwdConst, shared with the 128 x 128 kernel's operand
+// source), the LDS-DMA issue common.h's.  Partial tiles of the batch splits go to the slab workspace and are summed by
 // gemm_tn.hip's tn_reduce_kernel (fixed order up to 128 splits).
 #include "common.h"
 #include "mmvae_hip.h"
+#include "gemm_src.h"
+#include "gemm_tn_tile.h"
 
 namespace mm {
 
 struct TnwArgs {
     const bf16* p; unsigned ldp; const bf16* py; unsigned ldpy;
-    const float* mean; const float* rstd; const float* coef;
-    // coef == nullptr: mmvae_bn_bwd_finalize folded in -- the constants from the f64 sums, dgamma / dbeta by the (zz == 0, tk == 0) workgroups
-    const double* sum_d; const double* sum_dx; const float* gamma; float* dgamma; float* dbeta; int eval_mode;
+    // bn.coef == nullptr: mmvae_bn_bwd_finalize folded in -- the constants from the f64 sums, dgamma / dbeta by the (zz == 0, tk == 0) workgroups
+    BnBwdCols bn; float* dgamma; float* dbeta;
     const void* q; unsigned ldq;
     int M, N, K, ntk, ntiles, nsplit, rps, linear;
     float* slab; float* db;
 };
 
-// the three BatchNorm-backward constants of column `col` (mmvae_bn_bwd_finalize's coef rows), stored or formed from the sums
-__device__ __forceinline__ void tnw_coef(const TnwArgs& a, int col, float& k0, float& k1, float& k2) {
-    if (a.coef) { k0 = a.coef[col]; k1 = a.coef[a.N + col]; k2 = a.coef[2 * a.N + col]; return; }
-    k0 = a.gamma[col] * a.rstd[col];
-    k1 = a.eval_mode ? 0.f : (float)(a.sum_d[col] / a.M);
-    k2 = a.eval_mode ? 0.f : (float)(a.sum_dx[col] / a.M);
-}
 // dgamma += sum d * xhat, dbeta += sum d: once per column, by the first batch split of the first K tile of every N tile
 __device__ __forceinline__ void tnw_bn_grads(const TnwArgs& a, int n0, int nt, int zz, int tk, int tid, int nthreads) {
-    if (a.coef || zz != 0 || tk != 0) return;
+    if (a.bn.coef || zz != 0 || tk != 0) return;
     for (int c = tid; c < nt; c += nthreads) {
         const int col = n0 + c;
-        if (col < a.N) { a.dbeta[col] += (float)a.sum_d[col]; a.dgamma[col] += (float)a.sum_dx[col]; }
+        if (col < a.N) { a.dbeta[col] += (float)a.bn.sum_d[col]; a.dgamma[col] += (float)a.bn.sum_dx[col]; }
     }
 }
 
@@ -63,26 +58,6 @@ template <int WN_, int PA_, int WK_, int QB_> struct TnwCfg {
     static_assert(WN * WK == 8, "8 waves");
 };
 
-__device__ __forceinline__ int tnw_f(int r) { return (r & 3) | (((r >> 3) & 1) << 2); }
-// byte offset of 16-byte chunk ch (8 columns) of row r
-__device__ __forceinline__ int tnw_chunk_off(int r, int ch, int rowb) {
-    const int cin = ch & 15;
-    return r * rowb + (ch >> 4) * 256 + (((((cin >> 1) ^ tnw_f(r)) << 1) | (cin & 1)) << 4);
-}
-__device__ __forceinline__ bf16x8 tnw_frag(const unsigned char* tile, int rowb, int colbase, int lane) {
-    const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
-    const int r = 8 * g + q;
-    const int c32 = colbase >> 4;
-    const int off0 = r * rowb + (c32 >> 3) * 256 + (((c32 & 7) ^ tnw_f(r)) << 5) + (p << 3);
-    const int off1 = off0 + 4 * rowb;               // rows +4: the swizzle key is unchanged
-    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-    s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(tile + off0));
-    s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(tile + off1));
-    union { struct { s16x4 a, b; } s; bf16x8 v; } u;
-    u.s.a = lo; u.s.b = hi;
-    return u.v;
-}
-
 STAMP_BUFFER(tnw)          // cycles per batch step of gemm_tnw_dma_kernel (STAMP_TNW, common.h)
 
 template <typename QT, int VEC> struct TnwQRaw;
@@ -95,11 +70,9 @@ void gemm_tnw_kernel(const TnwArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float* aux = (float*)(smem + 2 * C::BUF);            // [4][NT]: mean, c0, c0 c2 rstd, c0 c1 of this tile's P columns
-    const int L = (int)blockIdx.x;
-    int tile, zz;
-    if (a.linear) { tile = L % a.ntiles; zz = L / a.ntiles; }     // fewer than 8 batch splits (very wide outputs): every XCD gets tiles
-    else { const int slot = L >> 3; tile = slot % a.ntiles; zz = (slot / a.ntiles) * 8 + (L & 7); }      // all tiles of a batch split on one XCD: P / Q rows shared in its L2
-    if (zz >= a.nsplit) return;
+    const TnBlock blk = tn_block((int)blockIdx.x, a.ntiles, a.nsplit, a.linear);
+    const int tile = blk.tile, zz = blk.zz;
+    if (zz < 0) return;
     const int tn = tile / a.ntk, tk = tile % a.ntk;
     const int n0 = tn * C::NT, k0 = tk * C::KT;
     const int M = a.M, N = a.N, K = a.K;
@@ -108,26 +81,14 @@ void gemm_tnw_kernel(const TnwArgs a)
     const int wn = wid / C::WK, wk = wid % C::WK;
 
     if constexpr (PMODE == 1) {
-        for (int c = tid; c < C::NT; c += C::THREADS) {
-            const int col = n0 + c;
-            const bool ok = col < N;
-            float c0 = 0.f, k1 = 0.f, k2 = 0.f;
-            if (ok) tnw_coef(a, col, c0, k1, k2);
-            aux[c] = ok ? a.mean[col] : 0.f; aux[C::NT + c] = c0;
-            aux[2 * C::NT + c] = ok ? c0 * k2 * a.rstd[col] : 0.f; aux[3 * C::NT + c] = ok ? c0 * k1 : 0.f;
-        }
+        for (int c = tid; c < C::NT; c += C::THREADS) a.bn.column(n0 + c, n0 + c < N).store(aux, C::NT, c);
         tnw_bn_grads(a, n0, C::NT, zz, tk, tid, C::THREADS);
         __syncthreads();
     }
 
     f32x4 acc[C::PA][C::QB];
-#pragma unroll
-    for (int i = 0; i < C::PA; ++i)
-#pragma unroll
-        for (int j = 0; j < C::QB; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     float bsum[C::PA];
-#pragma unroll
-    for (int i = 0; i < C::PA; ++i) bsum[i] = 0.f;
+    tn_zero(acc, bsum);
     const bool do_bias = a.db != nullptr && tk == 0 && wk == 0;     // wave-uniform
 
     struct PRaw { bf16x8 d, y; };
@@ -171,19 +132,17 @@ void gemm_tnw_kernel(const TnwArgs a)
             const bool ok = m_begin + t * C::MT + r < m_end;
             bf16x8 o;
             if constexpr (PMODE == 1) {
-                const float* ax = aux + ch * 8;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
-                    // P = c0 (d - c1 - (y - mean) rstd c2), as gemm_src.h's SrcBnBwdApply
-                    const float tt = fmaf((float)rp[i].y[e] - ax[e], ax[2 * C::NT + e], ax[3 * C::NT + e]);
-                    const float v = fmaf(ax[C::NT + e], (float)rp[i].d[e], -tt);
+                    const float* ax = aux + ch * 8;
+                    const float v = bn_bwd_apply(rp[i].d[e], rp[i].y[e], ax[e], ax[C::NT + e], ax[2 * C::NT + e], ax[3 * C::NT + e]);
                     o[e] = (bf16)(ok ? v : 0.f);
                 }
             } else {
                 const bf16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
                 o = ok ? rp[i].d : z;
             }
-            *(bf16x8*)(sP + tnw_chunk_off(r, ch, C::PROW)) = o;
+            *(bf16x8*)(sP + tn_chunk_off(r, ch, C::PROW)) = o;
         }
 #pragma unroll
         for (int i = 0; i < C::QI; ++i) {
@@ -194,7 +153,7 @@ void gemm_tnw_kernel(const TnwArgs a)
 #pragma unroll
                 for (int e = 0; e < 8; ++e) o[e] = (bf16)rq[i].v[e];
             }
-            *(bf16x8*)(sQ + tnw_chunk_off(r, ch, C::QROW)) = o;
+            *(bf16x8*)(sQ + tn_chunk_off(r, ch, C::QROW)) = o;
         }
     };
     auto compute = [&](int buf) {
@@ -202,19 +161,14 @@ void gemm_tnw_kernel(const TnwArgs a)
         const unsigned char* sQ = sP + C::MT * C::PROW;
         bf16x8 af[C::PA];
 #pragma unroll
-        for (int i = 0; i < C::PA; ++i) af[i] = tnw_frag(sP, C::PROW, (wn * C::PA + i) * 16, lane);
+        for (int i = 0; i < C::PA; ++i) af[i] = tn_frag_bf16(sP, C::PROW, (wn * C::PA + i) * 16, lane);
 #pragma unroll
         for (int j = 0; j < C::QB; ++j) {
-            const bf16x8 bq = tnw_frag(sQ, C::QROW, (wk * C::QB + j) * 16, lane);
+            const bf16x8 bq = tn_frag_bf16(sQ, C::QROW, (wk * C::QB + j) * 16, lane);
 #pragma unroll
             for (int i = 0; i < C::PA; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bq, af[i], acc[i][j], 0, 0, 0);   // swapped: a lane holds 4 consecutive k of one n
         }
-        if (do_bias) {
-#pragma unroll
-            for (int i = 0; i < C::PA; ++i)
-#pragma unroll
-                for (int e = 0; e < 8; ++e) bsum[i] += (float)af[i][e];
-        }
+        if (do_bias) tn_db_add<bf16>(bsum, af);
     };
 
     fetch(0);
@@ -228,37 +182,9 @@ void gemm_tnw_kernel(const TnwArgs a)
         __syncthreads();
     }
 
-    // accumulator (i, j), lane (li = lane & 15, lg = lane >> 4): dW[n = 16 i + li][k = 16 j + 4 lg + e], e = 0..3
-    float* sl = a.slab + (long)zz * N * K;
-    const bool v4 = (K & 3) == 0, v2 = (K & 1) == 0;
-#pragma unroll
-    for (int i = 0; i < C::PA; ++i) {
-        const int n = n0 + (wn * C::PA + i) * 16 + (lane & 15);
-        if (n >= N) continue;
-#pragma unroll
-        for (int j = 0; j < C::QB; ++j) {
-            const int k = k0 + (wk * C::QB + j) * 16 + (lane >> 4) * 4;
-            if (k >= K) continue;
-            float* sp = sl + (long)n * K + k;
-            if (v4) *(f32x4*)sp = acc[i][j];                     // K % 4 == 0: k + 4 <= K and 16-byte aligned
-            else if (v2) {
-                *(f32x2*)sp = f32x2{acc[i][j][0], acc[i][j][1]};
-                if (k + 2 < K) *(f32x2*)(sp + 2) = f32x2{acc[i][j][2], acc[i][j][3]};
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) if (k + e < K) sp[e] = acc[i][j][e];
-            }
-        }
-    }
-    if (do_bias) {
-#pragma unroll
-        for (int i = 0; i < C::PA; ++i) {
-            float v = bsum[i];
-            v += __shfl_xor(v, 16, 64); v += __shfl_xor(v, 32, 64);
-            const int n = n0 + (wn * C::PA + i) * 16 + lane;
-            if (lane < 16 && n < N) unsafeAtomicAdd(a.db + n, v);
-        }
-    }
+    const int n_w = n0 + wn * C::PA * 16, k_w = k0 + wk * C::QB * 16;         // this wave's piece of the tile
+    tn_store_slab(acc, a.slab, zz, n_w, k_w, N, K, lane);
+    if (do_bias) tn_db_store(bsum, a.db, n_w, N, lane);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -269,22 +195,12 @@ void gemm_tnw_kernel(const TnwArgs a)
 // converted in pairs.  No VGPR staging, no LDS write pass, no second copy of the tile: the register form above spent its step
 // waiting for the loads of its single register set (68 KB per step and CU at the ~25 B/clk a CU ingests) and then converting.
 // Swizzles are applied on the SOURCE side of the DMA (the LDS destination of a wave-instruction is lane-linear, 1 KB):
-//   bf16 tiles: gemm_tn.hip's XOR of the 32-byte units of a 256-byte panel;
+//   bf16 tiles: gemm_tn_tile.h's XOR of the 32-byte units of a 256-byte panel (tn_swz);
 //   fp32 Q tile [32][KT]: rows of KT / 16 units of 64 bytes, unit u of row r stored at (u + (r >> 3)) mod units -- the four row
 //   groups of a ds_read_b32 (16 lanes x 4 bytes each) then fall into four different 16-bank groups.
-// Needs: M % 32 == 0 (every step a full tile), fp32 Q rows 16-byte aligned with K % 4 == 0.
+// Needs: M % 32 == 0 (every step a full tile), fp32 Q rows 16-byte aligned with K % 4 == 0.  The transfers are issued from
+// assembly (lds_dma16, common.h) and waited for only by the counted s_waitcnt vmcnt(N) of the ring below.
 // ------------------------------------------------------------------------------------------
-// One LDS-DMA wave-instruction (64 lanes x 16 bytes -> 1 KB of LDS at `lds_addr`, lane-linear) as inline assembly.  The builtin
-// form makes hipcc's wait-count pass treat every later LDS read as possibly reading the DMA's destination: it puts
-// s_waitcnt vmcnt(0) in front of the first ds_read behind the issue, so the tile's whole trip from HBM sits inside each step
-// and a deeper ring buys nothing.  Issued from assembly the transfers are invisible to that pass and are waited for only by
-// the counted s_waitcnt vmcnt(N) of the ring below (vmcnt counts them in issue order like any other vector-memory op).
-__device__ __forceinline__ void tnw_dma16(const void* g, unsigned lds_addr) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" :: "s"(lds_addr), "v"(g) : "memory");      // m0 is written: nothing else in this kernel uses it
-}
-__device__ __forceinline__ unsigned tnw_lds_addr(const void* p) {
-    return (unsigned)(uintptr_t)(__attribute__((address_space(3))) const void*)p;
-}
 
 template <class C, int PMODE, typename QT, int NSTAGE>
 __global__ __launch_bounds__(512)
@@ -301,11 +217,9 @@ void gemm_tnw_dma_kernel(const TnwArgs a)
     typedef __attribute__((address_space(3))) void lds_void;
     typedef __attribute__((address_space(1))) const void gbl_void;
 
-    const int L = (int)blockIdx.x;
-    int tile, zz;
-    if (a.linear) { tile = L % a.ntiles; zz = L / a.ntiles; }
-    else { const int slot = L >> 3; tile = slot % a.ntiles; zz = (slot / a.ntiles) * 8 + (L & 7); }
-    if (zz >= a.nsplit) return;
+    const TnBlock blk = tn_block((int)blockIdx.x, a.ntiles, a.nsplit, a.linear);
+    const int tile = blk.tile, zz = blk.zz;
+    if (zz < 0) return;
     const int tn = tile / a.ntk, tk = tile % a.ntk;
     const int n0 = tn * C::NT, k0 = tk * C::KT;
     const int M = a.M, N = a.N, K = a.K;
@@ -316,16 +230,12 @@ void gemm_tnw_dma_kernel(const TnwArgs a)
     const int li = lane & 15, g = lane >> 4;
 
     // per-lane BatchNorm-backward constants of the PA fragment columns this wave multiplies
-    float cm[C::PA], c0[C::PA], c2[C::PA], c1[C::PA];
+    BnBwdConst bnc[C::PA];
     if constexpr (PMODE == 1) {
 #pragma unroll
         for (int i = 0; i < C::PA; ++i) {
             const int col = n0 + (wn * C::PA + i) * 16 + li;
-            const bool ok = col < N;
-            float k0_ = 0.f, k1_ = 0.f, k2_ = 0.f;
-            if (ok) tnw_coef(a, col, k0_, k1_, k2_);
-            cm[i] = ok ? a.mean[col] : 0.f; c0[i] = k0_;
-            c2[i] = ok ? k0_ * k2_ * a.rstd[col] : 0.f; c1[i] = ok ? k0_ * k1_ : 0.f;
+            bnc[i] = a.bn.column(col, col < N);
         }
         tnw_bn_grads(a, n0, C::NT, zz, tk, tid, C::THREADS);
     }
@@ -337,9 +247,8 @@ void gemm_tnw_dma_kernel(const TnwArgs a)
 #pragma unroll
     for (int i = 0; i < PI; ++i) {
         const int off = (wv + 8 * i) * 1024 + lane * 16;
-        const int r = off / C::PROW, s_ = (off % C::PROW) >> 4, pos = s_ & 15;
-        const int cin = (((pos >> 1) ^ tnw_f(r)) << 1) | (pos & 1);
-        psrc[i] = (unsigned)r * a.ldp + (unsigned)min(n0 + ((s_ >> 4) * 16 + cin) * 8, ncap);      // ldp == ldpy is checked by the host
+        const int r = off / C::PROW, s_ = (off % C::PROW) >> 4;
+        psrc[i] = (unsigned)r * a.ldp + (unsigned)min(n0 + ((s_ >> 4) * 16 + tn_swz(r, s_ & 15)) * 8, ncap);      // ldp == ldpy is checked by the host
     }
 #pragma unroll
     for (int i = 0; i < QI; ++i) {
@@ -349,11 +258,7 @@ void gemm_tnw_dma_kernel(const TnwArgs a)
             int u = (s_ >> 2) - ((r >> 3) & 3);
             u += u < 0 ? QUNITS : 0;
             qsrc[i] = (unsigned)r * a.ldq + (unsigned)min(k0 + (u * 4 + (s_ & 3)) * 4, K - 4);
-        } else {
-            const int pos = s_ & 15;
-            const int cin = (((pos >> 1) ^ tnw_f(r)) << 1) | (pos & 1);
-            qsrc[i] = (unsigned)r * a.ldq + (unsigned)min(k0 + ((s_ >> 4) * 16 + cin) * 8, ((K + 7) & ~7) - 8);
-        }
+        } else qsrc[i] = (unsigned)r * a.ldq + (unsigned)min(k0 + ((s_ >> 4) * 16 + tn_swz(r, s_ & 15)) * 8, ((K + 7) & ~7) - 8);
     }
     auto issue = [&](int t, int st) {
         unsigned char* sD = smem + st * STAGE;
@@ -366,25 +271,20 @@ void gemm_tnw_dma_kernel(const TnwArgs a)
         for (int i = 0; i < PI; ++i) {
             const int p = wv + 8 * i;
             if (PP % 8 == 0 || p < PP) {
-                tnw_dma16(gd + psrc[i], tnw_lds_addr(sD + p * 1024));
-                if constexpr (PMODE == 1) tnw_dma16(gy + psrc[i], tnw_lds_addr(sD + PBYTES + p * 1024));
+                lds_dma16(gd + psrc[i], lds_addr_of(sD + p * 1024));
+                if constexpr (PMODE == 1) lds_dma16(gy + psrc[i], lds_addr_of(sD + PBYTES + p * 1024));
             }
         }
 #pragma unroll
         for (int i = 0; i < QI; ++i) {
             const int p = wv + 8 * i;
-            if (QP % 8 == 0 || p < QP) tnw_dma16(gq + qsrc[i], tnw_lds_addr(sQ + p * 1024));
+            if (QP % 8 == 0 || p < QP) lds_dma16(gq + qsrc[i], lds_addr_of(sQ + p * 1024));
         }
     };
 
     f32x4 acc[C::PA][C::QB];
-#pragma unroll
-    for (int i = 0; i < C::PA; ++i)
-#pragma unroll
-        for (int j = 0; j < C::QB; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     float bsum[C::PA];
-#pragma unroll
-    for (int i = 0; i < C::PA; ++i) bsum[i] = 0.f;
+    tn_zero(acc, bsum);
     const bool do_bias = a.db != nullptr && tk == 0 && wk == 0;
     const int nt = (m_end - m_begin) / C::MT;
 
@@ -394,14 +294,11 @@ void gemm_tnw_dma_kernel(const TnwArgs a)
         bf16x8 af[C::PA];
 #pragma unroll
         for (int i = 0; i < C::PA; ++i) {
-            const bf16x8 d = tnw_frag(sD, C::PROW, (wn * C::PA + i) * 16, lane);
+            const bf16x8 d = tn_frag_bf16(sD, C::PROW, (wn * C::PA + i) * 16, lane);
             if constexpr (PMODE == 1) {
-                const bf16x8 y = tnw_frag(sD + PBYTES, C::PROW, (wn * C::PA + i) * 16, lane);
+                const bf16x8 y = tn_frag_bf16(sD + PBYTES, C::PROW, (wn * C::PA + i) * 16, lane);
 #pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float tt = fmaf((float)y[e] - cm[i], c2[i], c1[i]);        // as gemm_src.h's SrcBnBwdApply
-                    af[i][e] = (bf16)fmaf(c0[i], (float)d[e], -tt);
-                }
+                for (int e = 0; e < 8; ++e) af[i][e] = (bf16)bn_bwd_apply(d[e], y[e], bnc[i].mean, bnc[i].c0, bnc[i].c2r, bnc[i].c01);
             } else af[i] = d;
         }
 #pragma unroll
@@ -413,16 +310,11 @@ void gemm_tnw_dma_kernel(const TnwArgs a)
                 const unsigned char* base = sQ + (8 * g) * QROWB + u * 64 + li * 4;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) bq[e] = (bf16)(*(const float*)(base + e * QROWB));
-            } else bq = tnw_frag(sQ, QROWB, (wk * C::QB + j) * 16, lane);
+            } else bq = tn_frag_bf16(sQ, QROWB, (wk * C::QB + j) * 16, lane);
 #pragma unroll
             for (int i = 0; i < C::PA; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bq, af[i], acc[i][j], 0, 0, 0);
         }
-        if (do_bias) {
-#pragma unroll
-            for (int i = 0; i < C::PA; ++i)
-#pragma unroll
-                for (int e = 0; e < 8; ++e) bsum[i] += (float)af[i][e];
-        }
+        if (do_bias) tn_db_add<bf16>(bsum, af);
     };
 
     // NSTAGE-deep ring, NSTAGE - 1 steps of DMA ahead of the MFMAs: with two stages a step lasted as long as ONE tile's trip
@@ -462,56 +354,26 @@ void gemm_tnw_dma_kernel(const TnwArgs a)
     }
     STAMP_T(t_loop_end);
 
-    float* sl = a.slab + (long)zz * N * K;
-    const bool v4 = (K & 3) == 0, v2 = (K & 1) == 0;
-#pragma unroll
-    for (int i = 0; i < C::PA; ++i) {
-        const int n = n0 + (wn * C::PA + i) * 16 + li;
-        if (n >= N) continue;
-#pragma unroll
-        for (int j = 0; j < C::QB; ++j) {
-            const int k = k0 + (wk * C::QB + j) * 16 + g * 4;
-            if (k >= K) continue;
-            float* sp = sl + (long)n * K + k;
-            if (v4) *(f32x4*)sp = acc[i][j];
-            else if (v2) {
-                *(f32x2*)sp = f32x2{acc[i][j][0], acc[i][j][1]};
-                if (k + 2 < K) *(f32x2*)(sp + 2) = f32x2{acc[i][j][2], acc[i][j][3]};
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) if (k + e < K) sp[e] = acc[i][j][e];
-            }
-        }
-    }
-    if (do_bias) {
-#pragma unroll
-        for (int i = 0; i < C::PA; ++i) {
-            float v = bsum[i];
-            v += __shfl_xor(v, 16, 64); v += __shfl_xor(v, 32, 64);
-            const int n = n0 + (wn * C::PA + i) * 16 + lane;
-            if (lane < 16 && n < N) unsafeAtomicAdd(a.db + n, v);
-        }
-    }
+    const int n_w = n0 + wn * C::PA * 16, k_w = k0 + wk * C::QB * 16;         // this wave's piece of the tile
+    tn_store_slab(acc, a.slab, zz, n_w, k_w, N, K, lane);
+    if (do_bias) tn_db_store(bsum, a.db, n_w, N, lane);
     STAMP_T(t_end);
     STAMP_ADD(4, nt); STAMP_ADD(5, 1); STAMP_ADD(6, t_end - t_begin); STAMP_ADD(7, t_end - t_loop_end);
     STAMP_ONLY(if (tid == 0 && (blockIdx.x & 7) == 3) stamp_flush(stamps_tnw, st_acc));
 }
 
-template <class C, int PMODE, typename QT, int NSTAGE>
-static int tnw_dma_launch(TnwArgs& w, hipStream_t st) {
-    constexpr bool QF = sizeof(QT) == 4;
-    constexpr int LDS = NSTAGE * (C::MT * C::PROW * (PMODE ? 2 : 1) + C::MT * (QF ? C::KT * 4 : C::QROW));
-    const int grid = w.linear ? w.nsplit * w.ntiles : ((w.nsplit + 7) / 8) * 8 * w.ntiles;
-    return launch_lds<gemm_tnw_dma_kernel<C, PMODE, QT, NSTAGE>>(dim3(grid), dim3(512), LDS, st, w);
-}
-
 typedef TnwCfg<4, 4, 2, 9> CfgA;        // 256 x 288
 typedef TnwCfg<2, 4, 4, 7> CfgB;        // 128 x 448
 
-template <class C, int PMODE, typename QT, int QVEC>
-static int tnw_launch(TnwArgs& w, hipStream_t st) {
-    const int grid = w.linear ? w.nsplit * w.ntiles : ((w.nsplit + 7) / 8) * 8 * w.ntiles;
-    return launch_lds<gemm_tnw_kernel<C, PMODE, QT, QVEC>>(dim3(grid), dim3(512), C::LDS, st, w);
+// one launcher for both forms: the kernel and its dynamic LDS
+template <auto Kernel>
+static int tnw_go(const TnwArgs& w, int lds, hipStream_t st) {
+    return launch_lds<Kernel>(dim3(tn_grid(w.nsplit, w.ntiles, w.linear)), dim3(512), lds, st, w);
+}
+template <class C, int PMODE, typename QT, int NSTAGE>
+static int tnw_dma_launch(const TnwArgs& w, hipStream_t st) {
+    constexpr int LDS = NSTAGE * (C::MT * C::PROW * (PMODE ? 2 : 1) + C::MT * (sizeof(QT) == 4 ? C::KT * 4 : C::QROW));      // NSTAGE stages of the kernel's STAGE bytes
+    return tnw_go<gemm_tnw_dma_kernel<C, PMODE, QT, NSTAGE>>(w, LDS, st);
 }
 
 // Returns 0 after launching the GEMM (the caller then runs the slab reduce over *nsplit_out splits), > 0 on a launch error,
@@ -553,8 +415,8 @@ int launch_tn_wide(const mmvae_gemm_tn_args* a, hipStream_t st, int* nsplit_out)
     if (pmode && nsplit < 2) return NA;
     w.nsplit = nsplit; w.rps = rps; w.linear = nsplit < 8 ? 1 : 0;
     w.p = (const bf16*)a->p; w.ldp = (unsigned)a->ldp; w.py = (const bf16*)a->p_y; w.ldpy = (unsigned)a->ld_py;
-    w.mean = a->p_mean; w.rstd = a->p_rstd; w.coef = a->p_coef;
-    w.sum_d = a->p_sum_d; w.sum_dx = a->p_sum_dx; w.gamma = a->p_gamma; w.dgamma = a->p_dgamma; w.dbeta = a->p_dbeta; w.eval_mode = a->p_eval_mode;
+    w.bn = BnBwdCols{a->p_mean, a->p_rstd, a->p_coef, a->N, a->p_sum_d, a->p_sum_dx, a->p_gamma, a->p_eval_mode, a->M};
+    w.dgamma = a->p_dgamma; w.dbeta = a->p_dbeta;
     w.q = a->q; w.ldq = (unsigned)a->ldq; w.M = a->M; w.N = a->N; w.K = a->K; w.slab = a->slab; w.db = a->db;
     *nsplit_out = nsplit;
     if (qkind == 0) return tnw_dma_launch<CfgA, 0, bf16, 3>(w, st);
@@ -562,7 +424,7 @@ int launch_tn_wide(const mmvae_gemm_tn_args* a, hipStream_t st, int* nsplit_out)
     if (cfg == 0) return tnw_dma_launch<CfgA, 1, float, 2>(w, st);
     // 128 x 448 tiles (EncoderA.L0: K = 782, fp32 rows only 8-byte aligned -- 16-byte LDS-DMA pieces from such rows delivered wrong
     // data): the register form
-    return qkind == 4 ? tnw_launch<CfgB, 1, float, 4>(w, st) : tnw_launch<CfgB, 1, float, 2>(w, st);
+    return qkind == 4 ? tnw_go<gemm_tnw_kernel<CfgB, 1, float, 4>>(w, CfgB::LDS, st) : tnw_go<gemm_tnw_kernel<CfgB, 1, float, 2>>(w, CfgB::LDS, st);
 }
 
 }  // namespace mm
