@@ -524,6 +524,37 @@ int mmvae_knn_splits(int32_t Mq, int32_t Nt, int32_t* splits, int32_t* rows_per_
 int mmvae_knn_search_l1(const mmvae_knn_args* args, void* stream);
 int mmvae_knn_l1_work_bytes(int32_t Mq, int32_t Nt, int32_t k, int64_t* bytes);
 
+/* The grouped search: either search above with a say in which candidates a query may see, for k-fold cross-validation on ONE search
+ * over the whole matrix (every row searches the rows outside its own fold; vae_cross_modality_cv.py:300-340 fits per fold and k) and
+ * for the site-conditioned baseline in one launch (src/models/conditioned_knn.py:18-93 fits per site).
+ *   base: operands, outputs and work exactly as mmvae_knn_search (metric 0, euclidean) / mmvae_knn_search_l1 (metric 1, manhattan).
+ *   q_same [Mq], t_same [Nt] and q_differ [Mq], t_differ [Nt]: int32 codes (any value, negative included); a pair is given or NULL.
+ * Candidate j is admitted for query i iff (the same pair is NULL or t_same[j] == q_same[i]) and (the differ pair is NULL or
+ * t_differ[j] != q_differ[i]).  Among the admitted candidates everything is what the ungrouped entry of that metric specifies: the key
+ * arithmetic, the order (key, j) ascending with the smaller index first among equal keys, NaN after +inf, dist2 (euclidean: squared;
+ * manhattan: the distance itself), shift (NULL for manhattan), dtypes, limits (1 <= k <= min(Nt, MMVAE_KNN_MAXK)), the decomposition
+ * of mmvae_knn_splits and bit-reproducibility.  Since a pair's key depends only on the two rows' values and the shift, the result
+ * equals, bit for bit, the ungrouped search over the admitted subset with the indices mapped back.
+ * Short lists: a query with c < k admitted candidates (c = 0 included) gets c ordered entries; positions c .. k-1 hold idx -1 and
+ * distance +inf.  Nothing outside idx [Mq][k] / dist2 [Mq][k] is written.
+ * Tile skip: one small launch first writes the min and max of t_same and of t_differ per tile of 128 candidate rows into work; a
+ * workgroup reduces the same over its 128 query rows and walks only tiles that can hold an admitted pair: a tile is skipped iff
+ * (same given and the two code ranges do not meet) or (differ given and tile and block each carry one code, the same one).  The
+ * per-pair predicate holds in every tile that is walked, so results never depend on the skip; with rows sorted by group a same-group
+ * search does sum n_g^2 work instead of N^2.
+ * work: always needed, 8-byte aligned, at least mmvae_knn_group_work_bytes(Mq, Nt, k, metric) = the ungrouped size of that metric +
+ * 16 ceil(Nt / 128) bytes; the tile codes lie behind the ungrouped layout.
+ * MMVAE_ERR_ARG (nothing enqueued): everything the ungrouped entry refuses, a null struct, both pairs NULL (use the plain entry), half
+ * a pair, a code pointer not 4-byte aligned, metric outside {0, 1}, work_bytes below mmvae_knn_group_work_bytes. */
+typedef struct {
+    mmvae_knn_args base;
+    const int32_t* q_same;   const int32_t* t_same;
+    const int32_t* q_differ; const int32_t* t_differ;
+    int32_t metric;
+} mmvae_knn_group_args;
+int mmvae_knn_search_grouped(const mmvae_knn_group_args* args, void* stream);
+int mmvae_knn_group_work_bytes(int32_t Mq, int32_t Nt, int32_t k, int32_t metric, int64_t* bytes);
+
 /* Uniform k-NN regression from the indices of mmvae_knn_search:  out[i][:] = (sum_{n<k} y[idx[i][n]][:]) / k, in fp32, summed in
  * ascending n (deterministic; what KNeighborsRegressor.predict with uniform weights computes, conditioned_knn.py:84-91).
  * y [Ny][Fy]: MMVAE_F32 or MMVAE_BF16 rows (ld_y >= Fy), out [Mq][Fy] fp32 (ld_out >= Fy), idx [Mq][k] int32 (ld_idx >= k); indices

@@ -62,18 +62,27 @@ __device__ __forceinline__ void knn_insert(unsigned long long* L, bool pass, uns
 // the high word of the row's k-th entry; a wave-wide vote skips the insert when no lane passed.  The two waves that share query rows
 // (wc = 0, 1) take turns, one workgroup barrier each.  sL: [KNN_BM][kp] lists.  The euclidean kernel carries the same block written out,
 // with its key |t|^2 - 2 q.t in place of the accumulator (knn.hip says why).
-template <int S>
+// G (the grouped search): candidate j is admitted for a row iff (no same pair or ts[j] == the row's same code) and (no differ pair or
+// td[j] != the row's differ code); a tile's candidate codes are loaded once, next to jlo.
+// ts, td [Nt]: the candidates' codes in global memory, NULL for a pair that is not given; q_same, q_differ [KNN_BM]: the block's in LDS.
+template <int S, bool G = false>
 __device__ __forceinline__ void knn_select_tile(const f32x4 (&acc)[4][4], unsigned long long* sL, const RtMap& m, int tile, int Nt, int nr,
-                                                int k, int kp) {
+                                                int k, int kp, [[maybe_unused]] const int* ts = nullptr, [[maybe_unused]] const int* td = nullptr,
+                                                [[maybe_unused]] const int* q_same = nullptr, [[maybe_unused]] const int* q_differ = nullptr) {
     for (int phase = 0; phase < 2; ++phase) {
         if (m.wc == phase) {
             bool jok[4];
             unsigned jlo[4];
+            [[maybe_unused]] int tsv[4], tdv[4];
 #pragma unroll
             for (int ni = 0; ni < 4; ++ni) {
                 const long j = (long)tile * KNN_BN + m.acc_col(m.wc * 64, ni);
                 jok[ni] = j < Nt;
                 jlo[ni] = (unsigned)j;
+                if constexpr (G) {
+                    tsv[ni] = (ts && jok[ni]) ? ts[j] : 0;
+                    tdv[ni] = (td && jok[ni]) ? td[j] : 0;
+                }
             }
 #pragma unroll
             for (int mi = 0; mi < 4; ++mi)
@@ -82,10 +91,13 @@ __device__ __forceinline__ void knn_select_tile(const f32x4 (&acc)[4][4], unsign
                     const int row = m.acc_row(m.wr * 64, mi, r);
                     unsigned long long* L = sL + row * kp;
                     const unsigned thr = (unsigned)(L[k - 1] >> 32);
+                    [[maybe_unused]] int qsv = 0, qdv = 0;
+                    if constexpr (G) { qsv = q_same[row]; qdv = q_differ[row]; }
 #pragma unroll
                     for (int ni = 0; ni < 4; ++ni) {
                         const unsigned u = knn_order(acc[mi][ni][r]);
-                        const bool pass = jok[ni] && row < nr && u <= thr;
+                        bool pass = jok[ni] && row < nr && u <= thr;
+                        if constexpr (G) pass = pass && (!ts || tsv[ni] == qsv) && (!td || tdv[ni] != qdv);
                         if (__any(pass)) knn_insert<S>(L, pass, ((unsigned long long)u << 32) | jlo[ni], m.lane, k);
                     }
                 }

@@ -151,6 +151,10 @@ class KnnArgs(C.Structure):
                 ("Mq", i32), ("Nt", i32), ("F", i32), ("k", i32), ("q_dtype", i32), ("t_dtype", i32)]
 
 
+class KnnGroupArgs(C.Structure):
+    _fields_ = [("base", KnnArgs), ("q_same", vp), ("t_same", vp), ("q_differ", vp), ("t_differ", vp), ("metric", i32)]
+
+
 class SilhouetteArgs(C.Structure):
     _fields_ = [("x", vp), ("shift", vp), ("order", vp), ("class_start", vp), ("s", vp), ("intra", vp), ("inter", vp), ("work", vp),
                 ("ld_x", i64), ("work_bytes", i64),
@@ -243,6 +247,8 @@ _SIGNATURES = {
     "mmvae_knn_search_l1": [C.POINTER(KnnArgs), vp],
     "mmvae_knn_l1_work_bytes": [i32, i32, i32, C.POINTER(i64)],
     "mmvae_knn_weighted_rows": [vp, i64, vp, i64, i32, vp, i32, i64, vp, i64, i32, i32, i32, i32, vp],
+    "mmvae_knn_search_grouped": [C.POINTER(KnnGroupArgs), vp],
+    "mmvae_knn_group_work_bytes": [i32, i32, i32, i32, C.POINTER(i64)],
     "mmvae_silhouette_samples": [C.POINTER(SilhouetteArgs), vp],
     "mmvae_silhouette_work_bytes": [i32, i32, i32, C.POINTER(i64)],
     "mmvae_silhouette_splits": [i32, i32, i32, C.POINTER(i32)],

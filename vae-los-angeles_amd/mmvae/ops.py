@@ -883,6 +883,58 @@ def knn_search_l1(q, t, k, dist=True, *, idx_out=None, dist_out=None):
     return _knn_search("knn_search_l1", knn_l1_work_bytes, "valu", q, t, k, None, idx_out, dist_out if dist else False, "dist_out")
 
 
+_KNN_METRICS = {"euclidean": 0, "manhattan": 1}
+
+
+def knn_group_work_bytes(Mq, Nt, k, metric="euclidean"):
+    """Workspace bytes of knn_search_grouped (mmvae_knn_group_work_bytes): the ungrouped size of the metric + 16 per tile of 128 rows."""
+    if metric not in _KNN_METRICS:
+        raise ValueError(f"knn_group_work_bytes: metric must be one of {sorted(_KNN_METRICS)}, got {metric!r}")
+    return _plan("mmvae_knn_group_work_bytes", Mq, Nt, k, _KNN_METRICS[metric], outs=(C.c_int64,))
+
+
+def knn_search_grouped(q, t, k, *, same=None, differ=None, metric="euclidean", shift=None, dist=True, idx_out=None, dist_out=None):
+    """knn_search (metric "euclidean": squared distances) or knn_search_l1 ("manhattan": the distances themselves) among the candidates
+    a query may see (mmvae_knn_search_grouped): same = (q_codes, t_codes) admits the candidates whose code equals the query's, differ =
+    (q_codes, t_codes) those whose code differs; both may be given, one must be.  Codes are int32 device vectors of Mq and Nt entries.
+    Among the admitted candidates the result is, bit for bit, that of the plain search over them.  A query with c < k admitted candidates
+    gets c entries and then idx -1 / distance +inf.  Rows sorted by the `same` code let whole tiles be skipped.  There is no CPU fallback."""
+    what = "knn_search_grouped"
+    if metric not in _KNN_METRICS:
+        raise ValueError(f"{what}: metric must be one of {sorted(_KNN_METRICS)}, got {metric!r}")
+    if same is None and differ is None:
+        raise ValueError(f"{what}: give same=(q_codes, t_codes), differ=(q_codes, t_codes) or both; without codes use knn_search / knn_search_l1")
+    if metric == "manhattan" and shift is not None:
+        raise ValueError(f"{what}: the manhattan search takes no shift")
+    _operand(q, "q", what)
+    Mq, F = q.shape
+    _operand(t, "t", what, cols=F)
+    Nt = t.shape[0]
+    k = int(k)
+    if not 1 <= k <= min(Nt, L.KNN_MAXK):
+        raise ValueError(f"{what}: k = {k} outside [1, min({Nt} training rows, {L.KNN_MAXK})]")
+    if t.device != q.device:
+        raise ValueError(f"{what}: all operands must live on one device")
+    codes = []
+    for name, pair in (("same", same), ("differ", differ)):
+        if pair is None:
+            codes += [None, None]
+            continue
+        if not isinstance(pair, (tuple, list)) or len(pair) != 2:
+            raise ValueError(f"{what}: {name} must be a (q_codes, t_codes) pair")
+        codes += [_vector(pair[0], f"{name}[0]", what, torch.int32, Mq, q.device), _vector(pair[1], f"{name}[1]", what, torch.int32, Nt, q.device)]
+    shift = _shift(shift, what, F, q.device)
+    idx = _out_view(idx_out, "idx_out", what, torch.int32, Mq, k, q.device)
+    d = None if dist is False else _out_view(dist_out, "dist_out", what, torch.float32, Mq, k, q.device)
+    work = _workspace(knn_group_work_bytes(Mq, Nt, k, metric), q.device)
+    base = L.KnnArgs(q.data_ptr(), t.data_ptr(), _p(shift), idx.data_ptr(), _p(d), _p(work), _ld(q), _ld(t), _ld(idx), _ld0(d),
+                     work.numel() * 8, Mq, Nt, F, k, _dt(q), _dt(t))
+    a = L.KnnGroupArgs(base, *(_p(c) for c in codes), _KNN_METRICS[metric])
+    with probe_span(what, lambda: dict(kind="valu" if metric == "manhattan" else "gemm", flops=2.0 * Mq * Nt * F, M=Mq, N=Nt, K=F)):
+        L.check(L.load().mmvae_knn_search_grouped(C.byref(a), _stream()), "mmvae_knn_search_grouped")
+    return idx, d
+
+
 def _knn_idx(idx, what):
     """(Mq, k) of idx, the int32 (Mq, 1 <= k <= KNN_MAXK) neighbour lists of a search (the first k columns of a wider one are allowed)"""
     if not isinstance(idx, torch.Tensor) or not idx.is_cuda or idx.dtype != torch.int32 or idx.dim() != 2 or idx.stride(1) != 1 or idx.shape[0] < 1 \
