@@ -101,3 +101,25 @@ def consumed(n_mask, n_eps):
 def eps_base(offset, n_mask):
     """First counter of the normals of a combined call."""
     return (int(offset) + 4 * ((int(n_mask) + 15) // 16)) & 0xFFFFFFFFFFFFFFFF
+
+
+def mask_segments(B, widths):
+    """-> ([first byte of every (B, w) keep-mask], bytes in all) of one combined mask buffer: every segment starts on a
+    16-byte boundary (a whole quad), so the gaps draw and drop random bytes."""
+    segs, total = [], 0
+    for w in widths:
+        segs.append(total)
+        total = (total + int(B) * int(w) + 15) // 16 * 16
+    return segs, total
+
+
+def noise_source_draw(seed, offset, B, widths, Ld, keep_prob=0.9):
+    """One draw of the engine's noise source (mmvae.engine.NoiseSource.draw) restated on the host: ONE combined call for all
+    keep-masks of a forward, laid out by mask_segments, and the (B, Ld) normals behind them (none if Ld is None).
+    -> ([uint8 (B, w) keep-mask for w in widths], eps float32 (B, Ld) or None, offset of the next draw)."""
+    segs, total = mask_segments(B, widths)
+    ref = mask_bytes(total, keep_prob, seed, offset) if total else None
+    masks = [ref[o:o + B * w].reshape(B, w) for o, w in zip(segs, widths)]
+    n_eps = 0 if Ld is None else B * Ld
+    eps = normals(n_eps, seed, eps_base(offset, total)).astype(np.float32).reshape(B, Ld) if n_eps else None
+    return masks, eps, (int(offset) + consumed(total, n_eps)) & 0xFFFFFFFFFFFFFFFF

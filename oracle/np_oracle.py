@@ -346,14 +346,17 @@ def vae_forward(P, Bf, a=None, b=None, site=None, masks=None, eps=None, train=Tr
 
 
 def vae_backward(P, cache, d_out_a, d_out_b, d_out_c, d_mu, d_lv, q=None, b_is_logit_grad=False):
-    """Autograd of vae_forward (reference caller: optimize_hyperparameters.py:112)."""
+    """Autograd of vae_forward (reference caller: optimize_hyperparameters.py:112).  A d_out_* of None is a decoder no loss
+    term reads: it adds nothing to dz and its parameters are absent from the returned G (autograd leaves their .grad None)."""
     G = {}
-    dz = decoder_bwd(P, cache["dec_a"], d_out_a, G, q)
-    dz = dz + decoder_bwd(P, cache["dec_b"], d_out_b, G, q, b_is_logit_grad)
-    dz = dz + decoder_bwd(P, cache["dec_c"], d_out_c, G, q)
+    dz = np.zeros_like(cache["lv"])
+    for key, d_out, logit in (("dec_a", d_out_a, False), ("dec_b", d_out_b, b_is_logit_grad), ("dec_c", d_out_c, False)):
+        if d_out is not None:
+            dz = dz + decoder_bwd(P, cache[key], d_out, G, q, logit)
     std = np.exp(0.5 * cache["lv"])
-    dmu = d_mu + dz
-    dlv = d_lv + dz * cache["eps"] * std * 0.5
+    dmu = dz if d_mu is None else d_mu + dz                 # None: no KL term
+    dlv = dz * cache["eps"] * std * 0.5
+    dlv = dlv if d_lv is None else d_lv + dlv
     n = cache["n"]
     dmu_m, dlv_m = dmu / n, dlv / n
     if "enc_a" in cache:
@@ -428,20 +431,55 @@ def vae_loss(recon_a, a, recon_b, b, recon_c, site, mu, logvar, beta=1e-3, gamma
     return total, recon, cls, kld, grads
 
 
-def rna2dna_loss(recon_dna, dna, mu, logvar, beta=1e-3):
-    """src/utils/directional_losses.py:8-30."""
-    rec = _bce_sum(recon_dna, dna)
+def partial_loss(terms, recon_a=None, a=None, recon_b=None, b=None, recon_c=None, site=None, mu=None, logvar=None,
+                 beta=1e-3, gamma=1.0, class_weights=None, q=None):
+    """The loss of src/utils/losses.py:8-46 restricted to `terms`, a subset of {"a" (sum-MSE), "b" (clamped sum-BCE),
+    "c" (weighted sum-CE), "kl"}: what a caller gets who applies only those terms to the model's outputs.  Returns
+    (total, recon, class, kld, grads) like vae_loss; an absent term counts 0.0 and its gradient entries are None (both
+    recon_b and recon_b_logit for "b", both mu and logvar for "kl"), which is what vae_backward takes for "no gradient"."""
+    q = q or _id
+    terms = set(terms)
+    assert terms and terms <= {"a", "b", "c", "kl"}, terms
+    mse = bce = cls = kld = 0.0
+    grads = dict(recon_a=None, recon_b=None, recon_b_logit=None, recon_c=None, mu=None, logvar=None)
+    if "a" in terms:
+        mse = np.sum((recon_a - a) ** 2)
+        grads["recon_a"] = q(2.0 * (recon_a - a))
+    if "b" in terms:
+        with np.errstate(divide="ignore"):
+            bce = _bce_sum(recon_b, b)
+        grads["recon_b"] = _bce_grad(recon_b, b)
+        grads["recon_b_logit"] = q(_bce_logit_grad(recon_b, b))
+    if "c" in terms:
+        cls, g_c = _ce_sum(recon_c, site, class_weights)
+        grads["recon_c"] = gamma * g_c
+    if "kl" in terms:
+        kld = _kld(mu, logvar)
+        grads["mu"] = beta * mu
+        grads["logvar"] = beta * (-0.5) * (1.0 - np.exp(logvar))
+    recon = mse + bce
+    return recon + gamma * cls + beta * kld, recon, cls, kld, grads
+
+
+def rna2dna_loss(recon_dna, dna, mu, logvar, beta=1e-3, q=None):
+    """src/utils/directional_losses.py:8-30.  grads also holds `recon_logit`, the gradient w.r.t. the decoder's pre-sigmoid
+    logits, rounded with q as the device stores it (vae_loss's recon_b_logit)."""
+    q = q or _id
+    with np.errstate(divide="ignore"):
+        rec = _bce_sum(recon_dna, dna)
     kld = _kld(mu, logvar)
-    grads = dict(recon=_bce_grad(recon_dna, dna), mu=beta * mu,
+    grads = dict(recon=_bce_grad(recon_dna, dna), recon_logit=q(_bce_logit_grad(recon_dna, dna)), mu=beta * mu,
                  logvar=beta * (-0.5) * (1.0 - np.exp(logvar)))
     return rec + beta * kld, rec, kld, grads
 
 
-def dna2rna_loss(recon_rna, rna, mu, logvar, beta=1e-3):
-    """src/utils/directional_losses.py:33-55."""
+def dna2rna_loss(recon_rna, rna, mu, logvar, beta=1e-3, q=None):
+    """src/utils/directional_losses.py:33-55.  With q the reconstruction gradient is rounded as the device stores it
+    (vae_loss's recon_a)."""
+    q = q or _id
     rec = np.sum((recon_rna - rna) ** 2)
     kld = _kld(mu, logvar)
-    grads = dict(recon=2.0 * (recon_rna - rna), mu=beta * mu,
+    grads = dict(recon=q(2.0 * (recon_rna - rna)), mu=beta * mu,
                  logvar=beta * (-0.5) * (1.0 - np.exp(logvar)))
     return rec + beta * kld, rec, kld, grads
 
@@ -540,6 +578,22 @@ def train_step(P, Bf, state, step, a, b, site, masks, eps, beta=1e-3, gamma=1.0,
     step = adamw_step(P, G, state, step, lr, wd)
     return dict(out_a=out_a, out_b=out_b, out_c=out_c, mu=mu, logvar=lv, total=total, recon=rec,
                 cls=cls, kld=kld, grads=G, step=step)
+
+
+def directional_train_step(kind, P, Bf, state, step, x, target, site, masks, eps, beta=1e-3, lr=5e-4, wd=1e-5, q=None):
+    """train_step for RNA2DNAVAE (kind='rna2dna': x = rna, target = dna) / DNA2RNAVAE (kind='dna2rna': x = dna, target = rna):
+    forward -> directional loss -> backward -> AdamW (train_dna2rna.py:86-96).  P is keyed by the MultiModalVAE names; only
+    the sub-modules of `kind` are read, get a gradient and move.  With q the decoder's backward starts from the rounded
+    gradient the device hands over (w.r.t. the logits for rna2dna), as train_step does."""
+    out, mu, lv, cache = directional_forward(kind, P, Bf, x, site, masks, eps, True, q=q)
+    lossf = rna2dna_loss if kind == "rna2dna" else dna2rna_loss
+    total, rec, kld, g = lossf(out, target, mu, lv, beta, q=q)
+    if q is None or kind == "dna2rna":
+        G = directional_backward(P, cache, g["recon"], g["mu"], g["logvar"], q)
+    else:
+        G = directional_backward(P, cache, g["recon_logit"], g["mu"], g["logvar"], q, True)
+    step = adamw_step(P, G, state, step, lr, wd)
+    return dict(out=out, mu=mu, logvar=lv, total=total, recon=rec, kld=kld, grads=G, step=step)
 
 
 def cast_tree(d, dtype):

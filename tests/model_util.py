@@ -47,5 +47,29 @@ def named_grads(model, rename=None):
     return out
 
 
+ADAM_SHARE = {"fp32": 2e-3, "bf16": 2e-2}
+
+
+def check_params_after_adamw(model, P1, lr, prec, rename=None):
+    """Parameters after ONE AdamW step against the oracle's update of ITS gradients (P1, oracle names), in the form of
+    tests/test_fullsize_gpu.py::test_full_step_at_batch_65536: a first Adam step moves every element by ~lr, and an element
+    whose gradient is rounding noise may take the other sign -- the share of elements off by more than 1e-6 stays <= 2e-3
+    (fp32) / 2e-2 (bf16) per tensor and none is further off than 2.1 lr.  The analytically zero biases are skipped.
+    -> (worst share, worst distance)."""
+    inv = {v: k for k, v in rename.items()} if rename else None
+    worst_share = worst_d = 0.0
+    for k, p in model.named_parameters():
+        if inv is not None:
+            top, rest = k.split(".", 1)
+            k = inv[top] + "." + rest
+        if k in CHAOTIC_BIASES:
+            continue
+        d = np.abs(p.detach().cpu().numpy() - P1[k])
+        share = float(np.mean(d > 1e-6))
+        worst_share, worst_d = max(worst_share, share), max(worst_d, float(d.max()))
+        assert share <= ADAM_SHARE[prec] and d.max() <= 2.1 * lr, (k, float(d.max()), share)
+    return worst_share, worst_d
+
+
 def f64(d):
     return O.cast_tree(d, np.float64)

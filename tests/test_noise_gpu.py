@@ -189,21 +189,21 @@ def test_noise_source_draw_follows_the_reference_stream():
     src = engine.NoiseSource()
     dev = torch.device("cuda", torch.cuda.current_device())
     src.load_state_dict({"offset": 12345}, dev)
-    segs, total = [], 0
-    for w in widths:
-        segs.append(total)
-        total = (total + B * w + 15) // 16 * 16
+    segs, total = N.mask_segments(B, widths)
+    assert segs == [0, 7712, 7712 + B * 256] and total == 7712 + B * 256 + 2544      # 7700 -> 7712, 2541 -> 2544
     off = 12345
     for _ in range(2):                              # the second draw starts where the first one ended
         masks, eps = src.draw(B, widths, Ld, dev)
         torch.cuda.synchronize()
-        ref = N.mask_bytes(total, 1.0 - ops.DROP_P, seed, off)
-        for m, o, w in zip(masks, segs, widths):
+        ref, ref_eps, nxt = N.noise_source_draw(seed, off, B, widths, Ld, 1.0 - ops.DROP_P)
+        for m, r, w in zip(masks, ref, widths):
             assert tuple(m.shape) == (B, w) and m.dtype == torch.uint8
-            np.testing.assert_array_equal(m.cpu().numpy().reshape(-1), ref[o:o + B * w])
+            np.testing.assert_array_equal(m.cpu().numpy().reshape(-1), r.reshape(-1))
         assert tuple(eps.shape) == (B, Ld)
         _check_eps(eps.double().cpu().numpy().reshape(-1), B * Ld, seed, N.eps_base(off, total))
+        assert ref_eps.dtype == np.float32 and np.array_equal(ref_eps.reshape(-1), N.normals(B * Ld, seed, N.eps_base(off, total)).astype(np.float32))
         off += N.consumed(total, B * Ld)
+        assert nxt == off
         assert src.state_dict(dev)["offset"] == off
         assert (src.offset_tensor(dev) == off).all()
     masks, eps = src.draw(B, widths, None, dev)     # masks alone (a directional model without eps)

@@ -66,6 +66,25 @@ def test_counter_bookkeeping():
     assert N.eps_base(2 ** 64 - 4, 16) == 0                             # 64-bit wrap
 
 
+def test_noise_source_draw_layout():
+    """The host restatement of one engine draw: 16-byte aligned mask segments inside ONE mask stream, the normals behind it,
+    and the offset of the following draw."""
+    B, widths, Ld = 7, (5, 16, 3), 3                # 35 -> 48, 112 -> 112, 21 -> 32 bytes
+    assert N.mask_segments(B, widths) == ([0, 48, 160], 192)
+    masks, eps, nxt = N.noise_source_draw(11, 1000, B, widths, Ld, 0.5)
+    stream = N.mask_bytes(192, 0.5, 11, 1000)
+    for m, o, w in zip(masks, (0, 48, 160), widths):
+        assert m.shape == (B, w) and m.dtype == np.uint8 and np.array_equal(m.reshape(-1), stream[o:o + B * w])
+    assert np.array_equal(masks[1].reshape(-1)[:16], N.mask_bytes(16, 0.5, 11, 1000 + 4 * 3))    # segment 1 starts at quad 3
+    assert eps.shape == (B, Ld) and eps.dtype == np.float32
+    assert np.array_equal(eps.reshape(-1), N.normals(21, 11, 1000 + 4 * 12).astype(np.float32))
+    assert nxt == 1000 + 4 * 12 + 6
+    m2, e2, n2 = N.noise_source_draw(11, nxt, B, (), Ld)               # no masks: the normals start at the offset itself
+    assert m2 == [] and np.array_equal(e2.reshape(-1), N.normals(21, 11, nxt).astype(np.float32)) and n2 == nxt + 6
+    m3, e3, n3 = N.noise_source_draw(11, 0, B, (5,), None)             # masks alone
+    assert e3 is None and n3 == 4 * 3 and N.noise_source_draw(11, 2 ** 64 - 4, B, (5,), None)[2] == 8      # 64-bit wrap
+
+
 def test_reference_normals_moments():
     z = N.normals(1 << 20, 7, 0)
     assert z.dtype == np.float64 and np.isfinite(z).all()

@@ -78,6 +78,63 @@ def test_bf16_aware_oracle_vs_golden(name):
     print(f"{name}: worst gradient Frobenius {fros[worst]:.3e} ({worst}), median {np.median(list(fros.values())):.3e}")
 
 
+def _first_directional_step(fx, kind, q):
+    A, D, S, L, E = [int(x) for x in fx["dims"]]
+    B, seed = int(fx["B"]), int(fx["seed"])
+    P, Bf = O.make_params(seed, A, D, S, L, E)
+    P, Bf = O.cast_tree(P, F64), O.cast_tree(Bf, F64)
+    a, b, site = O.make_batch(seed + 1, B, A, D, S)
+    x, tgt = (a, b) if kind == "rna2dna" else (b, a)
+    state, step = O.adamw_init(P)
+    masks, eps = O.make_noise(seed + 100, B, L)
+    return O.directional_train_step(kind, P, Bf, state, step, x.astype(F64), tgt.astype(F64), site, masks, eps.astype(F64),
+                                    float(fx["beta"]), q=q)
+
+
+@pytest.mark.parametrize("kind", ["rna2dna", "dna2rna"])
+def test_identity_hook_is_the_fp64_oracle_directional(kind):
+    """The q path of the directional models (for rna2dna: DecoderB back-propagated from the logit gradient) with the identity
+    hook against the reference form, to 1e-9 (measured <= 5e-15)."""
+    fx = load(kind + "_b32")
+    r0, ri = _first_directional_step(fx, kind, None), _first_directional_step(fx, kind, O._id)
+    for k in ("out", "mu", "logvar"):
+        np.testing.assert_allclose(ri[k], r0[k], rtol=1e-9, atol=0)
+    for k in ("total", "recon", "kld"):
+        assert abs(ri[k] - r0[k]) <= 1e-9 * abs(r0[k])
+    assert set(ri["grads"]) == set(r0["grads"])
+    wscale = np.abs(r0["grads"]["encoder_a.fc.0.weight" if kind == "rna2dna" else "encoder_b.fc.0.weight"]).max()
+    for k, g in r0["grads"].items():
+        if k in CHAOTIC_BIASES:
+            assert np.abs(ri["grads"][k]).max() <= 1e-9 * max(1.0, wscale)
+            continue
+        assert np.linalg.norm(ri["grads"][k] - g) <= 1e-9 * np.linalg.norm(g), k
+
+
+@pytest.mark.parametrize("kind", ["rna2dna", "dna2rna"])
+def test_bf16_aware_oracle_vs_golden_directional(kind):
+    """q=BF16 on the directional models stays within this file's bounds of the reference's vectors (measured worst Frobenius:
+    0.061 rna2dna, encoder_a.fc.0.weight; 0.087 dna2rna, encoder_b.fc.1.bias)."""
+    fx = load(kind + "_b32")
+    A, D, S, L, E = [int(x) for x in fx["dims"]]
+    ren = O.directional_param_names(kind, A, D, S, L, E)
+    rq = _first_directional_step(fx, kind, O.BF16)
+    for k in ("out", "mu", "logvar"):
+        got, ref = _fixture_entry(fx, "s0." + k, rq[k])
+        assert np.abs(got - ref).max() <= 1e-2 * np.abs(ref).max(), k
+    np.testing.assert_allclose([rq["total"], rq["recon"], rq["kld"]], fx["s0.loss"], rtol=3e-3)
+    fros = {}
+    for k, g in rq["grads"].items():
+        if k in CHAOTIC_BIASES:
+            continue
+        top, rest = k.split(".", 1)
+        got, ref = _fixture_entry(fx, f"s0.grad.{ren[top]}.{rest}", g)
+        fros[k] = float(np.linalg.norm(got - ref) / np.linalg.norm(ref))
+        assert fros[k] <= 0.12, (k, fros[k])
+    assert len(fros) == len(rq["grads"]) - (1 if kind == "rna2dna" else 2)
+    worst = max(fros, key=fros.get)
+    print(f"{kind}: worst gradient Frobenius {fros[worst]:.3e} ({worst}), median {np.median(list(fros.values())):.3e}")
+
+
 def test_bf16_round_is_round_to_nearest_even():
     x = np.array([1.0, 1.00390625, 1.005859375, 1.01171875, -3.1415927, 0.0, 65504.0], dtype=np.float32)
     # 1 + 2^-8 is a tie between 1.0 and 1 + 2^-7: to even (1.0); 1 + 3*2^-9 rounds up; 1 + 3*2^-8 is a tie: to even (1 + 2^-6)

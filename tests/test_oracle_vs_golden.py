@@ -186,3 +186,59 @@ def test_eval_mode_backward_matches_autograd():
     G = O.vae_backward(P64, cache, g["recon_a"], g["recon_b"], g["recon_c"], g["mu"], g["logvar"])
     for k, t_ in p.items():
         np.testing.assert_allclose(G[k], t_.grad.numpy(), rtol=2e-3, atol=2e-4 + 3e-4 * np.abs(t_.grad.numpy()).max(), err_msg=k)
+
+
+@pytest.mark.parametrize("case", ["a", "b_site", "a_b", "site"])
+def test_partial_modality_backward_matches_autograd(case):
+    """A TRAINING step on a subset of the modalities and of the loss terms (tests/partial_cases.py): np_oracle's forward,
+    partial_loss and vae_backward with absent decoder gradients against float64 autograd of oracle/torch_ref.py with the same
+    injected masks and eps and stock torch losses on the chosen terms.  Every gradient to 1e-9 Frobenius-relative (measured
+    <= 2e-14), the parameters WITHOUT a gradient the same set on both sides."""
+    import torch
+    import torch.nn.functional as F
+    import torch_ref as T
+    from partial_cases import CASES, oracle_partial_step
+    A, D, S, L, E, B = 24, 40, 5, 4, 8, 33
+    beta, gamma = 0.01, 0.5
+    P, Bf = O.make_params(3, A, D, S, L, E)
+    a, b, site = O.make_batch(4, B, A, D, S)
+    masks, eps = O.make_noise(5, B, L)
+    cw = np.random.default_rng(6).uniform(0.5, 2.0, S)
+    P64, Bf64 = O.cast_tree(P, F64), O.cast_tree(Bf, F64)
+    ref = oracle_partial_step(P64, Bf64, a, b, site, masks, eps, case, beta, gamma, cw, None)
+
+    p = {k: torch.tensor(v, dtype=torch.float64, requires_grad=True) for k, v in P64.items()}
+    bufs = {k: torch.tensor(np.asarray(v)) for k, v in Bf64.items()}
+    ta, tb, ts = torch.from_numpy(a).double(), torch.from_numpy(b).double(), torch.from_numpy(site)
+    tm = {k: torch.from_numpy(v).double() for k, v in masks.items()}
+    c = CASES[case]
+    ra, rb, rc, mu, lv = T.forward(p, bufs, ta if "a" in c["inputs"] else None, tb if "b" in c["inputs"] else None,
+                                   ts if "site" in c["inputs"] else None, True, tm, torch.from_numpy(eps).double())
+    loss = 0.0
+    if "a" in c["terms"]:
+        loss = loss + F.mse_loss(ra, ta, reduction="sum")
+    if "b" in c["terms"]:
+        loss = loss + F.binary_cross_entropy(rb, tb, reduction="sum")
+    if "c" in c["terms"]:
+        loss = loss + gamma * F.cross_entropy(rc, ts, weight=torch.from_numpy(cw), reduction="sum")
+    if "kl" in c["terms"]:
+        loss = loss + beta * (-0.5 * torch.sum(1 + lv - mu.pow(2) - lv.exp()))
+    loss.backward()
+    np.testing.assert_allclose(ref["losses"][0], loss.item(), rtol=1e-12)
+    for nm, t_ in (("out_a", ra), ("out_b", rb), ("out_c", rc), ("mu", mu), ("logvar", lv)):
+        np.testing.assert_allclose(ref[nm], t_.detach().numpy(), rtol=1e-9, atol=1e-12, err_msg=nm)
+    G = ref["G"]
+    assert {k for k, t_ in p.items() if t_.grad is None} == set(p) - set(G)
+    assert set(p) - set(G), "every case leaves some block without a gradient"
+    worst = 0.0
+    for k, g in G.items():
+        want = p[k].grad.numpy()
+        if k in CHAOTIC_BIASES:             # analytically zero: rounding noise on both sides, measured against the layer's weight gradient
+            assert np.abs(g - want).max() <= 1e-9 * np.abs(G[k.replace(".bias", ".weight")]).max(), k
+            continue
+        err = float(np.linalg.norm(g - want) / np.linalg.norm(want))
+        worst = max(worst, err)
+        assert err <= 1e-9, (k, err)
+    for k, v in ref["Bf"].items():          # running statistics of the encoders that ran moved, the others did not
+        np.testing.assert_allclose(v, bufs[k].numpy(), rtol=1e-12, atol=0, err_msg=k)
+    print(f"partial case {case}: worst gradient Frobenius-rel {worst:.1e}; no gradient for {sorted({k.split('.')[0] for k in set(p) - set(G)})}")
