@@ -48,7 +48,8 @@ int mmvae_abi_version(void);    /* bumped on any struct change; the ctypes bindi
  * key 6 / key 7 = row-coalesced LDS form of the BatchNorm-backward / ReLU-mask dX epilogue on/off; key 8 = wave-specialised NT kernel
  * (gemm_ntp.h: producer / consumer waves) on/off, key 9 = its minimum M (default 16384); key 10 = the fused latent launch
  * (mmvae_latent_fwd) on/off: off, it returns MMVAE_ERR_ARG and the caller issues the launches it replaces; key 12 = the fused class-head
- * launch (mmvae_class_tail) on/off, in the same way.  Other keys: MMVAE_ERR_ARG. */
+ * launch (mmvae_class_tail) on/off, in the same way; key 13 = the merged head-of-step launch (mmvae_step_head) on/off and key 14 = the
+ * riders of the grouped dW launch (mmvae_gemm_tn_group_riders) on/off, in the same way.  Other keys: MMVAE_ERR_ARG. */
 int mmvae_set_tuning(int32_t key, int32_t value);
 
 /* ---------------------------------------------------------------------------------------------
@@ -169,6 +170,22 @@ int mmvae_gemm_tn(const mmvae_gemm_tn_args* args, void* stream);
 #define MMVAE_TN_GROUP_MAX 8
 #define MMVAE_TN_GROUP_SPLITS 256
 int mmvae_gemm_tn_group(const mmvae_gemm_tn_args* args, int32_t n, void* stream);
+/* The same grouped launch with RIDERS: small launches of the end of the backward that neither feed nor read the group run as extra
+ * workgroups appended to its grid instead of as latency chains of their own (10 + 5 us per step beside a 52 us launch).
+ *   EncoderC backward (S > 0): mmvae_embed_table_bwd's arguments, workgroups and LDS image; results bit-identical to that call.
+ *     It writes EncoderC's five gradient tensors, which no problem of the group may alias.
+ *   Loss finalisation (sums != NULL): mmvae_loss_finalize's arguments, one thread.
+ * Returns MMVAE_ERR_ARG, with nothing enqueued, when riders is NULL or names no rider, a rider's arguments are incomplete, the
+ * EncoderC rider's LDS need (S*2L + S*E + 2L*E floats) exceeds the dynamic LDS the group kernel is launched with (72 KiB) or
+ * mmvae_embed_table_bwd's own capacity (64 KiB: 24 sites x latent 128 x embed 32 ride, 59 KiB), tuning key 14 is off, or
+ * mmvae_gemm_tn_group would refuse the problems: the caller then issues the launches this one replaces. */
+typedef struct {
+    int32_t S, E, L, table_copies;
+    const float* emb; const float* w_mu; const float* w_lv; const float* d_table;
+    float* d_emb; float* d_w_mu; float* d_b_mu; float* d_w_lv; float* d_b_lv;
+    const double* sums; float beta, gamma; const float* beta_gamma_dev; float* out5;
+} mmvae_tn_riders;
+int mmvae_gemm_tn_group_riders(const mmvae_gemm_tn_args* args, int32_t n, const mmvae_tn_riders* riders, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * BatchNorm1d, training mode (encoders.py:14,32,36): from the column sums compute
@@ -409,6 +426,31 @@ int mmvae_scale_many(const mmvae_scale_item* items_host, int32_t n_items, const 
 int mmvae_noise(uint8_t* mask, int64_t n_mask, float keep_prob, float* eps, int64_t n_eps, uint64_t seed, uint64_t offset,
                 uint64_t* offset_dev, int32_t advance, void* stream);
 int mmvae_counter_add(uint64_t* counter_dev, uint64_t inc, void* stream);      /* *counter_dev += inc */
+
+/* ---------------------------------------------------------------------------------------------
+ * Head of a training step: the four mutually independent launches a forward begins with, as ONE launch whose workgroups take
+ * roles by block range.  Three of them are latency chains (9 + 5 + 5 us) that fit under the one with real work, the Philox
+ * arithmetic of the noise (25 us): they get the lowest block indices, in the order below, and the noise blocks follow.
+ *   table : mmvae_embed_table_fwd's arguments (S > 0)
+ *   zero  : up to MMVAE_HEAD_ZERO_MAX ranges (16-byte aligned, a whole multiple of 16 bytes each) filled with zeros --
+ *           the step's one memset
+ *   prep  : mmvae_prep_weights' arguments (n_prep > 0)
+ *   noise : mmvae_noise's arguments (n_mask + n_eps > 0), the same counter values consumed and the same advance
+ * Every role runs the device code of the stand-alone entry point named with it: results are bit-identical to those calls.
+ * A role whose count is 0 is empty.  Returns MMVAE_ERR_ARG, with nothing enqueued, when every role is empty, a role's arguments
+ * would be refused by its own entry point, a zero range is misaligned, or tuning key 13 is off.
+ * ------------------------------------------------------------------------------------------- */
+#define MMVAE_HEAD_ZERO_MAX 4
+typedef struct {
+    int32_t S, E, L, n_zero;
+    const float* emb; const float* w_mu; const float* b_mu; const float* w_lv; const float* b_lv; float* table;
+    void* zero_ptr[MMVAE_HEAD_ZERO_MAX]; int64_t zero_bytes[MMVAE_HEAD_ZERO_MAX];
+    const mmvae_prep_item* prep_items; int32_t n_prep;
+    int32_t advance;
+    uint8_t* mask; int64_t n_mask; float* eps; int64_t n_eps;
+    uint64_t seed, offset; uint64_t* offset_dev; float keep_prob; int32_t pad_;
+} mmvae_step_head_args;
+int mmvae_step_head(const mmvae_step_head_args* args, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Minibatch assembly from a device-resident dataset: dst_t[i][:] = src_t[idx[i]][:], i < rows, for up to MMVAE_GATHER_MAX

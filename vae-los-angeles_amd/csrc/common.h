@@ -215,6 +215,8 @@ struct Tuning {
     int ntp_min_m = 16384;           // key 9: below this a persistent 256-workgroup grid has < 1 tile per CU
     int latent_on = 1;               // key 10: the fused latent launch (latent.hip); off: mmvae_latent_fwd answers MMVAE_ERR_ARG
     int class_tail_on = 1;           // key 12: the fused class-head launch (class_tail.hip); off: mmvae_class_tail answers MMVAE_ERR_ARG
+    int step_head_on = 1;            // key 13: the merged head-of-step launch (elementwise.hip); off: mmvae_step_head answers MMVAE_ERR_ARG
+    int tn_riders_on = 1;            // key 14: riders in the grouped dW launch (gemm_tn.hip); off: mmvae_gemm_tn_group_riders answers MMVAE_ERR_ARG
 };
 inline Tuning g_tuning;
 

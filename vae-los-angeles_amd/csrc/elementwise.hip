@@ -8,6 +8,7 @@
 #include "mmvae_hip.h"
 #include "fuse_math.h"
 #include "loss_terms.h"
+#include "tail_riders.h"
 
 namespace mm {
 
@@ -16,16 +17,15 @@ namespace mm {
 // ------------------------------------------------------------------------------------------
 // 32 x 32 tiles of the destination; transposed copies go through LDS so that both the fp32 reads and the bf16 writes run along rows
 // (the element-per-thread form read the source of a transposed copy with a stride of one source row per lane: 21 us for 2 x 2.3 MB).
-__global__ __launch_bounds__(256) void prep_weights_kernel(const mmvae_prep_item* __restrict__ items) {
-    const mmvae_prep_item it = items[blockIdx.y];
-    __shared__ float tile[32][33];
+// Workgroup bx of the nbx that share item `it` (the stand-alone kernel's grid row; a block range of step_head_kernel)
+__device__ __forceinline__ void prep_item_tiles(const mmvae_prep_item& it, int bx, int nbx, float (*tile)[33]) {
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;                 // 32 x 8 threads, 4 rows each
     const int tiles_c = (it.dst_cols + 31) / 32, tiles_r = (it.dst_rows + 31) / 32;
     auto put = [&](int r, int c, float v) {
         if (it.dst_dtype == MMVAE_BF16) ((bf16*)it.dst)[(long)r * it.dst_ld + c] = (bf16)v;
         else ((float*)it.dst)[(long)r * it.dst_ld + c] = v;
     };
-    for (int t = blockIdx.x; t < tiles_r * tiles_c; t += gridDim.x) {       // block-uniform trip count
+    for (int t = bx; t < tiles_r * tiles_c; t += nbx) {                     // block-uniform trip count
         const int tr = t / tiles_c, tc = t - tr * tiles_c;
         if (it.transpose) {                                                  // dst[r][c] = src[c][r]
 #pragma unroll
@@ -48,6 +48,13 @@ __global__ __launch_bounds__(256) void prep_weights_kernel(const mmvae_prep_item
             }
         }
     }
+}
+
+constexpr int PREP_WG = 160;       // workgroups per item: 48 -> 14.9 us, 96 -> 10.6, 160 -> 8.8, 320 -> 9.0 (the largest item has 288 tiles; every tile is a load -> store round trip)
+__global__ __launch_bounds__(256) void prep_weights_kernel(const mmvae_prep_item* __restrict__ items) {
+    __shared__ float tile[32][33];
+    const mmvae_prep_item it = items[blockIdx.y];
+    prep_item_tiles(it, blockIdx.x, gridDim.x, tile);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -172,9 +179,10 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_cols_kernel(int M, int N, T*
 // ------------------------------------------------------------------------------------------
 // EncoderC table
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void embed_table_fwd_kernel(int S, int E, int L, const float* emb, const float* w_mu,
-                                                               const float* b_mu, const float* w_lv, const float* b_lv, float* table) {
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < S * 2 * L; i += gridDim.x * blockDim.x) {
+// elements i0, i0 + stride, ... of the table, each formed on its own (the stand-alone kernel; a block range of step_head_kernel)
+__device__ __forceinline__ void embed_table_fwd_elems(int S, int E, int L, const float* emb, const float* w_mu, const float* b_mu,
+                                                      const float* w_lv, const float* b_lv, float* table, int i0, int stride) {
+    for (int i = i0; i < S * 2 * L; i += stride) {
         const int s = i / (2 * L), j = i % (2 * L);
         const float* w = j < L ? w_mu + (long)j * E : w_lv + (long)(j - L) * E;
         float acc = j < L ? b_mu[j] : b_lv[j - L];
@@ -183,62 +191,15 @@ __global__ __launch_bounds__(256) void embed_table_fwd_kernel(int S, int E, int 
     }
 }
 
-// All operands are a few KB: every workgroup first copies them into LDS in ONE round of independent loads (the table gradient summed
-// over its scatter copies in fixed order, the embedding, both head weights), then every thread forms its output element from LDS.
-// (Round 2's form walked w_mu / w_lv / emb in global memory inside the dot products: 20-24 dependent rounds of L2 latency, 22 us for
-// a few thousand multiply-adds.)
-__global__ __launch_bounds__(256) void embed_table_bwd_kernel(int S, int E, int L, const float* emb, const float* w_mu,
-                                                               const float* w_lv, const float* dTc, int copies, float* d_emb, float* d_w_mu,
-                                                               float* d_b_mu, float* d_w_lv, float* d_b_lv) {
-    const int L2 = 2 * L;
+__global__ __launch_bounds__(256) void embed_table_fwd_kernel(int S, int E, int L, const float* emb, const float* w_mu,
+                                                               const float* b_mu, const float* w_lv, const float* b_lv, float* table) {
+    embed_table_fwd_elems(S, E, L, emb, w_mu, b_mu, w_lv, b_lv, table, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+}
+
+// the body (and why it stages everything in LDS first): tail_riders.h, shared with the rider workgroups of the grouped dW launch
+__global__ __launch_bounds__(256) void embed_table_bwd_kernel(const EmbedBwd a) {
     extern __shared__ float sm[];
-    float* dT = sm;                                      // [S][2L]: the copies of the table gradient summed (fixed order)
-    float* sE = dT + S * L2;                             // [S][E]
-    float* sW = sE + S * E;                              // [2L][E]: w_mu rows, then w_lv rows
-    const int t0 = blockIdx.x * blockDim.x + threadIdx.x, nt = gridDim.x * blockDim.x;
-    // one index space [dEmb | dWcat | db]: the three products run side by side
-    const int n0 = S * E, n1 = n0 + L2 * E, n2 = n1 + L2;
-    auto dst_of = [&](int i) -> float* {
-        if (i < n0) return d_emb + i;
-        if (i < n1) { const int k = i - n0, j = k / E, e = k - j * E; return j < L ? d_w_mu + (long)j * E + e : d_w_lv + (long)(j - L) * E + e; }
-        const int j = i - n1;
-        return j < L ? d_b_mu + j : d_b_lv + (j - L);
-    };
-    // the gradient element this thread adds to is requested together with the operands: behind the products it was one more
-    // dependent round trip of a launch that is nothing but round trips
-    float* const dst0 = t0 < n2 ? dst_of(t0) : nullptr;
-    const float old0 = dst0 ? *dst0 : 0.f;
-    for (int i = threadIdx.x; i < S * L2; i += blockDim.x) {
-        float c8[8];
-#pragma unroll
-        for (int c = 0; c < 8; ++c) c8[c] = c < copies ? dTc[(long)c * S * L2 + i] : 0.f;
-        float v = 0.f;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) v += c8[c];
-        for (int c = 8; c < copies; ++c) v += dTc[(long)c * S * L2 + i];
-        dT[i] = v;
-    }
-    for (int i = threadIdx.x; i < S * E; i += blockDim.x) sE[i] = emb[i];
-    for (int i = threadIdx.x; i < L2 * E; i += blockDim.x) sW[i] = i < L * E ? w_mu[i] : w_lv[i - L * E];
-    __syncthreads();
-    for (int i = t0; i < n2; i += nt) {
-        float acc = 0.f;
-        if (i < n0) {                                    // dEmb = dT x Wcat
-            const int s = i / E, e = i - s * E;
-#pragma unroll 4
-            for (int j = 0; j < L2; ++j) acc += dT[s * L2 + j] * sW[j * E + e];
-        } else if (i < n1) {                             // dWcat = dT^T x emb
-            const int k = i - n0, j = k / E, e = k - j * E;
-#pragma unroll 4
-            for (int s = 0; s < S; ++s) acc += dT[s * L2 + j] * sE[s * E + e];
-        } else {
-            const int j = i - n1;
-#pragma unroll 4
-            for (int s = 0; s < S; ++s) acc += dT[s * L2 + j];
-        }
-        if (i == t0) *dst0 = old0 + acc;
-        else { float* d = dst_of(i); *d += acc; }
-    }
+    embed_table_bwd_body(a, blockIdx.x, gridDim.x, sm);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -619,13 +580,9 @@ __global__ __launch_bounds__(256) void vae_loss_kernel(mmvae_loss_args a, int ce
     }
 }
 
-// out = {total, recon, class, kld, labels out of range} as the reference returns them (losses.py:44,46); stand-alone form of the
-// tail of vae_loss_kernel (callers that keep `sums` to themselves)
+// stand-alone form of the tail of vae_loss_kernel (callers that keep `sums` to themselves); the body: tail_riders.h
 __global__ void loss_finalize_kernel(const double* sums, float beta, float gamma, const float* beta_gamma_dev, float* out) {
-    if (beta_gamma_dev) { beta = beta_gamma_dev[0]; gamma = beta_gamma_dev[1]; }
-    const double recon = sums[0] + sums[1];
-    out[0] = (float)(recon + (double)gamma * sums[2] + (double)beta * sums[3]);
-    out[1] = (float)recon; out[2] = (float)sums[2]; out[3] = (float)sums[3]; out[4] = (float)sums[4];
+    loss_finalize_body(sums, beta, gamma, beta_gamma_dev, out);
 }
 
 template <typename OT>
@@ -706,16 +663,56 @@ __device__ __forceinline__ void ctr_advance(uint64_t* copies, unsigned L, unsign
         for (unsigned e = L; e < MMVAE_CTR_COPIES; e += nblocks) copies[e] = value;
 }
 
-__global__ __launch_bounds__(256) void noise_kernel(uint8_t* mask, long n_mask, float* eps, long n_eps, uint32_t thresh,
-                                                    uint64_t seed, uint64_t offset, uint64_t* offset_dev, uint64_t advance, int copies) {
-    const uint64_t base = offset_dev ? (copies ? ctr_read(offset_dev, blockIdx.x) : *offset_dev) : 0;
-    offset += base;
-    const long nqm = (n_mask + 15) / 16, nqe = (n_eps + 3) / 4;
-    for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < nqm + nqe; q += (long)gridDim.x * blockDim.x) {
-        if (q < nqm) mask_quad(mask, n_mask, q, thresh, seed, offset);
-        else randn_quad(eps, n_eps, q - nqm, seed, offset + (uint64_t)nqm * 4);
+struct NoiseArgs { uint8_t* mask; long n_mask; float* eps; long n_eps; uint32_t thresh; int copies; uint64_t seed, offset; uint64_t* offset_dev; uint64_t advance; };
+
+// Workgroup lb of the nb that draw the noise (the stand-alone kernel's grid; a block range of step_head_kernel): the quads and
+// the counter copies are indexed by the block's place among THOSE
+__device__ __forceinline__ void noise_block(const NoiseArgs& a, unsigned lb, unsigned nb) {
+    const uint64_t base = a.offset_dev ? (a.copies ? ctr_read(a.offset_dev, lb) : *a.offset_dev) : 0;
+    const uint64_t offset = a.offset + base;
+    const long nqm = (a.n_mask + 15) / 16, nqe = (a.n_eps + 3) / 4;
+    for (long q = (long)lb * blockDim.x + threadIdx.x; q < nqm + nqe; q += (long)nb * blockDim.x) {
+        if (q < nqm) mask_quad(a.mask, a.n_mask, q, a.thresh, a.seed, offset);
+        else randn_quad(a.eps, a.n_eps, q - nqm, a.seed, offset + (uint64_t)nqm * 4);
     }
-    if (copies) ctr_advance(offset_dev, blockIdx.x, gridDim.x, base + advance);
+    if (a.copies) ctr_advance(a.offset_dev, lb, nb, base + a.advance);
+}
+
+__global__ __launch_bounds__(256) void noise_kernel(const NoiseArgs a) { noise_block(a, blockIdx.x, gridDim.x); }
+
+// ------------------------------------------------------------------------------------------
+// head of a training step: EncoderC table | zero fill | weight preparation | noise as block ranges of ONE launch (mmvae_step_head).
+// The first three are chains of dependent round trips with next to no work (5 + 5 + 9 us as launches of their own); they take
+// the lowest block indices -- workgroups are dispatched in ascending order -- and are done while the noise blocks, which follow
+// and are VALU-bound (mask_quad), still run.  Every role calls the device function its stand-alone kernel calls.
+// ------------------------------------------------------------------------------------------
+struct ZeroRange { uint4* p; long n16; };
+struct StepHead {
+    int b_zero, b_prep, b_noise;                       // first block of each role after the table's (block 0); ascending
+    int S, E, L;
+    const float* emb; const float* w_mu; const float* b_mu; const float* w_lv; const float* b_lv; float* table;
+    ZeroRange zero[MMVAE_HEAD_ZERO_MAX]; int n_zero;
+    const mmvae_prep_item* items;
+    NoiseArgs noise;
+};
+
+__global__ __launch_bounds__(256) void step_head_kernel(const StepHead h) {
+    __shared__ float tile[32][33];
+    const int b = blockIdx.x;                          // every branch below is block-uniform
+    if (b >= h.b_noise) {
+        noise_block(h.noise, b - h.b_noise, gridDim.x - h.b_noise);
+    } else if (b >= h.b_prep) {
+        const int p = b - h.b_prep;
+        const mmvae_prep_item it = h.items[p / PREP_WG];
+        prep_item_tiles(it, p % PREP_WG, PREP_WG, tile);
+    } else if (b >= h.b_zero) {
+        const long t0 = (long)(b - h.b_zero) * 256 + threadIdx.x, nt = (long)(h.b_prep - h.b_zero) * 256;
+#pragma unroll
+        for (int k = 0; k < MMVAE_HEAD_ZERO_MAX; ++k)
+            if (k < h.n_zero) for (long i = t0; i < h.zero[k].n16; i += nt) h.zero[k].p[i] = uint4{0u, 0u, 0u, 0u};
+    } else {
+        embed_table_fwd_elems(h.S, h.E, h.L, h.emb, h.w_mu, h.b_mu, h.w_lv, h.b_lv, h.table, b * 256 + threadIdx.x, h.b_zero * 256);
+    }
 }
 
 __global__ void counter_add_kernel(uint64_t* ctr, uint64_t inc) { *ctr += inc; }
@@ -840,6 +837,19 @@ static inline int grid_for(long items, int per_block = 256, int cap = 2048) {
     return (int)g;
 }
 
+// mmvae_noise's argument checks, kernel arguments and grid (also the noise role of mmvae_step_head); false: refuse
+static bool noise_args(uint8_t* mask, int64_t n_mask, float keep_prob, float* eps, int64_t n_eps, uint64_t seed, uint64_t offset,
+                       uint64_t* offset_dev, int32_t advance, NoiseArgs& a, int& grid) {
+    if ((n_mask > 0 && (!mask || ((uintptr_t)mask & 15))) || (n_eps > 0 && !eps) || n_mask < 0 || n_eps < 0 || n_mask + n_eps == 0 ||
+        keep_prob < 0.f || keep_prob > 1.f || (advance && !offset_dev)) return false;
+    const uint64_t used = (uint64_t)((n_mask + 15) / 16 * 4 + (n_eps + 3) / 4);       // counter values this call consumes
+    const double t = (double)keep_prob * 4294967296.0;
+    const uint32_t thresh = t >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)t;
+    a = NoiseArgs{mask, (long)n_mask, eps, (long)n_eps, thresh, advance ? 1 : 0, seed, offset, offset_dev, used};
+    grid = grid_for((n_mask + 15) / 16 + (n_eps + 3) / 4);
+    return true;
+}
+
 }  // namespace mm
 
 using namespace mm;
@@ -848,8 +858,7 @@ extern "C" int mmvae_abi_version(void) { return 20; }
 
 extern "C" int mmvae_prep_weights(const mmvae_prep_item* items_dev, int32_t n_items, void* stream) {
     if (!items_dev || n_items <= 0) return MMVAE_ERR_ARG;
-    // workgroups per item: 48 -> 14.9 us, 96 -> 10.6, 160 -> 8.8, 320 -> 9.0 (the largest item has 288 tiles; every tile is a load -> store round trip)
-    hipLaunchKernelGGL(prep_weights_kernel, dim3(160, n_items), dim3(256), 0, (hipStream_t)stream, items_dev);
+    hipLaunchKernelGGL(prep_weights_kernel, dim3(PREP_WG, n_items), dim3(256), 0, (hipStream_t)stream, items_dev);
     MM_CHECK_LAUNCH();
     return 0;
 }
@@ -929,10 +938,10 @@ extern "C" int mmvae_embed_table_bwd(int32_t S, int32_t E, int32_t L, const floa
                                      float* d_b_lv, void* stream) {
     if (S <= 0 || E <= 0 || L <= 0 || !emb || !w_mu || !w_lv || !d_table || !d_emb || !d_w_mu || !d_b_mu || !d_w_lv || !d_b_lv) return MMVAE_ERR_ARG;
     if (table_copies < 1) table_copies = 1;
-    const size_t lds = ((size_t)S * 2 * L + (size_t)S * E + (size_t)2 * L * E) * sizeof(float);
-    if (lds > 64 * 1024) return MMVAE_ERR_ARG;                    // 60 KB at latent 128, embed 32, 24 sites
-    const int work = S * E + 2 * L * E + 2 * L;          // one output element per thread
-    hipLaunchKernelGGL(embed_table_bwd_kernel, dim3((work + 255) / 256), dim3(256), lds, (hipStream_t)stream, S, E, L, emb, w_mu, w_lv, d_table, table_copies, d_emb, d_w_mu, d_b_mu, d_w_lv, d_b_lv);
+    const size_t lds = embed_bwd_lds(S, E, L);
+    if (lds > EMBED_BWD_LDS_MAX) return MMVAE_ERR_ARG;
+    const EmbedBwd a{S, E, L, table_copies, emb, w_mu, w_lv, d_table, d_emb, d_w_mu, d_b_mu, d_w_lv, d_b_lv};
+    hipLaunchKernelGGL(embed_table_bwd_kernel, dim3(embed_bwd_blocks(S, E, L)), dim3(256), lds, (hipStream_t)stream, a);
     MM_CHECK_LAUNCH();
     return 0;
 }
@@ -1075,13 +1084,42 @@ extern "C" int mmvae_scale_if_needed(void* x, int32_t dtype, int64_t n, const fl
 
 extern "C" int mmvae_noise(uint8_t* mask, int64_t n_mask, float keep_prob, float* eps, int64_t n_eps, uint64_t seed,
                            uint64_t offset, uint64_t* offset_dev, int32_t advance, void* stream) {
-    if ((n_mask > 0 && (!mask || ((uintptr_t)mask & 15))) || (n_eps > 0 && !eps) || n_mask < 0 || n_eps < 0 || n_mask + n_eps == 0 ||
-        keep_prob < 0.f || keep_prob > 1.f || (advance && !offset_dev)) return MMVAE_ERR_ARG;
-    const uint64_t used = (uint64_t)((n_mask + 15) / 16 * 4 + (n_eps + 3) / 4);       // counter values this call consumes
-    const double t = (double)keep_prob * 4294967296.0;
-    const uint32_t thresh = t >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)t;
-    hipLaunchKernelGGL(noise_kernel, dim3(grid_for((n_mask + 15) / 16 + (n_eps + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
-                       mask, n_mask, eps, n_eps, thresh, seed, offset, offset_dev, used, advance ? 1 : 0);
+    NoiseArgs a; int grid;
+    if (!noise_args(mask, n_mask, keep_prob, eps, n_eps, seed, offset, offset_dev, advance, a, grid)) return MMVAE_ERR_ARG;
+    hipLaunchKernelGGL(noise_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+    MM_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int mmvae_step_head(const mmvae_step_head_args* a, void* stream) {
+    if (!a || !g_tuning.step_head_on) return MMVAE_ERR_ARG;
+    StepHead h{};
+    // table role (mmvae_embed_table_fwd's checks); 256-thread blocks here, every element is formed on its own
+    if (a->S < 0 || (a->S > 0 && (a->E <= 0 || a->L <= 0 || !a->emb || !a->w_mu || !a->b_mu || !a->w_lv || !a->b_lv || !a->table))) return MMVAE_ERR_ARG;
+    const int n_table = a->S > 0 ? (a->S * 2 * a->L + 255) / 256 : 0;
+    h.S = a->S; h.E = a->E; h.L = a->L; h.emb = a->emb; h.w_mu = a->w_mu; h.b_mu = a->b_mu; h.w_lv = a->w_lv; h.b_lv = a->b_lv; h.table = a->table;
+    // zero role: 16-byte vectors, grid-stride over every range; four vectors per thread and trip, at most one workgroup per CU
+    if (a->n_zero < 0 || a->n_zero > MMVAE_HEAD_ZERO_MAX) return MMVAE_ERR_ARG;
+    long n16 = 0;
+    for (int k = 0; k < a->n_zero; ++k) {
+        if (a->zero_bytes[k] < 0 || (a->zero_bytes[k] & 15) || (a->zero_bytes[k] > 0 && (!a->zero_ptr[k] || ((uintptr_t)a->zero_ptr[k] & 15)))) return MMVAE_ERR_ARG;
+        if (a->zero_bytes[k] == 0) continue;
+        h.zero[h.n_zero++] = ZeroRange{(uint4*)a->zero_ptr[k], (long)(a->zero_bytes[k] >> 4)};
+        n16 += a->zero_bytes[k] >> 4;
+    }
+    const int n_zero = n16 > 0 ? grid_for(n16, 256 * 4, NUM_CU) : 0;
+    // prep role: the stand-alone launch's (PREP_WG, n_items) grid, flattened
+    if (a->n_prep < 0 || (a->n_prep > 0 && !a->prep_items) || (long)a->n_prep * PREP_WG >= (1L << 30)) return MMVAE_ERR_ARG;
+    h.items = a->prep_items;
+    // noise role: the stand-alone launch's grid, behind the three small roles
+    int n_noise = 0;
+    if (a->n_mask != 0 || a->n_eps != 0) {
+        if (!noise_args(a->mask, a->n_mask, a->keep_prob, a->eps, a->n_eps, a->seed, a->offset, a->offset_dev, a->advance, h.noise, n_noise)) return MMVAE_ERR_ARG;
+    }
+    h.b_zero = n_table; h.b_prep = h.b_zero + n_zero; h.b_noise = h.b_prep + a->n_prep * PREP_WG;
+    const int grid = h.b_noise + n_noise;
+    if (grid == 0) return MMVAE_ERR_ARG;               // every role empty
+    hipLaunchKernelGGL(step_head_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, h);
     MM_CHECK_LAUNCH();
     return 0;
 }

@@ -24,6 +24,7 @@
 #include "mmvae_hip.h"
 #include "gemm_src.h"
 #include "gemm_tn_tile.h"
+#include "tail_riders.h"
 
 namespace mm {
 
@@ -358,12 +359,22 @@ struct TnProblem {
     const float* pro_scale; const float* pro_shift; const uint8_t* pro_mask; long ld_pro_mask; float pro_inv_keep;
 };
 struct TnGroup { TnProblem pr[MMVAE_TN_GROUP_MAX]; int n; };
+// Riders (mmvae_gemm_tn_group_riders): workgroups appended to the group's grid that run a small launch of the end of the backward
+// which neither feeds nor reads the group -- EncoderC's backward (nb_embed workgroups from block b_embed on, its own LDS image
+// inside this launch's dynamic LDS) and the loss finalisation (thread 0 of block b_loss).  Bodies: tail_riders.h.  No riders:
+// both first blocks lie past the grid.
+struct TnRiders { int b_embed, nb_embed, b_loss; EmbedBwd embed; const double* sums; float beta, gamma; const float* beta_gamma_dev; float* out5; };
 
 template <typename CT>
 __global__ __launch_bounds__(NTHREADS, 2)
-void gemm_tn_group_kernel(const TnGroup g)
+void gemm_tn_group_kernel(const TnGroup g, const TnRiders rd)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    if ((int)blockIdx.x >= rd.b_embed) {               // block-uniform
+        if ((int)blockIdx.x >= rd.b_loss) { if (threadIdx.x == 0) loss_finalize_body(rd.sums, rd.beta, rd.gamma, rd.beta_gamma_dev, rd.out5); }
+        else embed_table_bwd_body(rd.embed, (int)blockIdx.x - rd.b_embed, rd.nb_embed, (float*)smem);
+        return;
+    }
     int pi = 0;
 #pragma unroll
     for (int i = 1; i < MMVAE_TN_GROUP_MAX; ++i) if (i < g.n && (int)blockIdx.x >= g.pr[i].block0) pi = i;      // block ranges are ascending
@@ -566,8 +577,9 @@ static int tn_group_combo(const mmvae_gemm_tn_args* a) {
     return p_f32 ? 2 : -1;
 }
 
+// riders: NULL (mmvae_gemm_tn_group), or checked by mmvae_gemm_tn_group_riders except for what depends on this launch's LDS
 template <typename CT>
-static int launch_tn_group(const mmvae_gemm_tn_args* args, int n, hipStream_t st) {
+static int launch_tn_group(const mmvae_gemm_tn_args* args, int n, hipStream_t st, const mmvae_tn_riders* riders = nullptr) {
     typedef TnGeom<CT> G;
     TnGroup g; TnGroupReduce rd;
     g.n = rd.n = n;
@@ -597,7 +609,24 @@ static int launch_tn_group(const mmvae_gemm_tn_args* args, int n, hipStream_t st
     for (int i = n; i <= MMVAE_TN_GROUP_MAX; ++i) rd.first[i] = elems;
     for (int i = n; i < MMVAE_TN_GROUP_MAX; ++i) g.pr[i].block0 = 1 << 30;
     constexpr int LDS = 4 * G::MT * G::ROWB + 4096 + 4096;
-    const int rc = launch_lds<gemm_tn_group_kernel<CT>>(dim3(block), dim3(NTHREADS), LDS, st, g);
+    TnRiders rk{};
+    rk.b_embed = rk.b_loss = 1 << 30;
+    if (riders) {                                                // appended: the problems' block ranges (and their XCD balance) stay as they are
+        const mmvae_tn_riders& r = *riders;
+        rk.b_embed = block;
+        if (r.S > 0) {
+            // its LDS image lives in this launch's dynamic LDS; refused before anything is enqueued
+            if (embed_bwd_lds(r.S, r.E, r.L) > (size_t)LDS || embed_bwd_lds(r.S, r.E, r.L) > EMBED_BWD_LDS_MAX) return MMVAE_ERR_ARG;
+            rk.nb_embed = embed_bwd_blocks(r.S, r.E, r.L);
+            rk.embed = EmbedBwd{r.S, r.E, r.L, r.table_copies < 1 ? 1 : r.table_copies, r.emb, r.w_mu, r.w_lv, r.d_table,
+                                r.d_emb, r.d_w_mu, r.d_b_mu, r.d_w_lv, r.d_b_lv};
+            block += rk.nb_embed;
+        }
+        rk.b_loss = block;
+        if (r.sums) { rk.sums = r.sums; rk.beta = r.beta; rk.gamma = r.gamma; rk.beta_gamma_dev = r.beta_gamma_dev; rk.out5 = r.out5; block += 1; }
+        else rk.b_loss = 1 << 30;
+    }
+    const int rc = launch_lds<gemm_tn_group_kernel<CT>>(dim3(block), dim3(NTHREADS), LDS, st, g, rk);
     if (rc) return rc;
     hipLaunchKernelGGL(tn_group_reduce_kernel, dim3((elems + 255) / 256), dim3(256), 0, st, rd);
     MM_CHECK_LAUNCH();
@@ -606,7 +635,7 @@ static int launch_tn_group(const mmvae_gemm_tn_args* args, int n, hipStream_t st
 
 }  // namespace mm
 
-extern "C" int mmvae_gemm_tn_group(const mmvae_gemm_tn_args* args, int32_t n, void* stream) {
+static int tn_group_entry(const mmvae_gemm_tn_args* args, int32_t n, const mmvae_tn_riders* riders, void* stream) {
     if (!args || n <= 0 || n > MMVAE_TN_GROUP_MAX) return MMVAE_ERR_ARG;
     const long lim = 1L << 32;
     for (int i = 0; i < n; ++i) {
@@ -618,9 +647,20 @@ extern "C" int mmvae_gemm_tn_group(const mmvae_gemm_tn_args* args, int32_t n, vo
             if (args[j].slab == a->slab) return MMVAE_ERR_ARG;
     }
     hipStream_t st = (hipStream_t)stream;
-    if (args[0].prec == MMVAE_PREC_BF16) return mm::launch_tn_group<mm::bf16>(args, n, st);
-    if (args[0].prec == MMVAE_PREC_F32) return mm::launch_tn_group<float>(args, n, st);
+    if (args[0].prec == MMVAE_PREC_BF16) return mm::launch_tn_group<mm::bf16>(args, n, st, riders);
+    if (args[0].prec == MMVAE_PREC_F32) return mm::launch_tn_group<float>(args, n, st, riders);
     return MMVAE_ERR_ARG;
+}
+
+extern "C" int mmvae_gemm_tn_group(const mmvae_gemm_tn_args* args, int32_t n, void* stream) { return tn_group_entry(args, n, nullptr, stream); }
+
+extern "C" int mmvae_gemm_tn_group_riders(const mmvae_gemm_tn_args* args, int32_t n, const mmvae_tn_riders* r, void* stream) {
+    if (!r || !mm::g_tuning.tn_riders_on) return MMVAE_ERR_ARG;
+    if (r->S < 0 || (r->S == 0 && !r->sums)) return MMVAE_ERR_ARG;                       // no rider named
+    if (r->S > 0 && (r->E <= 0 || r->L <= 0 || !r->emb || !r->w_mu || !r->w_lv || !r->d_table || !r->d_emb || !r->d_w_mu || !r->d_b_mu ||
+                     !r->d_w_lv || !r->d_b_lv)) return MMVAE_ERR_ARG;                    // mmvae_embed_table_bwd's checks
+    if (r->sums && !r->out5) return MMVAE_ERR_ARG;                                       // mmvae_loss_finalize's
+    return tn_group_entry(args, n, r, stream);
 }
 
 namespace mm {

@@ -63,6 +63,26 @@ class GemmTnArgs(C.Structure):
                 ("p_sum_d", vp), ("p_sum_dx", vp), ("p_gamma", vp), ("p_dgamma", vp), ("p_dbeta", vp), ("p_eval_mode", i32)]
 
 
+class TnRiders(C.Structure):
+    _fields_ = [("S", i32), ("E", i32), ("L", i32), ("table_copies", i32),
+                ("emb", vp), ("w_mu", vp), ("w_lv", vp), ("d_table", vp),
+                ("d_emb", vp), ("d_w_mu", vp), ("d_b_mu", vp), ("d_w_lv", vp), ("d_b_lv", vp),
+                ("sums", vp), ("beta", f32), ("gamma", f32), ("beta_gamma_dev", vp), ("out5", vp)]
+
+
+HEAD_ZERO_MAX = 4       # MMVAE_HEAD_ZERO_MAX
+
+
+class StepHeadArgs(C.Structure):
+    _fields_ = [("S", i32), ("E", i32), ("L", i32), ("n_zero", i32),
+                ("emb", vp), ("w_mu", vp), ("b_mu", vp), ("w_lv", vp), ("b_lv", vp), ("table", vp),
+                ("zero_ptr", vp * HEAD_ZERO_MAX), ("zero_bytes", i64 * HEAD_ZERO_MAX),
+                ("prep_items", vp), ("n_prep", i32),
+                ("advance", i32),
+                ("mask", vp), ("n_mask", i64), ("eps", vp), ("n_eps", i64),
+                ("seed", C.c_uint64), ("offset", C.c_uint64), ("offset_dev", vp), ("keep_prob", f32), ("pad_", i32)]
+
+
 class ScaleItem(C.Structure):
     _fields_ = [("x", vp), ("n", i64), ("dtype", i32), ("pad_", i32)]
 
@@ -225,6 +245,8 @@ _SIGNATURES = {
     "mmvae_gemm_nt": [C.POINTER(GemmNtArgs), vp],
     "mmvae_gemm_tn": [C.POINTER(GemmTnArgs), vp],
     "mmvae_gemm_tn_group": [vp, i32, vp],
+    "mmvae_gemm_tn_group_riders": [vp, i32, C.POINTER(TnRiders), vp],
+    "mmvae_step_head": [C.POINTER(StepHeadArgs), vp],
     "mmvae_bn_finalize": [C.POINTER(BnFinalizeArgs), vp],
     "mmvae_bn_eval_coeffs": [i32, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp],
     "mmvae_bn_bwd_finalize": [C.POINTER(BnBwdFinalizeArgs), vp],

@@ -87,6 +87,14 @@ class NoiseSource:
 
     def draw(self, B, widths, Ld, device):
         """-> ([uint8 (B,w) keep-mask for w in widths], eps fp32 (B,Ld) or None if Ld is None)."""
+        masks, eps, launch = self.plan(B, widths, Ld, device)
+        if launch is not None:
+            ops.noise(*launch)                           # the launch advances the device offset itself
+        return masks, eps
+
+    def plan(self, B, widths, Ld, device):
+        """draw() without its launch -> (masks, eps, ops.noise()'s arguments): the caller issues the launch, alone or as a role of
+        ops.step_head.  Injected arrays need none: the third result is then None."""
         if self._injected is not None:
             masks = []
             for w in widths:
@@ -100,7 +108,7 @@ class NoiseSource:
                 if tuple(eps.shape) != (B, Ld):
                     raise ValueError(f"injected eps shape {tuple(eps.shape)} != {(B, Ld)}")
                 eps = eps.to(device=device, dtype=torch.float32).contiguous()
-            return masks, eps
+            return masks, eps, None
         segs, total = [], 0
         for w in widths:
             segs.append(total)
@@ -108,8 +116,7 @@ class NoiseSource:
         buf = torch.empty(total, dtype=torch.uint8, device=device) if total else None
         eps = torch.empty(B, Ld, dtype=torch.float32, device=device) if Ld is not None else None
         off = self.offset_tensor(device)
-        ops.noise(buf, eps, 1.0 - DROP_P, self._seed(), 0, off, advance=True)        # the launch advances the device offset itself
-        return [buf[o:o + B * w].view(B, w) for o, w in zip(segs, widths)], eps
+        return [buf[o:o + B * w].view(B, w) for o, w in zip(segs, widths)], eps, (buf, eps, 1.0 - DROP_P, self._seed(), 0, off, True)
 
 
 GLOBAL_NOISE = NoiseSource()
@@ -138,14 +145,16 @@ def _check_input(x, name, cols, prec):
     return x
 
 
-def zeros_pack(device, specs):
-    """[(numel, dtype)] -> zero-filled tensors carved out of ONE allocation (one memset launch instead of one per tensor)."""
+def zeros_pack(device, specs, fill=True):
+    """[(numel, dtype)] -> zero-filled tensors carved out of ONE allocation (one memset launch instead of one per tensor).
+    fill=False: allocated only -> (tensors, the allocation): the caller zeroes it (a role of ops.step_head)."""
     offs, total = [], 0
     for n, dt in specs:
         offs.append(total)
         total += ceil_to(n * _ITEMSIZE[dt], 16)
-    buf = torch.zeros(max(total, 16), dtype=torch.uint8, device=device)
-    return [buf[o:o + n * _ITEMSIZE[dt]].view(dt) for o, (n, dt) in zip(offs, specs)]
+    buf = (torch.zeros if fill else torch.empty)(max(total, 16), dtype=torch.uint8, device=device)
+    out = [buf[o:o + n * _ITEMSIZE[dt]].view(dt) for o, (n, dt) in zip(offs, specs)]
+    return out if fill else (out, buf)
 
 
 _ITEMSIZE = {torch.float32: 4, torch.float64: 8, torch.uint8: 1, torch.int64: 8}
@@ -168,15 +177,18 @@ class PrepCache:
     def __init__(self):
         self.key = self.prep = None
 
-    def ensure(self, prec, device, params, build):
-        """params: the parameters; build(prec, device) -> their PreparedLinears."""
+    def ensure(self, prec, device, params, build, run=True):
+        """params: the parameters; build(prec, device) -> their PreparedLinears.  run=False: no launch -> the ops.WeightPrep (or
+        None) for the caller to run, alone or as a role of ops.step_head -- on every call all the same: the masters may have
+        been rewritten in place since the last one."""
         key = (prec, str(device)) + tuple(p.data_ptr() for p in params)
         if key != self.key:
             pls = build(prec, device)
             self.prep = ops.WeightPrep(pls, device) if pls else None
             self.key = key
-        if self.prep is not None:
+        if run and self.prep is not None:
             self.prep.run()
+        return self.prep
 
 
 class BNState:
@@ -243,6 +255,7 @@ class StepZeros:
     arena: Optional[torch.Tensor]       # flat fp32 gradient arena (param_list() order)
     bwd_stats: list                     # per BN layer: float64 (2, width) sums of the BatchNorm backward
     d_table: Optional[torch.Tensor]     # (copies, sites, 2 * latent): the EncoderC table gradient, summed over the copies in its backward
+    unfilled: Optional[torch.Tensor] = None     # zero_pack(fill=False): the whole allocation, still to be zeroed by the caller
 
 
 @dataclass(slots=True, eq=False)
@@ -263,6 +276,8 @@ class StepState:
     fused: Optional[FusedRecon] = None
     loss_grads: Optional[LossGrads] = None
     class_tail: Optional[ClassTail] = None
+    tail_riders: bool = False           # VAEGraph.tail_riders at the forward: the loss leaves its finalisation to the backward
+    loss_tail: Optional[tuple] = None   # ops.loss_finalize's arguments, left by that loss for the backward's last launch
     consumed: bool = False              # the backward ran: buffers are not retained
 
 
@@ -435,16 +450,25 @@ class EmbedEncoder:
     def params(self):
         return [self.embedding.weight, self.fc_mu.weight, self.fc_mu.bias, self.fc_logvar.weight, self.fc_logvar.bias]
 
-    def table(self):
+    def table_args(self):
+        """ops.embed_table_fwd's arguments, the table (the last of them) freshly allocated."""
         emb = self.embedding.weight
         t = torch.empty(emb.shape[0], 2 * self.latent, dtype=torch.float32, device=emb.device)
-        ops.embed_table_fwd(emb, self.fc_mu.weight, self.fc_mu.bias, self.fc_logvar.weight, self.fc_logvar.bias, t)
-        return t
+        return (emb, self.fc_mu.weight, self.fc_mu.bias, self.fc_logvar.weight, self.fc_logvar.bias, t)
+
+    def table(self):
+        args = self.table_args()
+        ops.embed_table_fwd(*args)
+        return args[-1]
+
+    def backward_args(self, d_table, grads):
+        """ops.embed_table_bwd's arguments."""
+        return (self.embedding.weight, self.fc_mu.weight, self.fc_logvar.weight, d_table,
+                grads[self.embedding.weight], grads[self.fc_mu.weight], grads[self.fc_mu.bias],
+                grads[self.fc_logvar.weight], grads[self.fc_logvar.bias])
 
     def backward(self, d_table, grads):
-        ops.embed_table_bwd(self.embedding.weight, self.fc_mu.weight, self.fc_logvar.weight, d_table,
-                            grads[self.embedding.weight], grads[self.fc_mu.weight], grads[self.fc_mu.bias],
-                            grads[self.fc_logvar.weight], grads[self.fc_logvar.bias])
+        ops.embed_table_bwd(*self.backward_args(d_table, grads))
 
 
 class DecoderMLP:
@@ -560,6 +584,10 @@ class VAEGraph:
         # Training-step fusion (mmvae.graphs): the caller hands the class logits straight to fused_loss and never reads them, so the
         # next forward may leave the class decoder's last Linear to the loss (ClassTail).  Off, the forward returns real logits.
         self.defer_class_head = False
+        # Training-step fusion (mmvae.graphs): the caller reads the loss values only after the backward, so the loss may leave its
+        # finalisation to the backward, whose last grouped dW launch carries it and EncoderC's backward as riders
+        # (ops.gemm_tn_group).  Off, the loss finalises itself and EncoderC's backward is a launch of its own.
+        self.tail_riders = False
 
     def _late_decoder_params(self):
         """Decoder tensors whose dW GEMM is small-output (latent / class widths: the decoders' first layers, DecoderC): they are
@@ -606,22 +634,24 @@ class VAEGraph:
             pls.append(self.dec_stem)
         return pls
 
-    def zero_pack(self, device, has_a, has_b, has_site, fwd, bwd):
+    def zero_pack(self, device, has_a, has_b, has_site, fwd, bwd, fill=True):
         """ONE memset for what a step with these modalities needs zeroed -> StepZeros.  fwd: the forward BatchNorm sums (training);
         bwd: the flat gradient arena, the backward's BatchNorm sums and the embedding-table gradient; both: the loss accumulators
-        too (three fills before).  The half that was not asked for is empty / None."""
+        too (three fills before).  The half that was not asked for is empty / None.  fill=False: allocated only; the caller
+        zeroes StepZeros.unfilled (the head-of-step launch does)."""
         widths = (self.enc_a.widths() if has_a else []) + (self.enc_b.widths() if has_b else [])
         n_sums = 2 * sum(widths)                       # every layer's (2, width) float64 sums are a multiple of 16 bytes: no gaps
         n_sites = self.enc_c.embedding.weight.shape[0] if has_site else 0
         n_tab = n_sites * 2 * self.latent * L_.TABLE_COPIES
         both = fwd and bwd
-        fwd_sums, loss_sums, loss_out5, arena, bwd_sums, d_table = zeros_pack(device, [
+        packed = zeros_pack(device, [
             (n_sums if fwd else 0, torch.float64),
             (5 if both else 0, torch.float64),
             (5 if both else 0, torch.float32),
             (sum(p.numel() for p in self.param_list()) if bwd else 0, torch.float32),
             (n_sums if bwd else 0, torch.float64),
-            (max(n_tab, 1) if bwd else 0, torch.float32)])
+            (max(n_tab, 1) if bwd else 0, torch.float32)], fill)
+        (fwd_sums, loss_sums, loss_out5, arena, bwd_sums, d_table), unfilled = packed if not fill else (packed, None)
 
         def per_layer(sums):
             return [t.view(2, -1) for t in sums.split([2 * w for w in widths])]
@@ -629,7 +659,8 @@ class VAEGraph:
                          loss_ws=(loss_sums, loss_out5) if both else None,
                          arena=arena if bwd else None,
                          bwd_stats=per_layer(bwd_sums) if bwd else [],
-                         d_table=d_table[:n_tab].view(-1, n_sites, 2 * self.latent) if bwd and has_site else None)
+                         d_table=d_table[:n_tab].view(-1, n_sites, 2 * self.latent) if bwd and has_site else None,
+                         unfilled=unfilled)
 
     def forward(self, prec, xa, xb, site, train, want_bwd=False):
         """Returns (outs(list, fp32), mu, logvar, state).  want_bwd: a backward will follow (training only) -- decided by the caller
@@ -644,17 +675,38 @@ class VAEGraph:
     def _forward(self, prec, xa, xb, site, train, want_bwd):
         ref = xa if xa is not None else (xb if xb is not None else site)
         dev, B = ref.device, ref.shape[0]
-        self._prep.ensure(prec, dev, self.param_list(), self._prepare)
-        state = StepState(prec, B, train)
+        state = StepState(prec, B, train, tail_riders=self.tail_riders and want_bwd)
         heads_a = heads_b = table = None
         Ld = self.latent
         widths_a = self.enc_a.widths() if (train and xa is not None) else []
         widths_b = self.enc_b.widths() if (train and xb is not None) else []
         n_a = len(widths_a)
-        masks, eps = self.noise.draw(B, widths_a + widths_b, Ld, dev)       # eps is sampled in eval mode too (vae.py:73)
-        # ONE memset for everything this step needs zeroed: forward BatchNorm sums, the loss accumulators, and -- when a backward will
+        # A training forward begins with four launches that depend on nothing of the step -- the weight preparation, the Philox
+        # noise, the step's one memset and EncoderC's table -- of which only the noise has real work: ONE launch
+        # (ops.step_head), its arguments collected here.  The weights are prepared at the HEAD of every step, from the masters as
+        # they are then: a caller may rewrite parameters in place between two replays of a captured step (a checkpoint restore).
+        prep = self._prep.ensure(prec, dev, self.param_list(), self._prepare, run=False)
+        masks, eps, noise_launch = self.noise.plan(B, widths_a + widths_b, Ld, dev)       # eps is sampled in eval mode too (vae.py:73)
+        head = train and noise_launch is not None      # eval mode, injected noise: the launches as they were
+        # ONE fill for everything this step needs zeroed: forward BatchNorm sums, the loss accumulators, and -- when a backward will
         # follow -- the flat gradient arena with the backward's BatchNorm sums and embedding-table gradient (three fills before)
-        zeros = self.zero_pack(dev, xa is not None, xb is not None, site is not None, fwd=True, bwd=want_bwd) if train else None
+        zeros = self.zero_pack(dev, xa is not None, xb is not None, site is not None, fwd=True, bwd=want_bwd, fill=not head) if train else None
+        table_args = self.enc_c.table_args() if site is not None else None
+        if head:
+            try:
+                ops.step_head(noise_launch, prep, [zeros.unfilled], table_args)
+                table = table_args[-1] if table_args is not None else None
+            except L_.MMVAEArgError:                   # refused before anything was enqueued: the four launches, as before
+                head = False
+        if not head:
+            if prep is not None:
+                prep.run()
+            if noise_launch is not None:
+                ops.noise(*noise_launch)
+            if zeros is not None and zeros.unfilled is not None:
+                zeros.unfilled.zero_()
+        if zeros is not None:
+            zeros.unfilled = None
         if want_bwd:
             state.zeros = zeros
         # With merged decoder first layers in bf16 mode the encoders stop before their heads: heads, fusion, reparameterisation and the
@@ -676,7 +728,9 @@ class VAEGraph:
             if site.dtype != torch.int64:
                 site = site.long()
             site = site.contiguous()
-            table = self.enc_c.table()
+            if table is None:                          # not made by the head launch
+                ops.embed_table_fwd(*table_args)
+                table = table_args[-1]
             state.site = site
         mu = torch.empty(B, Ld, dtype=torch.float32, device=dev)
         logvar = torch.empty(B, Ld, dtype=torch.float32, device=dev)
@@ -779,11 +833,14 @@ class VAEGraph:
                 return
             ops.gemm_tn(prec_, p, q, dw, db, N, K, q_prologue=q_prologue, p_prologue=p_prologue, slab=slab, tag=tag)
 
-        def flush_tiny(tag):
+        def flush_tiny(tag, riders=None):
+            """-> whether `riders` rode in the grouped launch."""
+            rode = False
             if tiny:
                 need = ops.TN_GROUP_SPLITS * sum(t_["N"] * t_["K"] for t_ in tiny)
-                ops.gemm_tn_group(prec, tiny, torch.empty(need, dtype=torch.float32, device=dev), tag=tag)
+                rode = ops.gemm_tn_group(prec, tiny, torch.empty(need, dtype=torch.float32, device=dev), tag=tag, riders=riders)
                 tiny.clear()
+            return rode
         stem = self.dec_stem if all(g is not None for g in g_outs) else None      # every decoder must fill its slice
         D0, off = None, 0
         tail = state.class_tail
@@ -822,9 +879,23 @@ class VAEGraph:
             self.enc_a.backward(prec, state.enc_a, d_heads, grads, tn, zeros.bwd_stats[:n_a], train=state.train, d_heads_lp=d_heads_lp)
         if state.enc_b is not None:
             self.enc_b.backward(prec, state.enc_b, d_heads, grads, tn, zeros.bwd_stats[n_a:], train=state.train, d_heads_lp=d_heads_lp)
-        if site is not None:
-            self.enc_c.backward(zeros.d_table, grads)
-        flush_tiny("tiny_dW.heads")
+        # EncoderC's backward (it reads the table gradient the fusion backward scattered, and writes EncoderC's gradients only) and
+        # the loss finalisation the loss left behind have nothing to do with the grouped dW launch that ends the backward: with
+        # tail_riders they run as extra workgroups of it.  Without, where there is no such launch, or where the library refuses
+        # (nothing enqueued), they are the launches of their own they were.
+        embed_bwd = self.enc_c.backward_args(zeros.d_table, grads) if site is not None else None
+        loss_tail, state.loss_tail = state.loss_tail, None
+        riders = ops.tn_riders(embed_bwd, loss_tail) if (state.tail_riders and (embed_bwd is not None or loss_tail is not None)) else None
+        if riders is None and embed_bwd is not None:
+            ops.embed_table_bwd(*embed_bwd)
+        rode = flush_tiny("tiny_dW.heads", riders)
+        if riders is not None and not rode:
+            if embed_bwd is not None:
+                ops.embed_table_bwd(*embed_bwd)
+            if loss_tail is not None:
+                ops.loss_finalize(*loss_tail)
+        elif riders is None and loss_tail is not None:
+            ops.loss_finalize(*loss_tail)
         if self.grad_sync is not None:
             self.grad_sync.final(flat)
         return flat, grads

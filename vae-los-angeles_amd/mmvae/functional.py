@@ -294,7 +294,12 @@ def _fused_loss(terms, beta, gamma, class_weights=None, unit_grad=False, beta_ga
             ops.vae_loss(B, recon_a=ra_, a=a_, recon_b=rb_, b=b_, logits=lg_, site=site, class_weights=cw, mu=mu_, logvar=lv_,
                          beta=beta, gamma=gamma, sums=sums, g_a=ga, g_b=gb, grad_b_wrt_logit=True, g_c=gc, g_mu=g_mu, g_lv=g_lv,
                          beta_gamma_dev=beta_gamma_dev)
-        ops.loss_finalize(sums, beta, gamma, out4, beta_gamma_dev)
+        if state.tail_riders and unit_grad:
+            # the captured step reads out4 only after its backward: the finalisation rides in the backward's last launch
+            # (engine.VAEGraph._backward), or is launched there; until then out4 holds nothing
+            state.loss_tail = (sums, beta, gamma, out4, beta_gamma_dev)
+        else:
+            ops.loss_finalize(sums, beta, gamma, out4, beta_gamma_dev)
         if g_mu is None:                       # KL term absent: nothing flows into mu/logvar from this loss
             g_mu = torch.zeros(B, state.logvar.shape[1], dtype=torch.float32, device=dev)
             g_lv = torch.zeros_like(g_mu)

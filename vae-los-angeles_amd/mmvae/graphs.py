@@ -94,6 +94,7 @@ class GraphedTrainStep:
         # last GEMMs (engine.VAEGraph.fused_recon) instead of writing them as fp32 and reading them back with their targets.
         g = self.model._graph()
         try:
+            g.tail_riders = True                        # nor at the loss values before the backward is done (losses(), out4)
             if self.kind == "multimodal":
                 g.fused_recon = [self.a, self.b, None]
                 g.defer_class_head = True               # nor at the class logits: the loss makes them (ops.class_tail)
@@ -110,6 +111,7 @@ class GraphedTrainStep:
         finally:
             g.fused_recon = None
             g.defer_class_head = False
+            g.tail_riders = False
         return F_.fused_loss(terms, self.beta, self.gamma, self.class_weights, unit_grad=True, beta_gamma_dev=self.hyper)
 
     def run_eager(self):

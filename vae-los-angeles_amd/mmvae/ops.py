@@ -255,8 +255,11 @@ class WeightPrep:
         host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
         self.table = host.to(device)
 
+    def nbytes(self):
+        return sum(6 * w.numel() for pl in self.linears for w in pl.srcs)
+
     def run(self):
-        with stream_span("prep_weights", lambda: sum(6 * w.numel() for pl in self.linears for w in pl.srcs)):
+        with stream_span("prep_weights", self.nbytes):
             L.check(L.load().mmvae_prep_weights(self.table.data_ptr(), self.n, _stream()), "mmvae_prep_weights")
 
 
@@ -373,10 +376,31 @@ def _tn_args(prec, p, q, dw, db, N, K, q_prologue, p_prologue, nsplit, slab):
 TN_GROUP_SPLITS = 256        # MMVAE_TN_GROUP_SPLITS: most batch splits a problem of a grouped launch can get (slab sizing)
 
 
-def gemm_tn_group(prec, problems, slab, tag="tiny_dW.group"):
+def tn_riders(embed_bwd=None, loss=None):
+    """-> TnRiders of mmvae_gemm_tn_group_riders.  embed_bwd: embed_table_bwd's arguments (a tuple); loss: loss_finalize's
+    (sums, beta, gamma, out5, beta_gamma_dev)."""
+    r = L.TnRiders()
+    if embed_bwd is not None:
+        emb, w_mu, w_lv, d_table, d_emb, d_w_mu, d_b_mu, d_w_lv, d_b_lv = embed_bwd
+        r.S, r.E, r.L = emb.shape[0], emb.shape[1], w_mu.shape[0]
+        r.table_copies = d_table.shape[0] if d_table.dim() == 3 else 1
+        r.emb, r.w_mu, r.w_lv, r.d_table = emb.data_ptr(), w_mu.data_ptr(), w_lv.data_ptr(), d_table.data_ptr()
+        r.d_emb, r.d_w_mu, r.d_b_mu, r.d_w_lv, r.d_b_lv = (t.data_ptr() for t in (d_emb, d_w_mu, d_b_mu, d_w_lv, d_b_lv))
+    if loss is not None:
+        sums, beta, gamma, out5, beta_gamma_dev = loss
+        assert sums.dtype == torch.float64 and sums.numel() >= 5 and out5.numel() >= 5
+        r.sums, r.beta, r.gamma, r.beta_gamma_dev, r.out5 = sums.data_ptr(), beta, gamma, _p(beta_gamma_dev), out5.data_ptr()
+    return r
+
+
+def gemm_tn_group(prec, problems, slab, tag="tiny_dW.group", riders=None):
     """problems: list of dicts(p, q, dw, db, N, K, q_prologue=None): SMALL-output dW GEMMs (latent / class widths) launched as
-    ONE grouped GEMM + ONE reduce.  `slab`: fp32 workspace carved into one region per problem."""
+    ONE grouped GEMM + ONE reduce.  `slab`: fp32 workspace carved into one region per problem.
+    riders: a TnRiders (tn_riders()) whose work runs as extra workgroups of the first grouped launch.  Returns whether it did: the
+    library refuses riders it cannot carry with nothing enqueued, the group then runs without them and the caller issues their
+    stand-alone launches."""
     lib = L.load()
+    rode = False
     for i in range(0, len(problems), L.TN_GROUP_MAX):
         chunk = problems[i:i + L.TN_GROUP_MAX]
         arr = (L.GemmTnArgs * len(chunk))()
@@ -389,6 +413,12 @@ def gemm_tn_group(prec, problems, slab, tag="tiny_dW.group"):
             off += need
             nbytes += pr["p"].shape[0] * (pr["N"] * pr["p"].element_size() + pr["K"] * pr["q"].element_size()) + 4 * pr["N"] * pr["K"]
         with stream_span(tag if i == 0 else f"{tag}.{i}", nbytes):
+            if i == 0 and riders is not None:
+                status = lib.mmvae_gemm_tn_group_riders(C.cast(arr, C.c_void_p), len(chunk), C.byref(riders), _stream())
+                if status != -1:
+                    L.check(status, "mmvae_gemm_tn_group_riders")
+                    rode = True
+                    continue
             status = lib.mmvae_gemm_tn_group(C.cast(arr, C.c_void_p), len(chunk), _stream())
             if status == -1:
                 # a problem outside the grouped kernel's operand combinations (odd widths / alignments): the entry point checks
@@ -397,6 +427,7 @@ def gemm_tn_group(prec, problems, slab, tag="tiny_dW.group"):
                     L.check(lib.mmvae_gemm_tn(C.byref(arr[j]), _stream()), "mmvae_gemm_tn")
             else:
                 L.check(status, "mmvae_gemm_tn_group")
+    return rode
 
 
 def gemm_tn(prec, p, q, dw, db, N, K, *, q_prologue=None, p_prologue=None, nsplit=0, slab=None, tag=None):
@@ -661,6 +692,41 @@ def noise(mask, eps, keep_prob, seed, offset, offset_dev=None, advance=False):
     with stream_span("noise", n_mask + 4 * n_eps):
         L.check(L.load().mmvae_noise(_p(mask), n_mask, keep_prob, _p(eps), n_eps, seed, offset, _p(offset_dev), int(advance), _stream()), "mmvae_noise")
     return (n_mask + 15) // 16 * 4 + (n_eps + 3) // 4
+
+
+def step_head(noise_args=None, prep=None, zero=(), table_args=None):
+    """mmvae_step_head: the four independent launches a training forward begins with, as one.  noise_args: noise()'s positional
+    arguments (mask, eps, keep_prob, seed, offset, offset_dev, advance); prep: a WeightPrep; zero: uint8 tensors to fill with zeros
+    (16-byte aligned, a multiple of 16 bytes each); table_args: embed_table_fwd()'s arguments.  Any of them may be absent.  Raises
+    MMVAEArgError, with nothing enqueued, where the library refuses: the caller then issues the four launches."""
+    a = L.StepHeadArgs()
+    nbytes = 0
+    if noise_args is not None:
+        mask, eps, keep_prob, seed, offset, offset_dev, advance = noise_args
+        a.mask, a.n_mask = _p(mask), 0 if mask is None else mask.numel()
+        a.eps, a.n_eps = _p(eps), 0 if eps is None else eps.numel()
+        if advance:
+            assert offset_dev is not None and offset_dev.numel() == L.CTR_COPIES and offset_dev.dtype == torch.int64
+        a.keep_prob, a.seed, a.offset, a.offset_dev, a.advance = keep_prob, seed, offset, _p(offset_dev), int(advance)
+        nbytes += a.n_mask + 4 * a.n_eps
+    if prep is not None:
+        a.prep_items, a.n_prep = prep.table.data_ptr(), prep.n
+        nbytes += prep.nbytes()
+    zero = [z for z in zero if z is not None and z.numel()]
+    if len(zero) > L.HEAD_ZERO_MAX:
+        raise L.MMVAEArgError(f"step_head: more than {L.HEAD_ZERO_MAX} zero ranges")
+    a.n_zero = len(zero)
+    for k, z in enumerate(zero):
+        assert z.is_contiguous()
+        a.zero_ptr[k], a.zero_bytes[k] = z.data_ptr(), z.numel() * z.element_size()
+        nbytes += a.zero_bytes[k]
+    if table_args is not None:
+        emb, w_mu, b_mu, w_lv, b_lv, table = table_args
+        a.S, a.E, a.L = emb.shape[0], emb.shape[1], w_mu.shape[0]
+        a.emb, a.w_mu, a.b_mu, a.w_lv, a.b_lv, a.table = (t.data_ptr() for t in table_args)
+        nbytes += 4 * (emb.numel() + w_mu.numel() + w_lv.numel() + b_mu.numel() + b_lv.numel() + table.numel())
+    with stream_span("step_head", nbytes):
+        L.check(L.load().mmvae_step_head(C.byref(a), _stream()), "mmvae_step_head")
 
 
 def dropout_mask(mask, keep_prob, seed, offset):
