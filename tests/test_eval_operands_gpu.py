@@ -1,7 +1,8 @@
 """What the evaluation wrappers of mmvae.ops refuse in Python, before any launch: one table of malformed calls per wrapper (a transposed
 view, rows that overlap, a wrong dtype, a wrong width, outputs of the wrong shape or stride, a short workspace, k / splits out of range,
-misaligned LayerNorm operands) and the exception type each raises.  Operands are at most 8 x 8 (33 x 8 where the LayerNorm backward
-must need a workspace); a call that got as far as asking for the launch stream fails the test, whatever it raises."""
+misaligned LayerNorm operands) and the exception type each raises.  Operands are at most 8 x 8 (more rows only where an entry must need a
+workspace to be given a short one: 33 x 8 for the LayerNorm backward and two row splits of the scatter matrix, 5000 training rows for
+the split lists of the manhattan search); a call that got as far as asking for the launch stream fails the test, whatever it raises."""
 import functools
 import types
 
@@ -90,7 +91,7 @@ def recon_metrics_cases(g):
             ("row_cosine_stride", ValueError, lambda: f(g.x, g.t, g.shift, g.col_acc, g.vec, every_other(8)))]
 
 
-def _search_cases(f, dist_name, with_shift):
+def _search_cases(f, dist_name, with_shift, work_bytes):
     def cases(g):
         out = [("q_transposed", ValueError, lambda: f(transposed(8, 8), g.t, 5)),
                ("q_expanded", ValueError, lambda: f(expanded(8, 8), g.t, 5)),
@@ -109,13 +110,34 @@ def _search_cases(f, dist_name, with_shift):
                ("idx_out_expanded", ValueError, lambda: f(g.x, g.t, 5, idx_out=expanded(8, 5, I32))),
                ("dist_out_shape", ValueError, lambda: f(g.x, g.t, 5, **{dist_name: z(7, 5)})),
                ("dist_out_dtype", ValueError, lambda: f(g.x, g.t, 5, **{dist_name: z(8, 5, dt=F64)})),
-               ("dist_out_inner_stride", ValueError, lambda: f(g.x, g.t, 5, **{dist_name: inner2(8, 5)}))]
+               ("dist_out_inner_stride", ValueError, lambda: f(g.x, g.t, 5, **{dist_name: inner2(8, 5)})),
+               # 3 queries among 5000 rows: the training rows are split and both searches need a workspace for the lists
+               ("work_short", ValueError, lambda: f(z(3, 8), z(5000, 8), 5, work=_short(work_bytes(3, 5000, 5)))),
+               ("work_dtype", ValueError, lambda: f(g.x, g.t, 5, work=z(1024, dt=I32))),
+               ("work_strided", ValueError, lambda: f(g.x, g.t, 5, work=every_other(1024, I64)))]
         if with_shift:
             out += [("shift_length", ValueError, lambda: f(g.x, g.t, 5, z(7))),
                     ("shift_dtype", ValueError, lambda: f(g.x, g.t, 5, z(8, dt=BF16))),
                     ("shift_stride", ValueError, lambda: f(g.x, g.t, 5, every_other(8)))]
         return out
     return cases
+
+
+def knn_search_grouped_cases(g):
+    f = ops.knn_search_grouped
+    codes = (z(8, dt=I32), z(8, dt=I32))
+    return [("no_codes", ValueError, lambda: f(g.x, g.t, 5)),
+            ("metric", ValueError, lambda: f(g.x, g.t, 5, differ=codes, metric="cosine")),
+            ("half_a_pair", ValueError, lambda: f(g.x, g.t, 5, same=(codes[0],))),
+            ("codes_length", ValueError, lambda: f(g.x, g.t, 5, differ=(codes[0], z(7, dt=I32)))),
+            ("codes_dtype", ValueError, lambda: f(g.x, g.t, 5, same=(z(8, dt=I64), codes[1]))),
+            ("manhattan_shift", ValueError, lambda: f(g.x, g.t, 5, differ=codes, metric="manhattan", shift=g.shift)),
+            ("k_above_rows", ValueError, lambda: f(g.x, g.t, 9, differ=codes)),
+            ("t_cols", ValueError, lambda: f(g.x, z(8, 7), 5, differ=codes)),
+            ("work_short_euclidean", ValueError, lambda: f(g.x, g.t, 5, differ=codes, work=_short(ops.knn_group_work_bytes(8, 8, 5)))),
+            ("work_short_manhattan", ValueError,
+             lambda: f(g.x, g.t, 5, same=codes, metric="manhattan", work=_short(ops.knn_group_work_bytes(8, 8, 5, "manhattan")))),
+            ("work_dtype", ValueError, lambda: f(g.x, g.t, 5, differ=codes, work=z(1024, dt=I32)))]
 
 
 def _rows_cases(f, weighted):
@@ -159,7 +181,10 @@ def silhouette_cases(g):
             ("splits_negative", ValueError, lambda: f(g.x, g.order, g.class_start, splits=-1)),
             ("s_out_length", ValueError, lambda: f(g.x, g.order, g.class_start, s_out=z(7))),
             ("intra_out_dtype", ValueError, lambda: f(g.x, g.order, g.class_start, intra_out=z(8, dt=F64))),
-            ("inter_out_stride", ValueError, lambda: f(g.x, g.order, g.class_start, inter_out=every_other(8)))]
+            ("inter_out_stride", ValueError, lambda: f(g.x, g.order, g.class_start, inter_out=every_other(8))),
+            ("work_short", ValueError, lambda: f(g.x, g.order, g.class_start, work=_short(ops.silhouette_work_bytes(8, 2)))),
+            ("work_short_split", ValueError, lambda: f(g.x, g.order, g.class_start, splits=2, work=_short(ops.silhouette_work_bytes(8, 2, 2)))),
+            ("work_dtype", ValueError, lambda: f(g.x, g.order, g.class_start, work=z(1024, dt=I32)))]
 
 
 def pca_scatter_cases(g):
@@ -174,7 +199,10 @@ def pca_scatter_cases(g):
             ("out_shape", ValueError, lambda: f(g.x, g.shift, out=z(8, 7))),
             ("out_dtype", ValueError, lambda: f(g.x, g.shift, out=z(8, 8, dt=F64))),
             ("out_inner_stride", ValueError, lambda: f(g.x, g.shift, out=inner2(8, 8))),
-            ("out_expanded", ValueError, lambda: f(g.x, g.shift, out=expanded(8, 8)))]
+            ("out_expanded", ValueError, lambda: f(g.x, g.shift, out=expanded(8, 8))),
+            # 33 rows are two chunks of 32: the fewest at which two row splits, and with them a workspace, exist
+            ("work_short", ValueError, lambda: f(z(33, 8), g.shift, 2, work=_short(ops.pca_scatter_work_bytes(33, 8, 2)))),
+            ("work_dtype", ValueError, lambda: f(g.x, g.shift, work=z(1024, dt=I32)))]
 
 
 def pca_project_cases(g):
@@ -312,8 +340,9 @@ def wce_mean_cases(g):
 
 
 TABLES = {"recon_metrics": recon_metrics_cases,
-          "knn_search": _search_cases(ops.knn_search, "dist2_out", True),
-          "knn_search_l1": _search_cases(ops.knn_search_l1, "dist_out", False),
+          "knn_search": _search_cases(ops.knn_search, "dist2_out", True, ops.knn_work_bytes),
+          "knn_search_l1": _search_cases(ops.knn_search_l1, "dist_out", False, ops.knn_l1_work_bytes),
+          "knn_search_grouped": knn_search_grouped_cases,
           "knn_mean_rows": _rows_cases(ops.knn_mean_rows, False),
           "knn_weighted_rows": _rows_cases(ops.knn_weighted_rows, True),
           "silhouette_samples": silhouette_cases,

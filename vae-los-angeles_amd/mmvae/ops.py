@@ -911,9 +911,9 @@ def knn_l1_work_bytes(Mq, Nt, k):
     return _plan("mmvae_knn_l1_work_bytes", Mq, Nt, k, outs=(C.c_int64,))
 
 
-def _knn_search(what, work_bytes, kind, q, t, k, shift, idx_out, dist_out, dist_name):
+def _knn_search(what, work_bytes, kind, q, t, k, shift, idx_out, dist_out, dist_name, work):
     """The one body of knn_search and knn_search_l1: entry point mmvae_<what>, workspace size work_bytes(Mq, Nt, k), probe kind `kind`;
-    dist_out is False for no distances, else the caller's `dist_name` or None."""
+    dist_out is False for no distances, else the caller's `dist_name` or None; work: the caller's workspace or None."""
     _operand(q, "q", what)
     Mq, F = q.shape
     _operand(t, "t", what, cols=F)
@@ -926,7 +926,7 @@ def _knn_search(what, work_bytes, kind, q, t, k, shift, idx_out, dist_out, dist_
     shift = _shift(shift, what, F, q.device)
     idx = _out_view(idx_out, "idx_out", what, torch.int32, Mq, k, q.device)
     d = None if dist_out is False else _out_view(dist_out, dist_name, what, torch.float32, Mq, k, q.device)
-    work = _workspace(work_bytes(Mq, Nt, k), q.device)
+    work = _work(work, work_bytes(Mq, Nt, k), what, q.device)
     a = L.KnnArgs(q.data_ptr(), t.data_ptr(), _p(shift), idx.data_ptr(), _p(d), _p(work), _ld(q), _ld(t), _ld(idx), _ld0(d),
                   work.numel() * 8 if work is not None else 0, Mq, Nt, F, k, _dt(q), _dt(t))
     with probe_span(what, lambda: dict(kind=kind, flops=2.0 * Mq * Nt * F, M=Mq, N=Nt, K=F)):
@@ -934,19 +934,21 @@ def _knn_search(what, work_bytes, kind, q, t, k, shift, idx_out, dist_out, dist_
     return idx, d
 
 
-def knn_search(q, t, k, shift=None, dist2=True, *, idx_out=None, dist2_out=None):
+def knn_search(q, t, k, shift=None, dist2=True, *, idx_out=None, dist2_out=None, work=None):
     """The k nearest training rows (euclidean) of every query row (mmvae_knn_search): idx int32 (Mq, k) ascending by (distance key,
     training index), and the squared distances fp32 (Mq, k) unless dist2 is False (then None).  q (Mq, F), t (Nt, F): fp32 or bf16,
     unit inner stride, any row stride (padded bf16 rows included).  shift (F,) fp32 is subtracted from both operands on load (pass the
-    training column means: the distances do not change, their rounding does).  idx_out / dist2_out: write into these (views allowed)."""
-    return _knn_search("knn_search", knn_work_bytes, "gemm", q, t, k, shift, idx_out, dist2_out if dist2 else False, "dist2_out")
+    training column means: the distances do not change, their rounding does).  idx_out / dist2_out: write into these (views allowed).
+    work: a workspace to use (an int64 tensor of at least knn_work_bytes(Mq, Nt, k) bytes, any contents)."""
+    return _knn_search("knn_search", knn_work_bytes, "gemm", q, t, k, shift, idx_out, dist2_out if dist2 else False, "dist2_out", work)
 
 
-def knn_search_l1(q, t, k, dist=True, *, idx_out=None, dist_out=None):
+def knn_search_l1(q, t, k, dist=True, *, idx_out=None, dist_out=None, work=None):
     """The k nearest training rows of every query row under the manhattan distance (mmvae_knn_search_l1): idx int32 (Mq, k) ascending
     by (distance, training index), and the L1 distances themselves -- not squared -- fp32 (Mq, k) unless dist is False (then None).
-    Every distance is one fp32 chain of |q - t| over the columns in ascending order.  Operands as knn_search; there is no shift."""
-    return _knn_search("knn_search_l1", knn_l1_work_bytes, "valu", q, t, k, None, idx_out, dist_out if dist else False, "dist_out")
+    Every distance is one fp32 chain of |q - t| over the columns in ascending order.  Operands as knn_search; there is no shift.
+    work: a workspace to use (an int64 tensor of at least knn_l1_work_bytes(Mq, Nt, k) bytes, any contents)."""
+    return _knn_search("knn_search_l1", knn_l1_work_bytes, "valu", q, t, k, None, idx_out, dist_out if dist else False, "dist_out", work)
 
 
 _KNN_METRICS = {"euclidean": 0, "manhattan": 1}
@@ -959,12 +961,13 @@ def knn_group_work_bytes(Mq, Nt, k, metric="euclidean"):
     return _plan("mmvae_knn_group_work_bytes", Mq, Nt, k, _KNN_METRICS[metric], outs=(C.c_int64,))
 
 
-def knn_search_grouped(q, t, k, *, same=None, differ=None, metric="euclidean", shift=None, dist=True, idx_out=None, dist_out=None):
+def knn_search_grouped(q, t, k, *, same=None, differ=None, metric="euclidean", shift=None, dist=True, idx_out=None, dist_out=None, work=None):
     """knn_search (metric "euclidean": squared distances) or knn_search_l1 ("manhattan": the distances themselves) among the candidates
     a query may see (mmvae_knn_search_grouped): same = (q_codes, t_codes) admits the candidates whose code equals the query's, differ =
     (q_codes, t_codes) those whose code differs; both may be given, one must be.  Codes are int32 device vectors of Mq and Nt entries.
     Among the admitted candidates the result is, bit for bit, that of the plain search over them.  A query with c < k admitted candidates
-    gets c entries and then idx -1 / distance +inf.  Rows sorted by the `same` code let whole tiles be skipped.  There is no CPU fallback."""
+    gets c entries and then idx -1 / distance +inf.  Rows sorted by the `same` code let whole tiles be skipped.  There is no CPU fallback.
+    work: a workspace to use (an int64 tensor of at least knn_group_work_bytes(Mq, Nt, k, metric) bytes, any contents)."""
     what = "knn_search_grouped"
     if metric not in _KNN_METRICS:
         raise ValueError(f"{what}: metric must be one of {sorted(_KNN_METRICS)}, got {metric!r}")
@@ -992,7 +995,7 @@ def knn_search_grouped(q, t, k, *, same=None, differ=None, metric="euclidean", s
     shift = _shift(shift, what, F, q.device)
     idx = _out_view(idx_out, "idx_out", what, torch.int32, Mq, k, q.device)
     d = None if dist is False else _out_view(dist_out, "dist_out", what, torch.float32, Mq, k, q.device)
-    work = _workspace(knn_group_work_bytes(Mq, Nt, k, metric), q.device)
+    work = _work(work, knn_group_work_bytes(Mq, Nt, k, metric), what, q.device)
     base = L.KnnArgs(q.data_ptr(), t.data_ptr(), _p(shift), idx.data_ptr(), _p(d), _p(work), _ld(q), _ld(t), _ld(idx), _ld0(d),
                      work.numel() * 8, Mq, Nt, F, k, _dt(q), _dt(t))
     a = L.KnnGroupArgs(base, *(_p(c) for c in codes), _KNN_METRICS[metric])
@@ -1054,12 +1057,13 @@ def silhouette_work_bytes(N, n_classes, splits=0):
     return _plan("mmvae_silhouette_work_bytes", N, n_classes, splits, outs=(C.c_int64,))
 
 
-def silhouette_samples(x, order, class_start, shift=None, *, splits=0, s_out=None, intra_out=None, inter_out=None):
+def silhouette_samples(x, order, class_start, shift=None, *, splits=0, s_out=None, intra_out=None, inter_out=None, work=None):
     """Silhouette coefficient of every row of x (mmvae_silhouette_samples): (s, intra, inter), fp32 (N,) each in x's row order.
     x (N, F): fp32 or bf16, unit inner stride, any row stride (padded bf16 rows included).  order: int32 (N,) row indices grouped by
     class, or None when the rows are already grouped; class_start: int32 (C + 1,) positions, class c owns order[class_start[c] :
     class_start[c + 1]].  shift (F,) fp32 is subtracted from every element on load (pass the column means).  splits: 0 = the library's
-    choice, 1 .. 64 forces that many column splits.  *_out: write into these (views allowed)."""
+    choice, 1 .. 64 forces that many column splits.  *_out: write into these (views allowed).  work: a workspace to use (an int64 tensor
+    of at least silhouette_work_bytes(N, C, splits) bytes, any contents)."""
     what = "silhouette_samples"
     _operand(x, "x", what)
     N, F = x.shape
@@ -1075,7 +1079,7 @@ def silhouette_samples(x, order, class_start, shift=None, *, splits=0, s_out=Non
     shift = _shift(shift, what, F, dev)
     splits = _splits_arg(splits, what)
     outs = [_out_vector(o, name, what, torch.float32, N, dev, strided=True) for o, name in ((s_out, "s_out"), (intra_out, "intra_out"), (inter_out, "inter_out"))]
-    work = _workspace(silhouette_work_bytes(N, nc, splits), dev)
+    work = _work(work, silhouette_work_bytes(N, nc, splits), what, dev)
     a = L.SilhouetteArgs(x.data_ptr(), _p(shift), _p(order), class_start.data_ptr(), outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(),
                          work.data_ptr(), _ld(x), work.numel() * 8, N, F, nc, splits, _dt(x), 0)
     with probe_span("silhouette_samples", lambda: dict(kind="gemm", flops=2.0 * N * N * F, M=N, N=N, K=F)):
@@ -1095,18 +1099,19 @@ def pca_scatter_work_bytes(N, F, splits=0):
     return _plan("mmvae_pca_scatter_work_bytes", N, F, splits, outs=(C.c_int64,))
 
 
-def pca_scatter(x, shift, splits=0, out=None):
+def pca_scatter(x, shift, splits=0, out=None, *, work=None):
     """S = (x - shift)^T (x - shift), fp32 (F, F), bitwise symmetric (mmvae_pca_scatter).  x (N, F): fp32 or bf16, unit inner stride, any
     row stride (padded bf16 rows included); shift (F,) fp32 or None is subtracted from every element on load (pass the column means).
-    splits: 0 = the library's choice, 1 .. 64 forces that many row splits.  out: write into this (a view is allowed)."""
+    splits: 0 = the library's choice, 1 .. 64 forces that many row splits.  out: write into this (a view is allowed).  work: a workspace
+    to use (an int64 tensor of at least pca_scatter_work_bytes(N, F, splits) bytes, any contents)."""
     _operand(x, "x", "pca_scatter")
     N, F = x.shape
     shift = _shift(shift, "pca_scatter", F, x.device)
     splits = _splits_arg(splits, "pca_scatter")
     s = _out_view(out, "out", "pca_scatter", torch.float32, F, F, x.device)
     nbytes = pca_scatter_work_bytes(N, F, splits)
-    work = _workspace(nbytes, x.device)
-    a = L.PcaScatterArgs(x.data_ptr(), _p(shift), s.data_ptr(), _p(work), _ld(x), _ld(s), nbytes, N, F, splits, _dt(x))
+    work = _work(work, nbytes, "pca_scatter", x.device)
+    a = L.PcaScatterArgs(x.data_ptr(), _p(shift), s.data_ptr(), _p(work), _ld(x), _ld(s), work.numel() * 8 if work is not None else 0, N, F, splits, _dt(x))
     with probe_span("pca_scatter", lambda: dict(kind="gemm", flops=1.0 * N * F * F, M=F, N=F, K=N)):
         L.check(L.load().mmvae_pca_scatter(C.byref(a), _stream()), "mmvae_pca_scatter")
     return s
