@@ -49,7 +49,8 @@ int mmvae_abi_version(void);    /* bumped on any struct change; the ctypes bindi
  * (gemm_ntp.h: producer / consumer waves) on/off, key 9 = its minimum M (default 16384); key 10 = the fused latent launch
  * (mmvae_latent_fwd) on/off: off, it returns MMVAE_ERR_ARG and the caller issues the launches it replaces; key 12 = the fused class-head
  * launch (mmvae_class_tail) on/off, in the same way; key 13 = the merged head-of-step launch (mmvae_step_head) on/off and key 14 = the
- * riders of the grouped dW launch (mmvae_gemm_tn_group_riders) on/off, in the same way.  Other keys: MMVAE_ERR_ARG. */
+ * riders of the grouped dW launch (mmvae_gemm_tn_group_riders) on/off, in the same way; key 15 = the autoencoders' fused latent launch
+ * (mmvae_ae_latent_fwd) on/off, in the same way.  Other keys: MMVAE_ERR_ARG. */
 int mmvae_set_tuning(int32_t key, int32_t value);
 
 /* ---------------------------------------------------------------------------------------------
@@ -276,6 +277,46 @@ typedef struct {
 int mmvae_fuse_reparam_bwd(const mmvae_fuse_bwd_args* args, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The latent path of the non-variational baselines RNA2DNAAE / DNA2RNAAE (directional_ae.py:46-64): the encoder ends in ONE
+ * Linear(hidden, latent), the site enters through Embedding -> Linear(embed, latent), the fusion is the plain mean.
+ *
+ * mmvae_embed_proj_fwd / _bwd: the one-head case of mmvae_embed_table_fwd / _bwd (the same kernels' bodies with one head):
+ *   table[S][L] = emb[S][E] x w[L][E]^T + b   (fp32; every element accumulates from the bias over e ascending)
+ *   backward, from d_table[table_copies][S][L] (the copies are summed in fixed order): d_emb, d_w, d_b are accumulated into.
+ *   Capacity as mmvae_embed_table_bwd, for one head: MMVAE_ERR_ARG (nothing enqueued) when (S*L + S*E + L*E) * 4 bytes exceed 64 KiB.
+ *
+ * mmvae_fuse_mean_fwd:  latent = (head + table[site]) * (1 / n_mod), the sum formed in the order head, table row, multiplied only
+ *   when n_mod > 1 (one or two terms: exact after the one addition).  head: fp32 [B][ld_head] or NULL; table / site / S: the
+ *   projected table [S][L] fp32 + int64 labels, or NULL; n_mod must equal the number of modalities present (>= 1), else
+ *   MMVAE_ERR_ARG.  latent: CONTIGUOUS fp32 [B][L]; z: the same values in z_dtype (MMVAE_F32 / MMVAE_BF16) with leading dimension
+ *   ldz >= L, pad columns zeroed.  A label outside [0, S) poisons its own row with NaN and reads nothing outside the table.
+ * mmvae_fuse_mean_bwd:  d_head[B][ld_head] = (dz + g_latent) * (1 / n_mod) (g_latent: the gradient that arrived at the returned
+ *   latent, contiguous [B][L] or NULL), an optional bf16 copy d_head_lp (pad columns zeroed), and -- d_table given -- the same rows
+ *   scatter-added into d_table[w % table_copies][site[b]] by workgroup w (0 copies = 1), through LDS when S*L*4 <= 48 KiB, with
+ *   global atomics otherwise; rows with a label outside [0, S) are not scattered.
+ * ------------------------------------------------------------------------------------------- */
+int mmvae_embed_proj_fwd(int32_t S, int32_t E, int32_t L, const float* emb, const float* w, const float* b, float* table, void* stream);
+int mmvae_embed_proj_bwd(int32_t S, int32_t E, int32_t L, const float* emb, const float* w, const float* d_table, int32_t table_copies,
+                         float* d_emb, float* d_w, float* d_b, void* stream);
+typedef struct {
+    int32_t B, L, n_mod;
+    const float* head; int64_t ld_head;
+    const float* table; const int64_t* site; int32_t S;
+    float* latent;
+    void* z; int32_t z_dtype; int64_t ldz;
+} mmvae_fuse_mean_fwd_args;
+int mmvae_fuse_mean_fwd(const mmvae_fuse_mean_fwd_args* args, void* stream);
+typedef struct {
+    int32_t B, L, n_mod;
+    const float* dz; int64_t lddz;
+    const float* g_latent;
+    float* d_head; int64_t ld_head;
+    void* d_head_lp; int64_t ld_head_lp;
+    float* d_table; const int64_t* site; int32_t S; int32_t table_copies;
+} mmvae_fuse_mean_bwd_args;
+int mmvae_fuse_mean_bwd(const mmvae_fuse_mean_bwd_args* args, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The latent path of the forward in ONE launch (latent.hip): from the encoders' last PRE-BatchNorm outputs to the decoders' first
  * hidden activation, per 16-row slab without leaving the CU --
  *   per encoder present:  heads = bf16(relu(y * scale + shift) * keep * inv_keep) x Wheads^T + bias   (the arithmetic of
@@ -323,6 +364,31 @@ typedef struct {
     void* h0; int64_t ldh0;
 } mmvae_latent_fwd_args;
 int mmvae_latent_fwd(const mmvae_latent_fwd_args* args, void* stream);
+
+/* The autoencoders' latent path of the forward in ONE launch: the deterministic instantiation of mmvae_latent_fwd's kernel
+ * (latent.hip), per 16-row slab without leaving the CU --
+ *   head   = bf16(relu(y * scale + shift) * keep * inv_keep) x Wproj^T + bias   (mmvae_gemm_nt with MMVAE_PRO_BN_RELU_DROP, K ascending,
+ *            with the folded BatchNorm finalisation through enc.finalize; fp32, NOT stored)
+ *   latent = (head + table[site]) * (1 / n_mod) as mmvae_fuse_mean_fwd forms it, written as contiguous fp32 [B][L]; z: bf16, pads zeroed
+ *   h0     = bf16(relu(z x W0^T + b0))   (mmvae_gemm_nt with MMVAE_ACT_RELU on the ONE decoder's first layer)
+ * bit for bit what the three launches it replaces write.  No eps is read, no logvar written.  enc.y == NULL: the encoder is absent
+ * (site only); table == NULL: no site.  n_mod must equal the number of modalities present (>= 1).
+ * Limits, those of mmvae_latent_fwd restated for one head (anything else: MMVAE_ERR_ARG, fp32: MMVAE_ERR_DTYPE, before anything is
+ * enqueued; the caller then issues the three launches): 1 <= L <= 24, B * L < 2^31; enc: K % 32 == 0, 32 <= K <= 256 and the operand
+ * alignments of mmvae_latent_enc; the prepared head weight has at least 48 readable rows, rows >= L zero; ldz % 8 == 0, L <= ldz <= 32,
+ * z 16-byte aligned; N_stem % 64 == 0, 64 <= N_stem <= 448 (DecoderA's 128 and DecoderB's 256 fit), ldw_stem % 64 == 0, >= 32; h0 rows
+ * whole 128-byte lines (ldh0 % 64 == 0, >= N_stem, base 128-byte aligned); S * L <= 1024 with site given; row operands below 4 GiB;
+ * tuning key 15 on. */
+typedef struct {
+    int32_t prec, B, L, n_mod;
+    mmvae_latent_enc enc;
+    const float* table; const int64_t* site; int32_t S;
+    float* latent;
+    void* z; int64_t ldz;
+    const void* w_stem; int64_t ldw_stem; const float* bias_stem; int32_t N_stem;
+    void* h0; int64_t ldh0;
+} mmvae_ae_latent_fwd_args;
+int mmvae_ae_latent_fwd(const mmvae_ae_latent_fwd_args* args, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * The class head of the training step in ONE launch (class_tail.hip): the class decoder's last Linear, the weighted cross-entropy

@@ -4,6 +4,7 @@ same shuffled folds, both directions, compared with paired t-tests on Mean R2, M
 
     python cross_validate.py --folds 10 --subset 0.1 --neighbors 5 10 --epochs 200 --batch-size 32 --out cv.json
     python cross_validate.py --models mean knn --knn-by-site            # baselines only, with the site-conditioned kNN
+    python cross_validate.py --autoencoder                              # adds the non-variational AE rows and their two t-tests
 
 The folds are sklearn's KFold(folds, shuffle=True, random_state=42) and the subset is DataFrame.sample(frac, random_state=42), so a
 run on the reference's processed_data.pkl sees the reference's rows and folds.  All folds and all k of the kNN come from one
@@ -45,6 +46,8 @@ def build_parser():
     ap.add_argument("--seed", type=int, default=Config.RANDOM_SEED, help="folds, subset, VAE initialisation, noise and batch order")
     ap.add_argument("--models", nargs="+", default=["mean", "knn", "vae"], help="any of: mean knn vae")
     ap.add_argument("--knn-by-site", action="store_true", help="with knn: add the site-conditioned kNN under the same folds")
+    ap.add_argument("--autoencoder", action="store_true", help="add the non-variational baselines RNA2DNAAE / DNA2RNAAE (the reference's "
+                    "'ae' rows) under the same folds, trained with --epochs, --batch-size, --precision, --eager and --seed")
     ap.add_argument("--eager", action="store_true", help="train the VAEs with launches issued from Python instead of the captured step")
     ap.add_argument("--out", default=None, help="write the results and the comparisons as JSON here")
     return ap
@@ -70,7 +73,9 @@ def print_comparison(metric, entries):
     for e in entries:
         print(f"\nDirection: {e['direction']}")
         print(f"  Best kNN: k={e['best_knn']}   Best VAE: epochs={e['best_vae']}")
-        for key in ("vae_vs_mean", "knn_site_vs_vae", "knn_vs_vae"):
+        if "best_ae" in e:
+            print(f"  Best AE: epochs={e['best_ae']}")
+        for key in ("ae_vs_vae", "ae_vs_knn", "vae_vs_mean", "knn_site_vs_vae", "knn_vs_vae"):
             if key in e:
                 c = e[key]
                 print(f"  {c['a']} vs {c['b']}: t={c['t']:.4f}, p={c['p']:.4e}  ({metric}: {c['mean_a']:.4f} vs {c['mean_b']:.4f})")
@@ -112,7 +117,8 @@ def run(argv=None):
         from mmvae import to_bf16_rows
         rna, dna = to_bf16_rows(rna), to_bf16_rows(dna)
     fold = crossval.kfold_assignments(n, args.folds, args.seed)
-    models = [m for m in ("mean", "knn") if m in args.models] + (["knn_site"] if args.knn_by_site else []) + (["vae"] if "vae" in args.models else [])
+    models = [m for m in ("mean", "knn") if m in args.models] + (["knn_site"] if args.knn_by_site else []) \
+        + (["vae"] if "vae" in args.models else []) + ([crossval.AE_MODEL] if args.autoencoder else [])
 
     def say(r):
         label = "Mean baseline" if r["model"] == "mean" else f"{r['model']} {r['param_name']}={r['param_value']}"

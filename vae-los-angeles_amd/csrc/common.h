@@ -216,6 +216,7 @@ struct Tuning {
     int latent_on = 1;               // key 10: the fused latent launch (latent.hip); off: mmvae_latent_fwd answers MMVAE_ERR_ARG
     int class_tail_on = 1;           // key 12: the fused class-head launch (class_tail.hip); off: mmvae_class_tail answers MMVAE_ERR_ARG
     int step_head_on = 1;            // key 13: the merged head-of-step launch (elementwise.hip); off: mmvae_step_head answers MMVAE_ERR_ARG
+    int ae_latent_on = 1;            // key 15: the autoencoders' fused latent launch (latent.hip); off: mmvae_ae_latent_fwd answers MMVAE_ERR_ARG
     int tn_riders_on = 1;            // key 14: riders in the grouped dW launch (gemm_tn.hip); off: mmvae_gemm_tn_group_riders answers MMVAE_ERR_ARG
 };
 inline Tuning g_tuning;

@@ -180,12 +180,16 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_cols_kernel(int M, int N, T*
 // EncoderC table
 // ------------------------------------------------------------------------------------------
 // elements i0, i0 + stride, ... of the table, each formed on its own (the stand-alone kernel; a block range of step_head_kernel)
+// HEADS = 2: EncoderC's (mu | logvar) table; HEADS = 1: the autoencoders' one projection, table[S][L] (w_lv / b_lv are not read)
+template <int HEADS = 2>
 __device__ __forceinline__ void embed_table_fwd_elems(int S, int E, int L, const float* emb, const float* w_mu, const float* b_mu,
                                                       const float* w_lv, const float* b_lv, float* table, int i0, int stride) {
-    for (int i = i0; i < S * 2 * L; i += stride) {
-        const int s = i / (2 * L), j = i % (2 * L);
-        const float* w = j < L ? w_mu + (long)j * E : w_lv + (long)(j - L) * E;
-        float acc = j < L ? b_mu[j] : b_lv[j - L];
+    const int LW = HEADS * L;
+    for (int i = i0; i < S * LW; i += stride) {
+        const int s = i / LW, j = i % LW;
+        const bool first = HEADS == 1 || j < L;
+        const float* w = first ? w_mu + (long)j * E : w_lv + (long)(j - L) * E;
+        float acc = first ? b_mu[j] : b_lv[j - L];
         for (int e = 0; e < E; ++e) acc += emb[(long)s * E + e] * w[e];
         table[i] = acc;
     }
@@ -200,6 +204,16 @@ __global__ __launch_bounds__(256) void embed_table_fwd_kernel(int S, int E, int 
 __global__ __launch_bounds__(256) void embed_table_bwd_kernel(const EmbedBwd a) {
     extern __shared__ float sm[];
     embed_table_bwd_body(a, blockIdx.x, gridDim.x, sm);
+}
+
+// the one-head case of the two kernels above: the autoencoders' Embedding -> Linear(embed, latent)
+__global__ __launch_bounds__(256) void embed_proj_fwd_kernel(int S, int E, int L, const float* emb, const float* w, const float* b, float* table) {
+    embed_table_fwd_elems<1>(S, E, L, emb, w, b, nullptr, nullptr, table, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+}
+
+__global__ __launch_bounds__(256) void embed_proj_bwd_kernel(const EmbedBwd a) {
+    extern __shared__ float sm[];
+    embed_table_bwd_body<1>(a, blockIdx.x, gridDim.x, sm);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -283,6 +297,79 @@ __global__ __launch_bounds__(256) void fuse_bwd_kernel(mmvae_fuse_bwd_args a, in
     if (use_lds && a.d_table) {
         __syncthreads();
         for (int i = threadIdx.x; i < a.S * L2; i += blockDim.x) if (sT[i] != 0.f) unsafeAtomicAdd(&dtab[i], sT[i]);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// the autoencoders' fusion: the plain mean of the encoder's head and the site's table row (no eps, no logvar)
+// ------------------------------------------------------------------------------------------
+template <typename ZT>
+__global__ __launch_bounds__(256) void fuse_mean_fwd_kernel(mmvae_fuse_mean_fwd_args a) {
+    const long total = (long)a.B * a.ldz;
+    const float inv_n = 1.f / (float)a.n_mod;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int b = (int)(i / a.ldz), l = (int)(i % a.ldz);
+        ZT* zp = (ZT*)a.z + i;
+        if (l >= a.L) { *zp = from_f32<ZT>(0.f); continue; }
+        float sum = 0.f;                           // the first term present is taken as it is: a head of -0 leaves as -0
+        if (a.head) sum = a.head[(long)b * a.ld_head + l];
+        if (a.table) {
+            // an index outside [0, S) poisons its own row and reads nothing outside the table, as fuse_fwd_kernel does
+            const long s = a.site[b];
+            const bool ok = s >= 0 && s < a.S;
+            const long sc = ok ? s : 0;
+            const float t = ok ? a.table[sc * a.L + l] : __builtin_nanf("");
+            sum = a.head ? sum + t : t;
+        }
+        const float m = fuse_mean_elem(sum, a.n_mod, inv_n);
+        a.latent[(long)b * a.L + l] = m;
+        *zp = from_f32<ZT>(m);
+    }
+}
+
+// fuse_bwd_kernel without the reparameterisation: one head, d_table is [copies][S][L]
+__global__ __launch_bounds__(256) void fuse_mean_bwd_kernel(mmvae_fuse_mean_bwd_args a, int rows_per_block, int use_lds) {
+    extern __shared__ float sT[];                 // [S][L] when use_lds
+    if (use_lds) { for (int i = threadIdx.x; i < a.S * a.L; i += blockDim.x) sT[i] = 0.f; __syncthreads(); }
+    const int b0 = blockIdx.x * rows_per_block, b1 = min(a.B, b0 + rows_per_block);
+    float* dtab = a.d_table ? a.d_table + (long)(blockIdx.x % (a.table_copies > 0 ? a.table_copies : 1)) * a.S * a.L : nullptr;
+    const float inv_n = 1.f / (float)a.n_mod;
+    constexpr int U = 4;                          // loads first, as fuse_bwd_kernel
+    const long iend = (long)b1 * a.L;
+    for (long i0 = (long)b0 * a.L + threadIdx.x; i0 < iend; i0 += (long)U * blockDim.x) {
+        float dz[U];
+        int bb[U], ll[U];
+        long sidx[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const long i = min(i0 + (long)u * blockDim.x, iend - 1);        // clamped: the loads always issue
+            const int b = (int)(i / a.L), l = (int)(i - (long)b * a.L);
+            bb[u] = b; ll[u] = l;
+            dz[u] = a.dz[(long)b * a.lddz + l];
+            if (a.g_latent) dz[u] += a.g_latent[i];
+            sidx[u] = a.d_table ? a.site[b] : 0;
+            if (sidx[u] < 0 || sidx[u] >= a.S) sidx[u] = -1;                  // out of range: no scatter (the forward poisoned the row)
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (i0 + (long)u * blockDim.x >= iend) break;
+            const int b = bb[u], l = ll[u];
+            const float d = fuse_mean_elem(dz[u], a.n_mod, inv_n);
+            a.d_head[(long)b * a.ld_head + l] = d;
+            if (a.d_head_lp) {
+                bf16* lp = (bf16*)a.d_head_lp + (long)b * a.ld_head_lp;
+                lp[l] = (bf16)d;
+                if (l == 0) for (int e = a.L; e < a.ld_head_lp; ++e) lp[e] = (bf16)0.f;       // pad columns
+            }
+            if (a.d_table && sidx[u] >= 0) {
+                if (use_lds) atomicAdd(&sT[sidx[u] * a.L + l], d);
+                else unsafeAtomicAdd(&dtab[sidx[u] * a.L + l], d);
+            }
+        }
+    }
+    if (use_lds && a.d_table) {
+        __syncthreads();
+        for (int i = threadIdx.x; i < a.S * a.L; i += blockDim.x) if (sT[i] != 0.f) unsafeAtomicAdd(&dtab[i], sT[i]);
     }
 }
 
@@ -966,6 +1053,53 @@ extern "C" int mmvae_fuse_reparam_bwd(const mmvae_fuse_bwd_args* a, void* stream
     const size_t lds = a->d_table ? (size_t)a->S * 2 * a->L * sizeof(float) : 0;
     const int use_lds = lds > 0 && lds <= 48 * 1024;
     hipLaunchKernelGGL(fuse_bwd_kernel, dim3(grid), dim3(256), use_lds ? lds : 0, (hipStream_t)stream, *a, rows_per_block, use_lds);
+    MM_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int mmvae_embed_proj_fwd(int32_t S, int32_t E, int32_t L, const float* emb, const float* w, const float* b, float* table,
+                                    void* stream) {
+    if (S <= 0 || E <= 0 || L <= 0 || !emb || !w || !b || !table) return MMVAE_ERR_ARG;
+    hipLaunchKernelGGL(embed_proj_fwd_kernel, dim3((S * L + 63) / 64), dim3(64), 0, (hipStream_t)stream, S, E, L, emb, w, b, table);
+    MM_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int mmvae_embed_proj_bwd(int32_t S, int32_t E, int32_t L, const float* emb, const float* w, const float* d_table,
+                                    int32_t table_copies, float* d_emb, float* d_w, float* d_b, void* stream) {
+    if (S <= 0 || E <= 0 || L <= 0 || !emb || !w || !d_table || !d_emb || !d_w || !d_b) return MMVAE_ERR_ARG;
+    if (table_copies < 1) table_copies = 1;
+    const size_t lds = embed_bwd_lds(S, E, L, 1);
+    if (lds > EMBED_BWD_LDS_MAX) return MMVAE_ERR_ARG;
+    const EmbedBwd a{S, E, L, table_copies, emb, w, nullptr, d_table, d_emb, d_w, d_b, nullptr, nullptr};
+    hipLaunchKernelGGL(embed_proj_bwd_kernel, dim3(embed_bwd_blocks(S, E, L, 1)), dim3(256), lds, (hipStream_t)stream, a);
+    MM_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int mmvae_fuse_mean_fwd(const mmvae_fuse_mean_fwd_args* a, void* stream) {
+    if (!a || a->B <= 0 || a->L <= 0 || !a->latent || !a->z || a->ldz < a->L) return MMVAE_ERR_ARG;
+    const int present = (a->head != nullptr) + (a->table != nullptr);
+    if (present == 0 || present != a->n_mod) return MMVAE_ERR_ARG;
+    if (a->head && a->ld_head < a->L) return MMVAE_ERR_ARG;
+    if (a->table && (!a->site || a->S <= 0)) return MMVAE_ERR_ARG;
+    if (a->z_dtype != MMVAE_BF16 && a->z_dtype != MMVAE_F32) return MMVAE_ERR_DTYPE;
+    const int grid = grid_for((long)a->B * a->ldz);
+    if (a->z_dtype == MMVAE_BF16) hipLaunchKernelGGL(fuse_mean_fwd_kernel<bf16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, *a);
+    else hipLaunchKernelGGL(fuse_mean_fwd_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, *a);
+    MM_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int mmvae_fuse_mean_bwd(const mmvae_fuse_mean_bwd_args* a, void* stream) {
+    if (!a || a->B <= 0 || a->L <= 0 || a->n_mod < 1 || a->n_mod > 2 || !a->dz || a->lddz < a->L || !a->d_head || a->ld_head < a->L) return MMVAE_ERR_ARG;
+    if (a->d_head_lp && a->ld_head_lp < a->L) return MMVAE_ERR_ARG;
+    if (a->d_table && (!a->site || a->S <= 0)) return MMVAE_ERR_ARG;
+    const int rows_per_block = 128;          // as mmvae_fuse_reparam_bwd
+    const int grid = (a->B + rows_per_block - 1) / rows_per_block;
+    const size_t lds = a->d_table ? (size_t)a->S * a->L * sizeof(float) : 0;
+    const int use_lds = lds > 0 && lds <= 48 * 1024;
+    hipLaunchKernelGGL(fuse_mean_bwd_kernel, dim3(grid), dim3(256), use_lds ? lds : 0, (hipStream_t)stream, *a, rows_per_block, use_lds);
     MM_CHECK_LAUNCH();
     return 0;
 }

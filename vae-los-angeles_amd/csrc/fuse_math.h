@@ -11,4 +11,8 @@ __device__ __forceinline__ float fuse_reparam_elem(float& mu, float& lv, int n_m
     return mu + eps * expf(0.5f * lv);
 }
 
+// The autoencoders' fusion (reference src/models/directional_ae.py:58-64): `sum` over the modalities present in the order head, table
+// row; it leaves as the mean.  One or two terms: the result is exact after the one addition.
+__device__ __forceinline__ float fuse_mean_elem(float sum, int n_mod, float inv_n) { return n_mod > 1 ? sum * inv_n : sum; }
+
 }  // namespace mm

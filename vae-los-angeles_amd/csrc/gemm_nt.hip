@@ -399,6 +399,7 @@ extern "C" int mmvae_set_tuning(int32_t key, int32_t value) {
     case 12: t.class_tail_on = value; return 0;
     case 13: t.step_head_on = value; return 0;
     case 14: t.tn_riders_on = value; return 0;
+    case 15: t.ae_latent_on = value; return 0;
     }
     return MMVAE_ERR_ARG;
 }

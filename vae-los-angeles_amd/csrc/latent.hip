@@ -54,6 +54,9 @@ struct LatArgs {
     int nslabs;
 };
 
+// DET: the autoencoders' deterministic form (mmvae_ae_latent_fwd) -- ONE head of width L per encoder (the staged head rows >= L are
+// zero), the table is [S][L], the fusion is fuse_mean_elem: no eps is read, no logvar written, a.mu receives the latent.
+template <bool DET>
 __global__ __launch_bounds__(LAT_THREADS) void latent_fwd_kernel(const LatArgs a) {
     typedef SrcBnReluDrop<bf16>::Raw Raw;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -65,7 +68,7 @@ __global__ __launch_bounds__(LAT_THREADS) void latent_fwd_kernel(const LatArgs a
     unsigned char* const scr = smem + LAT_OFF_SCR + wid * LAT_SCR;
     float* const ssum = (float*)scr;
     unsigned char* const sz = scr + LAT_SCR_Z;
-    const int L = a.L, L2 = 2 * a.L;
+    const int L = a.L, L2 = DET ? a.L : 2 * a.L;
     const bool any_enc = a.e[0].nk + a.e[1].nk > 0;
 
     // slab-independent lane constants: element lane + 64 i of the slab's [16][L] block is (row fr[i], latent fl[i])
@@ -77,7 +80,7 @@ __global__ __launch_bounds__(LAT_THREADS) void latent_fwd_kernel(const LatArgs a
     const int total = a.B * L;
 
     Raw raw[2][LAT_NK];
-    float eps_r[LAT_FU];
+    float eps_r[LAT_FU] = {};
     long long site_r[LAT_FU] = {};
     auto fetch = [&](int slab) __attribute__((always_inline)) {
         const int row = slab * 16 + li;
@@ -86,10 +89,12 @@ __global__ __launch_bounds__(LAT_THREADS) void latent_fwd_kernel(const LatArgs a
 #pragma unroll
             for (int j = 0; j < LAT_NK; ++j)
                 if (j < a.e[e].nk) a.e[e].src.fetch(raw[e][j], row, 32 * j + 8 * lg);
+        if constexpr (!DET) {
 #pragma unroll
-        for (int i = 0; i < LAT_FU; ++i) {
-            const int idx = min(slab * 16 * L + lane + 64 * i, total - 1);          // clamped: the loads always issue
-            eps_r[i] = a.eps[idx];
+            for (int i = 0; i < LAT_FU; ++i) {
+                const int idx = min(slab * 16 * L + lane + 64 * i, total - 1);          // clamped: the loads always issue
+                eps_r[i] = a.eps[idx];
+            }
         }
         // a kernel-uniform branch around loads only: an else-side that writes the same registers makes the compiler wait for every load
         // in flight right here (gemm_src.h)
@@ -164,6 +169,22 @@ __global__ __launch_bounds__(LAT_THREADS) void latent_fwd_kernel(const LatArgs a
         for (int i = 0; i < LAT_FU; ++i) {
             if (lane + 64 * i >= 16 * L) break;
             const int r = fr[i], l = fl[i];
+            if constexpr (DET) {
+                float sum = 0.f;
+                bool first = true;                                          // the first term present is taken as it is (a -0 stays -0)
+                if (any_enc) { sum = ssum[r * LAT_SUMLD + l]; first = false; }
+                if (a.table) {
+                    const long long s = st[i];
+                    const bool ok = s >= 0 && s < a.S;
+                    const float t = ok ? stab[(int)s * L + l] : __builtin_nanf("");
+                    sum = first ? t : sum + t;
+                }
+                const float m = fuse_mean_elem(sum, a.n_mod, inv_n);
+                const int idx = slab * 16 * L + lane + 64 * i;
+                if (idx < total) a.mu[idx] = m;
+                ((bf16*)sz)[r * (LAT_SROW / 2) + l] = (bf16)m;
+                continue;
+            }
             float mu = 0.f, lv = 0.f;
             if (any_enc) { mu += ssum[r * LAT_SUMLD + l]; lv += ssum[r * LAT_SUMLD + L + l]; }
             if (a.table) {
@@ -258,5 +279,28 @@ extern "C" int mmvae_latent_fwd(const mmvae_latent_fwd_args* a, void* stream) {
     k.ws = (const bf16*)a->w_stem; k.ldws = a->ldw_stem; k.bs = a->bias_stem; k.ns = a->N_stem;
     k.h0 = (bf16*)a->h0; k.ldh0 = a->ldh0;
     k.nslabs = (a->B + 15) / 16;
-    return launch_lds<latent_fwd_kernel>(dim3(persistent_grid(k.nslabs, LAT_WAVES)), dim3(LAT_THREADS), LAT_LDS, (hipStream_t)stream, k);
+    return launch_lds<latent_fwd_kernel<false>>(dim3(persistent_grid(k.nslabs, LAT_WAVES)), dim3(LAT_THREADS), LAT_LDS, (hipStream_t)stream, k);
+}
+
+extern "C" int mmvae_ae_latent_fwd(const mmvae_ae_latent_fwd_args* a, void* stream) {
+    using namespace mm;
+    if (!a || !g_tuning.ae_latent_on) return MMVAE_ERR_ARG;
+    if (a->prec != MMVAE_PREC_BF16) return MMVAE_ERR_DTYPE;
+    if (a->B <= 0 || a->L <= 0 || a->L > LAT_HN / 2 || (long)a->B * a->L >= (1L << 31)) return MMVAE_ERR_ARG;
+    if (!a->latent || !a->z || !a->w_stem || !a->h0) return MMVAE_ERR_ARG;
+    const int present = (a->enc.y != nullptr) + (a->table != nullptr);
+    if (present == 0 || present != a->n_mod) return MMVAE_ERR_ARG;
+    if (a->table && (!a->site || a->S <= 0 || (long)a->S * a->L > LAT_MAXTAB)) return MMVAE_ERR_ARG;
+    if (a->ldz % 8 || a->ldz < a->L || a->ldz > 32 || ((uintptr_t)a->z & 15)) return MMVAE_ERR_ARG;
+    if (a->N_stem < 64 || a->N_stem % 64 || a->N_stem > LAT_NS || a->ldw_stem % 64 || a->ldw_stem < 32 || ((uintptr_t)a->w_stem & 15)) return MMVAE_ERR_ARG;
+    if (a->ldh0 % 64 || a->ldh0 < a->N_stem || ((uintptr_t)a->h0 & 127) || (long)a->B * a->ldh0 * 2 >= (1L << 32)) return MMVAE_ERR_ARG;
+    LatArgs k{};
+    { const int rc = lat_enc(a->enc, a->B, k.e[0]); if (rc) return rc; }
+    k.B = a->B; k.L = a->L; k.n_mod = a->n_mod; k.S = a->S;
+    k.table = a->table; k.site = (const long long*)a->site; k.mu = a->latent;
+    k.z = (bf16*)a->z; k.ldz = a->ldz;
+    k.ws = (const bf16*)a->w_stem; k.ldws = a->ldw_stem; k.bs = a->bias_stem; k.ns = a->N_stem;
+    k.h0 = (bf16*)a->h0; k.ldh0 = a->ldh0;
+    k.nslabs = (a->B + 15) / 16;
+    return launch_lds<latent_fwd_kernel<true>>(dim3(persistent_grid(k.nslabs, LAT_WAVES)), dim3(LAT_THREADS), LAT_LDS, (hipStream_t)stream, k);
 }

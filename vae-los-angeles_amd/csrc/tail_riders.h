@@ -12,20 +12,22 @@ struct EmbedBwd {
     float* d_emb; float* d_w_mu; float* d_b_mu; float* d_w_lv; float* d_b_lv;
 };
 constexpr size_t EMBED_BWD_LDS_MAX = 64 * 1024;          // the stand-alone launch's capacity (60 KB at latent 128, embed 32, 24 sites); a rider takes no more
-static inline size_t embed_bwd_lds(int S, int E, int L) { return ((size_t)S * 2 * L + (size_t)S * E + (size_t)2 * L * E) * sizeof(float); }
-static inline int embed_bwd_blocks(int S, int E, int L) { return (S * E + 2 * L * E + 2 * L + 255) / 256; }       // one output element per thread
+// heads: 2 = EncoderC's (mu | logvar) table, 1 = the autoencoders' one projection (w_lv / d_w_lv / d_b_lv unused, L2 = L below)
+static inline size_t embed_bwd_lds(int S, int E, int L, int heads = 2) { return ((size_t)S * heads * L + (size_t)S * E + (size_t)heads * L * E) * sizeof(float); }
+static inline int embed_bwd_blocks(int S, int E, int L, int heads = 2) { return (S * E + heads * L * E + heads * L + 255) / 256; }       // one output element per thread
 
 // Workgroup lb of nb (256 threads each).
 // All operands are a few KB: every workgroup first copies them into LDS in ONE round of independent loads (the table gradient summed
 // over its scatter copies in fixed order, the embedding, both head weights), then every thread forms its output element from LDS.
 // (Round 2's form walked w_mu / w_lv / emb in global memory inside the dot products: 20-24 dependent rounds of L2 latency, 22 us for
 // a few thousand multiply-adds.)
+template <int HEADS = 2>
 __device__ __forceinline__ void embed_table_bwd_body(const EmbedBwd& a, int lb, int nb, float* sm) {
     const int S = a.S, E = a.E, L = a.L, copies = a.copies;
     const float* const emb = a.emb; const float* const w_mu = a.w_mu; const float* const w_lv = a.w_lv; const float* const dTc = a.dTc;
     float* const d_emb = a.d_emb; float* const d_w_mu = a.d_w_mu; float* const d_b_mu = a.d_b_mu; float* const d_w_lv = a.d_w_lv;
     float* const d_b_lv = a.d_b_lv;
-    const int L2 = 2 * L;
+    const int L2 = HEADS * L;                            // one head: every j below is < L, w_lv and its gradients are never touched
     float* dT = sm;                                      // [S][2L]: the copies of the table gradient summed (fixed order)
     float* sE = dT + S * L2;                             // [S][E]
     float* sW = sE + S * E;                              // [2L][E]: w_mu rows, then w_lv rows

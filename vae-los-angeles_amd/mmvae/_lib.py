@@ -123,6 +123,16 @@ class LatentFwdArgs(C.Structure):
                 ("h0", vp), ("ldh0", i64)]
 
 
+class AELatentFwdArgs(C.Structure):
+    _fields_ = [("prec", i32), ("B", i32), ("L", i32), ("n_mod", i32),
+                ("enc", LatentEnc),
+                ("table", vp), ("site", vp), ("S", i32),
+                ("latent", vp),
+                ("z", vp), ("ldz", i64),
+                ("w_stem", vp), ("ldw_stem", i64), ("bias_stem", vp), ("N_stem", i32),
+                ("h0", vp), ("ldh0", i64)]
+
+
 class ClassTailArgs(C.Structure):
     _fields_ = [("prec", i32), ("B", i32), ("S", i32), ("L", i32), ("hidden", i32),
                 ("h0", vp), ("ldh0", i64),
@@ -142,6 +152,23 @@ class FuseBwdArgs(C.Structure):
                 ("eps", vp), ("logvar", vp),
                 ("d_heads", vp), ("ld_heads", i64),
                 ("d_table", vp), ("site", vp), ("S", i32), ("d_heads_lp", vp), ("ld_heads_lp", i64), ("table_copies", i32)]
+
+
+class FuseMeanFwdArgs(C.Structure):
+    _fields_ = [("B", i32), ("L", i32), ("n_mod", i32),
+                ("head", vp), ("ld_head", i64),
+                ("table", vp), ("site", vp), ("S", i32),
+                ("latent", vp),
+                ("z", vp), ("z_dtype", i32), ("ldz", i64)]
+
+
+class FuseMeanBwdArgs(C.Structure):
+    _fields_ = [("B", i32), ("L", i32), ("n_mod", i32),
+                ("dz", vp), ("lddz", i64),
+                ("g_latent", vp),
+                ("d_head", vp), ("ld_head", i64),
+                ("d_head_lp", vp), ("ld_head_lp", i64),
+                ("d_table", vp), ("site", vp), ("S", i32), ("table_copies", i32)]
 
 
 class LossArgs(C.Structure):
@@ -256,7 +283,12 @@ _SIGNATURES = {
     "mmvae_embed_table_bwd": [i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp],
     "mmvae_fuse_reparam_fwd": [C.POINTER(FuseFwdArgs), vp],
     "mmvae_fuse_reparam_bwd": [C.POINTER(FuseBwdArgs), vp],
+    "mmvae_embed_proj_fwd": [i32, i32, i32, vp, vp, vp, vp, vp],
+    "mmvae_embed_proj_bwd": [i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp],
+    "mmvae_fuse_mean_fwd": [C.POINTER(FuseMeanFwdArgs), vp],
+    "mmvae_fuse_mean_bwd": [C.POINTER(FuseMeanBwdArgs), vp],
     "mmvae_latent_fwd": [C.POINTER(LatentFwdArgs), vp],
+    "mmvae_ae_latent_fwd": [C.POINTER(AELatentFwdArgs), vp],
     "mmvae_class_tail": [C.POINTER(ClassTailArgs), vp],
     "mmvae_class_tail_fits": [i32, i32, i32, i32, i64, i64],
     "mmvae_vae_loss": [C.POINTER(LossArgs), vp],

@@ -21,6 +21,10 @@ import numpy as np
 METRIC_KEYS = {"Mean R2": "MeanR2", "Global R2": "R2", "MSE": "MSE", "MAE": "MAE", "Cosine Sim": "CosineSimilarity", "Pearson": "PearsonMean"}
 DIRECTIONS = {"DNA -> RNA": "dna2rna", "RNA -> DNA": "rna2dna"}
 MODELS = ("mean", "knn", "knn_site", "vae")
+# The non-variational baselines are asked for as "autoencoder"; their result rows carry the reference's model name "ae".  The name
+# "ae" itself stays refused among `models` (the refusal predates the AE models and is pinned by tests).
+AE_MODEL, AE_ROW = "autoencoder", "ae"
+AE_KINDS = {"dna2rna": "dna2rna_ae", "rna2dna": "rna2dna_ae"}
 HIGHER_IS_BETTER = ("R2", "Cosine", "Pearson")              # perform_statistical_comparison: substrings of the metric name
 
 
@@ -135,14 +139,16 @@ def compare(results, metric="Mean R2"):
     """The reference's perform_statistical_comparison as data: per direction (in order of appearance; one without kNN or VAE results is
     left out, as there) the best kNN and the best VAE by mean_Mean R2 compared on `metric`, VAE against the mean baseline and, when
     present, the best site-conditioned kNN against the VAE.  Every pair: t, p, df, the two means and the winner under the reference's
-    rule (p < 0.05; higher is better for R2 / Cosine / Pearson metrics, lower otherwise), None without a significant difference."""
+    rule (p < 0.05; higher is better for R2 / Cosine / Pearson metrics, lower otherwise), None without a significant difference.
+    With AE rows (model "ae") an entry also has best_ae, ae_vs_vae and ae_vs_knn: the best AE by mean_Mean R2 against the best VAE and
+    the best kNN (vae_cross_modality_cv.py:491-502); without them the entries are what they were."""
     out = []
     for direction in dict.fromkeys(r["direction"] for r in results):
         rows = [r for r in results if r["direction"] == direction]
-        by = {m: [r for r in rows if r["model"] == m] for m in MODELS}
+        by = {m: [r for r in rows if r["model"] == m] for m in MODELS + (AE_ROW,)}
         if not by["knn"] or not by["vae"]:
             continue
-        best = {m: max(by[m], key=lambda r: r["mean_Mean R2"]) for m in MODELS if by[m]}
+        best = {m: max(by[m], key=lambda r: r["mean_Mean R2"]) for m in by if by[m]}
         entry = {"direction": direction, "metric": metric, "best_knn": best["knn"]["param_value"], "best_vae": best["vae"]["param_value"],
                  "knn_vs_vae": _pair("kNN", best["knn"], "VAE", best["vae"], metric)}
         if by["mean"]:
@@ -150,6 +156,10 @@ def compare(results, metric="Mean R2"):
         if by["knn_site"]:
             entry["best_knn_site"] = best["knn_site"]["param_value"]
             entry["knn_site_vs_vae"] = _pair("kNN-site", best["knn_site"], "VAE", best["vae"], metric)
+        if by[AE_ROW]:
+            entry["best_ae"] = best[AE_ROW]["param_value"]
+            entry["ae_vs_vae"] = _pair("AE", best[AE_ROW], "VAE", best["vae"], metric)
+            entry["ae_vs_knn"] = _pair("AE", best[AE_ROW], "kNN", best["knn"], metric)
         out.append(entry)
     return out
 
@@ -215,8 +225,35 @@ def fit_vae(kind, A, B, S, dims, *, epochs, batch_size, seed=42, fold=0, precisi
     (BestState).  The model's initialisation and its noise stream are functions of (seed, fold): the Philox offset of the device is
     reset.  dims: (input_dim_a, input_dim_b, n_sites, latent_dim).  val_loss_fn(model, epoch) replaces the validation pass (tests).
     Returns (model in eval mode, BestState)."""
-    import torch
     import trainer
+    args = SimpleNamespace(input_dim_a=dims[0], input_dim_b=dims[1], n_sites=dims[2], latent_dim=dims[3])
+    return _fit(kind, lambda: trainer.make_model(kind, args), lambda model, a, b, s, beta: trainer.forward_loss(kind, model, a, b, s, beta, None),
+                True, A, B, S, epochs=epochs, batch_size=batch_size, seed=seed, fold=fold, precision=precision, eager=eager, val_loss_fn=val_loss_fn)
+
+
+def _ae_forward_loss(kind, model, a, b, s):
+    """one reference-shaped AE forward + loss (vae_cross_modality_cv.py:225-237) -> the loss tensor"""
+    from src.utils.ae_losses import dna2rna_ae_loss, rna2dna_ae_loss
+    if kind == "dna2rna":
+        return dna2rna_ae_loss(model(dna=b, site=s)[0], a)[0]
+    return rna2dna_ae_loss(model(rna=a, site=s)[0], b)[0]
+
+
+def fit_ae(kind, A, B, S, dims, *, epochs, batch_size, seed=42, fold=0, precision="bf16", eager=False, val_loss_fn=None):
+    """train_ae of the reference (vae_cross_modality_cv.py:198-283) with the objects and the loop of fit_vae: a fresh DNA2RNAAE / RNA2DNAAE
+    (kind "dna2rna" / "rna2dna"), the reconstruction loss alone (dna2rna_ae_loss / rna2dna_ae_loss), no beta warm-up; the captured
+    step is GraphedTrainStep's kind "dna2rna_ae" / "rna2dna_ae".  Arguments and results as fit_vae."""
+    from src.models import DNA2RNAAE, RNA2DNAAE
+    cls = DNA2RNAAE if kind == "dna2rna" else RNA2DNAAE
+    return _fit(AE_KINDS[kind], lambda: cls(dims[0], dims[1], dims[2], dims[3]), lambda model, a, b, s, beta: _ae_forward_loss(kind, model, a, b, s),
+                False, A, B, S, epochs=epochs, batch_size=batch_size, seed=seed, fold=fold, precision=precision, eager=eager, val_loss_fn=val_loss_fn)
+
+
+def _fit(step_kind, make_model, forward_loss, warm_beta, A, B, S, *, epochs, batch_size, seed, fold, precision, eager, val_loss_fn):
+    """The training loop fit_vae and fit_ae share.  step_kind: the GraphedTrainStep kind; make_model() -> the fresh model (called after
+    the seed is set); forward_loss(model, a, b, s, beta) -> the loss tensor of the eager step and of the validation pass; warm_beta:
+    the KL weight follows the beta warm-up (else it stays 0)."""
+    import torch
     from src.config import Config
     from . import engine
     from .graphs import GraphedTrainStep
@@ -232,17 +269,16 @@ def fit_vae(kind, A, B, S, dims, *, epochs, batch_size, seed=42, fold=0, precisi
     run_seed = (int(seed) * 1000 + int(fold)) * 100003
     torch.manual_seed(run_seed)
     engine.GLOBAL_NOISE.load_state_dict({"offset": 0}, dev)
-    args = SimpleNamespace(input_dim_a=dims[0], input_dim_b=dims[1], n_sites=dims[2], latent_dim=dims[3])
-    model = trainer.make_model(kind, args).to(dev).set_precision(precision)
+    model = make_model().to(dev).set_precision(precision)
     optimizer = FusedAdamW(model.parameters(), lr=Config.LEARNING_RATE, weight_decay=Config.WEIGHT_DECAY)
     scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(optimizer, mode="min", factor=Config.LR_SCHEDULER_FACTOR, patience=Config.LR_SCHEDULER_PATIENCE)
-    graphed = None if eager else GraphedTrainStep(model, optimizer, beta=0.0, gamma=Config.GAMMA, warmup=1, preserve_state=True, kind=kind,
+    graphed = None if eager else GraphedTrainStep(model, optimizer, beta=0.0, gamma=Config.GAMMA, warmup=1, preserve_state=True, kind=step_kind,
                                                   dataset=tuple(tr), batch_size=Bsz)
     perm_gen = torch.Generator(device=dev)
     best = BestState(Config.PATIENCE)
     for epoch in range(int(epochs)):
         model.train()
-        beta = min(1.0, epoch / Config.BETA_WARMUP_EPOCHS) * Config.BETA_START
+        beta = min(1.0, epoch / Config.BETA_WARMUP_EPOCHS) * Config.BETA_START if warm_beta else 0.0
         perm_gen.manual_seed(run_seed + 1 + epoch)
         order = torch.randperm(n_train, device=dev, generator=perm_gen)
         if graphed is not None:
@@ -255,7 +291,7 @@ def fit_vae(kind, A, B, S, dims, *, epochs, batch_size, seed=42, fold=0, precisi
         else:
             for i in range(steps):
                 idx = order[i * Bsz:(i + 1) * Bsz]
-                loss = trainer.forward_loss(kind, model, _rows(tr[0], idx), _rows(tr[1], idx), tr[2][idx], beta, None)
+                loss = forward_loss(model, _rows(tr[0], idx), _rows(tr[1], idx), tr[2][idx], beta)
                 optimizer.zero_grad()
                 loss.backward()
                 optimizer.step()
@@ -266,7 +302,7 @@ def fit_vae(kind, A, B, S, dims, *, epochs, batch_size, seed=42, fold=0, precisi
             total, nb = 0.0, 0
             with torch.no_grad():
                 for i in range(0, va[0].shape[0], Bsz):
-                    total += trainer.forward_loss(kind, model, va[0][i:i + Bsz], va[1][i:i + Bsz], va[2][i:i + Bsz], beta, None).item()
+                    total += forward_loss(model, va[0][i:i + Bsz], va[1][i:i + Bsz], va[2][i:i + Bsz], beta).item()
                     nb += 1
             val_loss = total / max(nb, 1)
         scheduler.step(val_loss)
@@ -277,8 +313,9 @@ def fit_vae(kind, A, B, S, dims, *, epochs, batch_size, seed=42, fold=0, precisi
     return model, best
 
 
-def _predict_vae(kind, model, X, S, chunk=4096):
-    """one eval-mode forward of the rows (eps is drawn in eval mode too, as the reference's models do): fp32 (rows, outputs)"""
+def _predict(kind, model, X, S, chunk=4096):
+    """one eval-mode forward of the rows -> fp32 (rows, outputs): the first of a VAE's three results (eps is drawn in eval mode too, as
+    the reference's models do) or of an AE's two"""
     import torch
     out = []
     with torch.no_grad():
@@ -339,22 +376,23 @@ def cross_validate(X, Y, site, fold, direction, models=("mean", "knn", "vae"), k
                    precision="bf16", eager=False, latent_dim=None, n_sites=None, log=None, predictions=None):
     """run_cross_validation of the reference for one direction ("DNA -> RNA" / "RNA -> DNA") on the device.  X (N, Fx) inputs and
     Y (N, Fy) targets: fp32 or padded-bf16-row device matrices; site (N,) and fold (N,) integer codes (host or device; fold from
-    kfold_assignments).  models: any of "mean", "knn", "knn_site", "vae".  Returns the reference's aggregated_results dicts in the
-    reference's order: mean, knn per k, knn_site per k, vae.  Fold metrics are ImputationMetrics on that fold's rows under the
+    kfold_assignments).  models: any of "mean", "knn", "knn_site", "vae", "autoencoder".  Returns the reference's aggregated_results dicts
+    in the reference's order: mean, knn per k, knn_site per k, vae, ae.  Fold metrics are ImputationMetrics on that fold's rows under the
     reference's six keys (METRIC_KEYS).
       mean      per fold the column means of the other folds' Y rows, float64 (total column sums minus the fold's)
       knn       knn_predictions(): one fold-masked search for all folds and all k
       knn_site  the same with the site condition
       vae       per fold fit_vae() on the other folds' rows, then one eval-mode forward of the fold's rows
+      autoencoder  the same with fit_ae(): the rows carry the reference's model name "ae" (the name "ae" itself is refused here)
     log(result) is called as results arrive.  predictions: a dict that receives {(model, param_value): fp32 (N, Fy)}, every row as its
     own fold's model predicted it (the mean baseline's rows are not materialised)."""
     import torch
     from . import ops
     if direction not in DIRECTIONS:
         raise ValueError(f"direction must be one of {sorted(DIRECTIONS)}")
-    unknown = [m for m in models if m not in MODELS]
+    unknown = [m for m in models if m not in MODELS + (AE_MODEL,)]
     if unknown:
-        raise ValueError(f"models {unknown}: any of {MODELS}")
+        raise ValueError(f"models {unknown}: any of {MODELS + (AE_MODEL,)}")
     X, Y = ops._device_matrix(X, "X", "cross_validate"), ops._device_matrix(Y, "Y", "cross_validate")
     N, dev = X.shape[0], X.device
     site = torch.as_tensor(site).to(dev).long().reshape(-1)
@@ -392,7 +430,9 @@ def cross_validate(X, Y, site, fold, direction, models=("mean", "knn", "vae"), k
             scores = _fold_metrics(Y_folds, lambda f: preds[int(k)][fold_rows[f]])
             results.append(aggregate(direction, model, "k", int(k), t_search / len(k_values) + time.time() - t1, scores))
             say(results[-1])
-    if "vae" in models:
+    for name, row_name, fit in (("vae", "vae", fit_vae), (AE_MODEL, AE_ROW, fit_ae)):
+        if name not in models:
+            continue
         kind = DIRECTIONS[direction]
         A, B = (Y, X) if kind == "dna2rna" else (X, Y)
         from src.config import Config
@@ -402,16 +442,16 @@ def cross_validate(X, Y, site, fold, direction, models=("mean", "knn", "vae"), k
         preds = []
         for f in range(n_folds):
             rows = torch.from_numpy(np.flatnonzero(fold_h != f)).to(dev)
-            model, _ = fit_vae(kind, _rows(A, rows), _rows(B, rows), site[rows].contiguous(), dims, epochs=epochs, batch_size=batch_size,
-                               seed=seed, fold=f, precision=precision, eager=eager)
-            preds.append(_predict_vae(kind, model, _rows(X, fold_rows[f]), site[fold_rows[f]].contiguous()))
+            model, _ = fit(kind, _rows(A, rows), _rows(B, rows), site[rows].contiguous(), dims, epochs=epochs, batch_size=batch_size,
+                           seed=seed, fold=f, precision=precision, eager=eager)
+            preds.append(_predict(kind, model, _rows(X, fold_rows[f]), site[fold_rows[f]].contiguous()))
         scores = _fold_metrics(Y_folds, lambda f: preds[f])
         torch.cuda.synchronize(dev)
         if predictions is not None:
             full = torch.zeros(N, Y.shape[1], dtype=torch.float32, device=dev)
             for r, p in zip(fold_rows, preds):
                 full.index_add_(0, r, p)                                      # a row predicted twice would show
-            predictions[("vae", int(epochs))] = full
-        results.append(aggregate(direction, "vae", "epochs", int(epochs), time.time() - t0, scores))
+            predictions[(row_name, int(epochs))] = full
+        results.append(aggregate(direction, row_name, "epochs", int(epochs), time.time() - t0, scores))
         say(results[-1])
     return results

@@ -254,7 +254,7 @@ class StepZeros:
     loss_ws: Optional[tuple]            # (sums float64[5], out5 float32[5]) as ops.loss_workspace; None once the loss took it
     arena: Optional[torch.Tensor]       # flat fp32 gradient arena (param_list() order)
     bwd_stats: list                     # per BN layer: float64 (2, width) sums of the BatchNorm backward
-    d_table: Optional[torch.Tensor]     # (copies, sites, 2 * latent): the EncoderC table gradient, summed over the copies in its backward
+    d_table: Optional[torch.Tensor]     # (copies, sites, 2 * latent): the EncoderC table gradient, summed over the copies in its backward; AEGraph: (copies, sites, latent)
     unfilled: Optional[torch.Tensor] = None     # zero_pack(fill=False): the whole allocation, still to be zeroed by the caller
 
 
@@ -287,18 +287,21 @@ class StepState:
 class EncoderMLP:
     """EncoderA / EncoderB (reference src/models/encoders.py:8-23, 26-46):
     [Linear -> BatchNorm1d -> ReLU -> Dropout(0.1)] x n, then the fc_mu | fc_logvar heads
-    computed as ONE GEMM with N = 2*latent."""
+    computed as ONE GEMM with N = 2*latent.
+    fc_logvar=None: the single-head form of the autoencoders (directional_ae.py:20-26, 81-91) -- the stack ends in ONE
+    Linear(hidden, latent) (`fc_mu` here): the head GEMM has N = latent, the arena one weight and one bias."""
 
-    def __init__(self, linears, bns, fc_mu, fc_logvar, name="enc"):
+    def __init__(self, linears, bns, fc_mu, fc_logvar=None, name="enc"):
         self.linears, self.bns, self.fc_mu, self.fc_logvar = list(linears), list(bns), fc_mu, fc_logvar
         self.in_dim = self.linears[0].in_features
         self.latent = fc_mu.out_features
+        self.head_width = self.latent * (1 if fc_logvar is None else 2)
         self.name = name
 
     def prepare(self, prec, device):
         self.pl = [ops.PreparedLinear([l.weight], [l.bias], prec, device) for l in self.linears]
-        self.pl_heads = ops.PreparedLinear([self.fc_mu.weight, self.fc_logvar.weight],
-                                           [self.fc_mu.bias, self.fc_logvar.bias], prec, device)
+        heads = [self.fc_mu] if self.fc_logvar is None else [self.fc_mu, self.fc_logvar]
+        self.pl_heads = ops.PreparedLinear([h.weight for h in heads], [h.bias for h in heads], prec, device)
         return self.pl + [self.pl_heads]
 
     def params(self):
@@ -306,6 +309,8 @@ class EncoderMLP:
         out = []
         for l, bn in zip(self.linears, self.bns):
             out += [l.weight, l.bias, bn.weight, bn.bias]
+        if self.fc_logvar is None:
+            return out + [self.fc_mu.weight, self.fc_mu.bias]
         out += [self.fc_mu.weight, self.fc_logvar.weight, self.fc_mu.bias, self.fc_logvar.bias]
         return out
 
@@ -372,19 +377,19 @@ class EncoderMLP:
         return (self.run_heads(prec, owed) if heads else owed), layers
 
     def run_heads(self, prec, owed):
-        """The fc_mu | fc_logvar heads as a GEMM of their own -> fp32 (B, 2 * latent)."""
-        heads = torch.empty(owed.y.shape[0], 2 * self.latent, dtype=torch.float32, device=owed.y.device)
-        self._consume(prec, owed.y, owed.prologue, owed.fin, 2 * self.latent, self.pl_heads.K, heads, self.pl_heads.bias, self.pl_heads.w,
+        """The fc_mu | fc_logvar heads as a GEMM of their own -> fp32 (B, 2 * latent); (B, latent) in the single-head form."""
+        heads = torch.empty(owed.y.shape[0], self.head_width, dtype=torch.float32, device=owed.y.device)
+        self._consume(prec, owed.y, owed.prologue, owed.fin, self.head_width, self.pl_heads.K, heads, self.pl_heads.bias, self.pl_heads.w,
                       f"{self.name}.heads.fwd")
         return heads
 
     def backward(self, prec, layers, d_heads, grads, tn=ops.gemm_tn, stats_bufs=None, train=True, d_heads_lp=None):
-        """d_heads: [B][2L] fp32.  grads: dict param -> fp32 view (pre-zeroed, accumulated).
+        """d_heads: [B][2L] fp32 ([B][L] in the single-head form).  grads: dict param -> fp32 view (pre-zeroed, accumulated).
         train=False: the forward ran in eval mode (running statistics, no dropout) -- torch's
         batch_norm(training=False) backward: dy = gamma * rstd * d, no batch-statistics correction."""
         B, dev = d_heads.shape[0], d_heads.device
         adt = act_dtype(prec)
-        L2 = 2 * self.latent
+        L2 = self.head_width
         Kl = self.pl_heads.K
         gw = grads[self.fc_mu.weight]            # fc_logvar.weight follows immediately in the arena
         gb = grads[self.fc_mu.bias]
@@ -467,8 +472,52 @@ class EmbedEncoder:
                 grads[self.embedding.weight], grads[self.fc_mu.weight], grads[self.fc_mu.bias],
                 grads[self.fc_logvar.weight], grads[self.fc_logvar.bias])
 
+    rides = True                       # its backward may run as rider workgroups of the grouped dW launch (ops.tn_riders)
+    table_width = 2                    # table columns per latent dimension
+
+    def launch_backward(self, *args):
+        ops.embed_table_bwd(*args)
+
     def backward(self, d_table, grads):
-        ops.embed_table_bwd(*self.backward_args(d_table, grads))
+        self.launch_backward(*self.backward_args(d_table, grads))
+
+
+class ProjectedEmbedding:
+    """The autoencoders' site path (directional_ae.py:29-30, 52-56): Embedding(S,E) -> Linear(E, latent) == a [S][L] table + gather.
+    The one-head EmbedEncoder: the table is a launch of its own (ops.embed_proj_fwd), and so is its backward."""
+    rides = False
+    table_width = 1
+
+    def __init__(self, embedding, projection):
+        self.embedding, self.projection = embedding, projection
+        self.latent = projection.out_features
+
+    def prepare(self, prec, device):
+        return []
+
+    def params(self):
+        return [self.embedding.weight, self.projection.weight, self.projection.bias]
+
+    def table_args(self):
+        """ops.embed_proj_fwd's arguments, the table (the last of them) freshly allocated."""
+        emb = self.embedding.weight
+        return (emb, self.projection.weight, self.projection.bias, torch.empty(emb.shape[0], self.latent, dtype=torch.float32, device=emb.device))
+
+    def table(self):
+        args = self.table_args()
+        ops.embed_proj_fwd(*args)
+        return args[-1]
+
+    def backward_args(self, d_table, grads):
+        """ops.embed_proj_bwd's arguments."""
+        return (self.embedding.weight, self.projection.weight, d_table,
+                grads[self.embedding.weight], grads[self.projection.weight], grads[self.projection.bias])
+
+    def launch_backward(self, *args):
+        ops.embed_proj_bwd(*args)
+
+    def backward(self, d_table, grads):
+        self.launch_backward(*self.backward_args(d_table, grads))
 
 
 class DecoderMLP:
@@ -642,7 +691,8 @@ class VAEGraph:
         widths = (self.enc_a.widths() if has_a else []) + (self.enc_b.widths() if has_b else [])
         n_sums = 2 * sum(widths)                       # every layer's (2, width) float64 sums are a multiple of 16 bytes: no gaps
         n_sites = self.enc_c.embedding.weight.shape[0] if has_site else 0
-        n_tab = n_sites * 2 * self.latent * L_.TABLE_COPIES
+        tab_w = self.enc_c.table_width * self.latent if has_site else 0
+        n_tab = n_sites * tab_w * L_.TABLE_COPIES
         both = fwd and bwd
         packed = zeros_pack(device, [
             (n_sums if fwd else 0, torch.float64),
@@ -659,7 +709,7 @@ class VAEGraph:
                          loss_ws=(loss_sums, loss_out5) if both else None,
                          arena=arena if bwd else None,
                          bwd_stats=per_layer(bwd_sums) if bwd else [],
-                         d_table=d_table[:n_tab].view(-1, n_sites, 2 * self.latent) if bwd and has_site else None,
+                         d_table=d_table[:n_tab].view(-1, n_sites, tab_w) if bwd and has_site else None,
                          unfilled=unfilled)
 
     def forward(self, prec, xa, xb, site, train, want_bwd=False):
@@ -672,30 +722,28 @@ class VAEGraph:
         with ops.pinned_stream():
             return self._forward(prec, xa, xb, site, train, train and want_bwd)
 
-    def _forward(self, prec, xa, xb, site, train, want_bwd):
-        ref = xa if xa is not None else (xb if xb is not None else site)
-        dev, B = ref.device, ref.shape[0]
-        state = StepState(prec, B, train, tail_riders=self.tail_riders and want_bwd)
-        heads_a = heads_b = table = None
-        Ld = self.latent
-        widths_a = self.enc_a.widths() if (train and xa is not None) else []
-        widths_b = self.enc_b.widths() if (train and xb is not None) else []
-        n_a = len(widths_a)
+    def _head_of_step(self, prec, dev, B, has_a, has_b, has_site, train, want_bwd, eps_width, table_args):
+        """What a forward begins with -> (masks, eps, zeros, n_a, whether the head launch ran -- it then made the table of table_args).
+        eps_width: the latent width eps is drawn for; None: masks only (AEGraph)."""
+        widths_a = self.enc_a.widths() if (train and has_a) else []
+        widths_b = self.enc_b.widths() if (train and has_b) else []
         # A training forward begins with four launches that depend on nothing of the step -- the weight preparation, the Philox
         # noise, the step's one memset and EncoderC's table -- of which only the noise has real work: ONE launch
         # (ops.step_head), its arguments collected here.  The weights are prepared at the HEAD of every step, from the masters as
         # they are then: a caller may rewrite parameters in place between two replays of a captured step (a checkpoint restore).
         prep = self._prep.ensure(prec, dev, self.param_list(), self._prepare, run=False)
-        masks, eps, noise_launch = self.noise.plan(B, widths_a + widths_b, Ld, dev)       # eps is sampled in eval mode too (vae.py:73)
+        masks, eps, noise_launch = self.noise.plan(B, widths_a + widths_b, eps_width, dev)       # eps is sampled in eval mode too (vae.py:73)
+        # (Only an AEGraph gets here with neither masks nor eps -- eval mode, or no encoder: nothing is drawn.  A VAEGraph always draws
+        # eps, eps_width is its latent width, so this branch changes no launch of it.)
+        if eps_width is None and noise_launch is not None and noise_launch[0] is None:
+            noise_launch = None
         head = train and noise_launch is not None      # eval mode, injected noise: the launches as they were
         # ONE fill for everything this step needs zeroed: forward BatchNorm sums, the loss accumulators, and -- when a backward will
         # follow -- the flat gradient arena with the backward's BatchNorm sums and embedding-table gradient (three fills before)
-        zeros = self.zero_pack(dev, xa is not None, xb is not None, site is not None, fwd=True, bwd=want_bwd, fill=not head) if train else None
-        table_args = self.enc_c.table_args() if site is not None else None
+        zeros = self.zero_pack(dev, has_a, has_b, has_site, fwd=True, bwd=want_bwd, fill=not head) if train else None
         if head:
             try:
                 ops.step_head(noise_launch, prep, [zeros.unfilled], table_args)
-                table = table_args[-1] if table_args is not None else None
             except L_.MMVAEArgError:                   # refused before anything was enqueued: the four launches, as before
                 head = False
         if not head:
@@ -707,6 +755,19 @@ class VAEGraph:
                 zeros.unfilled.zero_()
         if zeros is not None:
             zeros.unfilled = None
+        return masks, eps, zeros, len(widths_a), head
+
+    def _forward(self, prec, xa, xb, site, train, want_bwd):
+        ref = xa if xa is not None else (xb if xb is not None else site)
+        dev, B = ref.device, ref.shape[0]
+        state = StepState(prec, B, train, tail_riders=self.tail_riders and want_bwd)
+        heads_a = heads_b = table = None
+        Ld = self.latent
+        table_args = self.enc_c.table_args() if site is not None else None
+        masks, eps, zeros, n_a, head = self._head_of_step(prec, dev, B, xa is not None, xb is not None, site is not None, train, want_bwd,
+                                                          Ld, table_args)
+        if head and table_args is not None:
+            table = table_args[-1]
         if want_bwd:
             state.zeros = zeros
         # With merged decoder first layers in bf16 mode the encoders stop before their heads: heads, fusion, reparameterisation and the
@@ -750,11 +811,18 @@ class VAEGraph:
         # i.e. every step's activations would pile up in HBM until it runs)
         state.eps, state.logvar = eps, logvar.detach()
         state.n_mod = (heads_a is not None) + (heads_b is not None) + (table is not None)
+        return self._decode(prec, B, dev, z, H0, fuse_latent, state, zeros, want_bwd, site), mu, logvar, state
+
+    def _decode(self, prec, B, dev, z, H0, stem_done, state, zeros, want_bwd, site, first0=None):
+        """The decoders on z -> their outputs; fills state.dec / fused / class_tail.  H0: the merged first layers' output buffer (None
+        without a stem), already computed when stem_done.  first0: the first decoder's layer-0 output, computed elsewhere (AEGraph)."""
+        stem = self.dec_stem
         outs, state.dec = [None] * len(self.decoders), [None] * len(self.decoders)
         order = sorted(range(len(self.decoders)), key=lambda i: -sum(l.weight.numel() for l in self.decoders[i].linears))
         firsts = [None] * len(self.decoders)
+        firsts[0] = first0
         if stem is not None:
-            if not fuse_latent:
+            if not stem_done:
                 ops.gemm_nt(prec, z, stem.w, stem.N, stem.K, H0, bias=stem.bias, act=ACT_RELU, tag="Decoders.L0.fwd")
             off = 0
             for i, d in enumerate(self.decoders):
@@ -785,7 +853,7 @@ class VAEGraph:
                 o, acts = dec.forward(prec, z, first=firsts[i])
             outs[i] = o
             state.dec[i] = (acts, o.detach())
-        return outs, mu, logvar, state
+        return outs
 
     def _class_tail_index(self, prec, H0, want, site):
         """The decoder whose last Linear the fused class-head launch can take over, or None: the training step asked for it
@@ -808,7 +876,7 @@ class VAEGraph:
         Returns (flat_arena, {param: grad view})."""
         prec, B = state.prec, state.B
         site = state.site
-        dev = state.eps.device
+        dev = state.dec[0][1].device
         Ld = self.latent
         zeros, state.zeros = state.zeros, None         # zeroed by the forward's one memset; else (eval-mode forward, no want_bwd) here
         if zeros is None:
@@ -871,10 +939,7 @@ class VAEGraph:
             # small-output tensors sit in front of the cut: their grouped dW launch stays ONE launch at the end of backward, as on one GPU
             # (round 3; before, data parallelism flushed that launch here: an extra grouped GEMM + reduce per step).
             self.grad_sync.early(flat, self.early_cut())
-        d_heads = torch.empty(B, 2 * Ld, dtype=torch.float32, device=dev)
-        # bf16 mode: a bf16 copy of d_heads for the heads' dX GEMMs (they round it on load anyway; plain bf16 A -> LDS-DMA kernel)
-        d_heads_lp = torch.empty(B, ceil_to(2 * Ld, 8), dtype=torch.bfloat16, device=dev) if prec == PREC_BF16 else None
-        ops.fuse_reparam_bwd(B, Ld, state.n_mod, g_mu, g_lv, dzs, state.eps, state.logvar, d_heads, zeros.d_table, site, d_heads_lp=d_heads_lp)
+        d_heads, d_heads_lp = self._fusion_backward(state, zeros, dzs, g_mu, g_lv, dev)
         if state.enc_a is not None:
             self.enc_a.backward(prec, state.enc_a, d_heads, grads, tn, zeros.bwd_stats[:n_a], train=state.train, d_heads_lp=d_heads_lp)
         if state.enc_b is not None:
@@ -883,15 +948,17 @@ class VAEGraph:
         # the loss finalisation the loss left behind have nothing to do with the grouped dW launch that ends the backward: with
         # tail_riders they run as extra workgroups of it.  Without, where there is no such launch, or where the library refuses
         # (nothing enqueued), they are the launches of their own they were.
+        # (A ProjectedEmbedding's backward does not ride: the rider role is EncoderC's two-head table; it is always its own launch.)
         embed_bwd = self.enc_c.backward_args(zeros.d_table, grads) if site is not None else None
+        ride_embed = embed_bwd if (embed_bwd is not None and self.enc_c.rides) else None
         loss_tail, state.loss_tail = state.loss_tail, None
-        riders = ops.tn_riders(embed_bwd, loss_tail) if (state.tail_riders and (embed_bwd is not None or loss_tail is not None)) else None
-        if riders is None and embed_bwd is not None:
-            ops.embed_table_bwd(*embed_bwd)
+        riders = ops.tn_riders(ride_embed, loss_tail) if (state.tail_riders and (ride_embed is not None or loss_tail is not None)) else None
+        if embed_bwd is not None and (riders is None or ride_embed is None):
+            self.enc_c.launch_backward(*embed_bwd)
         rode = flush_tiny("tiny_dW.heads", riders)
         if riders is not None and not rode:
-            if embed_bwd is not None:
-                ops.embed_table_bwd(*embed_bwd)
+            if ride_embed is not None:
+                self.enc_c.launch_backward(*ride_embed)
             if loss_tail is not None:
                 ops.loss_finalize(*loss_tail)
         elif riders is None and loss_tail is not None:
@@ -899,3 +966,87 @@ class VAEGraph:
         if self.grad_sync is not None:
             self.grad_sync.final(flat)
         return flat, grads
+
+    def _fusion_backward(self, state, zeros, dzs, g_mu, g_lv, dev):
+        """Backward of the mean fusion + reparameterisation -> (d_heads fp32 (B, 2L), its bf16 copy or None); scatters into zeros.d_table."""
+        prec, B, Ld = state.prec, state.B, self.latent
+        d_heads = torch.empty(B, 2 * Ld, dtype=torch.float32, device=dev)
+        # bf16 mode: a bf16 copy of d_heads for the heads' dX GEMMs (they round it on load anyway; plain bf16 A -> LDS-DMA kernel)
+        d_heads_lp = torch.empty(B, ceil_to(2 * Ld, 8), dtype=torch.bfloat16, device=dev) if prec == PREC_BF16 else None
+        ops.fuse_reparam_bwd(B, Ld, state.n_mod, g_mu, g_lv, dzs, state.eps, state.logvar, d_heads, zeros.d_table, state.site, d_heads_lp=d_heads_lp)
+        return d_heads, d_heads_lp
+
+
+# --------------------------------------------------------------------------------------------
+# an autoencoder graph: one single-head encoder and / or the projected site embedding -> plain mean -> one decoder
+# --------------------------------------------------------------------------------------------
+class AEGraph(VAEGraph):
+    """Compute graph of RNA2DNAAE / DNA2RNAAE (reference src/models/directional_ae.py:10-134): a single-head MLP encoder (in slot a for
+    RNA, slot b for DNA), the site through a ProjectedEmbedding, the plain mean of the latents present, one decoder.  No eps is drawn,
+    no logvar exists, nothing of a KL term: forward returns (outs, latent, state).  Everything else -- the head of the step, the one
+    memset, the decoders, fused_recon, tail_riders, the gradient arena, grad_sync -- is VAEGraph's."""
+
+    def __init__(self, enc_a=None, enc_b=None, site=None, decoder=None):
+        if (enc_a is None) == (enc_b is None) or site is None or decoder is None:
+            raise ValueError("AEGraph: exactly one MLP encoder, the projected site embedding and one decoder")
+        if (enc_a or enc_b).fc_logvar is not None or not isinstance(site, ProjectedEmbedding):
+            raise ValueError("AEGraph: the encoder must be in its single-head form and the site a ProjectedEmbedding")
+        super().__init__(enc_a=enc_a, enc_b=enc_b, enc_c=site, decoders=[decoder])
+
+    def _forward(self, prec, xa, xb, site, train, want_bwd):
+        x = xa if xa is not None else xb
+        enc = self.enc_a if xa is not None else self.enc_b
+        if x is not None and enc is None:
+            raise RuntimeError("AEGraph: this graph has no encoder for that input")
+        ref = x if x is not None else site
+        dev, B, Ld = ref.device, ref.shape[0], self.latent
+        state = StepState(prec, B, train, tail_riders=self.tail_riders and want_bwd)
+        # masks only: the Philox offset advances by exactly the mask draw, and not at all in eval mode.  The table is a launch of its
+        # own (the head launch's table role is EncoderC's two-head table).
+        masks, _, zeros, _, _ = self._head_of_step(prec, dev, B, xa is not None, xb is not None, site is not None, train, want_bwd, None, None)
+        if want_bwd:
+            state.zeros = zeros
+        head = table = None
+        dec = self.decoders[0]
+        fuse = prec == PREC_BF16 and isinstance(dec, DecoderMLP) and len(dec.linears) >= 2
+        if x is not None:
+            x = _check_input(x.reshape(x.shape[0], -1), "a" if xa is not None else "b", enc.in_dim, prec)
+            # in bf16 mode the encoder stops before its head: head, mean and the decoder's first layer are ONE launch
+            # (mmvae_ae_latent_fwd); where the library does not take it, the three launches it replaces run below
+            head, layers = enc.forward(prec, x, train, masks if train else None, zeros.fwd_stats if train else None, want_bwd=want_bwd,
+                                       heads=not fuse)
+            if xa is not None:
+                state.enc_a = layers
+            else:
+                state.enc_b = layers
+        if site is not None:
+            if site.dtype != torch.int64:
+                site = site.long()
+            site = state.site = site.contiguous()
+            table = self.enc_c.table()
+        latent = torch.empty(B, Ld, dtype=torch.float32, device=dev)
+        z = torch.empty(B, ceil_to(Ld, 8), dtype=act_dtype(prec), device=dev)
+        first = None
+        if fuse:
+            pl0 = dec.pl[0]
+            first = torch.empty(B, ceil_to(pl0.N, 8), dtype=act_dtype(prec), device=dev)
+            try:
+                ops.ae_latent_fwd(prec, B, Ld, head, table, site, latent, z, pl0, first)
+            except L_.MMVAEArgError:                   # refused before anything was enqueued
+                fuse, first = False, None
+                head = enc.run_heads(prec, head) if head is not None else None
+        if not fuse:
+            ops.fuse_mean_fwd(B, Ld, head, table, site, latent, z)
+        state.n_mod = (head is not None) + (table is not None)
+        return self._decode(prec, B, dev, z, None, False, state, zeros, want_bwd, site, first0=first), latent, state
+
+    def _backward(self, state, g_outs, g_logit_flags, g_latent, g_lv=None):
+        return super()._backward(state, g_outs, g_logit_flags, g_latent, None)
+
+    def _fusion_backward(self, state, zeros, dzs, g_latent, g_lv, dev):
+        """Backward of the plain mean -> (d_head fp32 (B, L), its bf16 copy or None); scatters into zeros.d_table (copies, S, L)."""
+        prec, B, Ld = state.prec, state.B, self.latent
+        d_head = torch.empty(B, Ld, dtype=torch.float32, device=dev)
+        d_head_lp = torch.empty(B, ceil_to(Ld, 8), dtype=torch.bfloat16, device=dev) if prec == PREC_BF16 else None
+        ops.fuse_mean_bwd(B, Ld, state.n_mod, dzs[0], g_latent, d_head, zeros.d_table, state.site, d_head_lp=d_head_lp)
+        return d_head, d_head_lp

@@ -41,27 +41,54 @@ class VAEGraphFn(torch.autograd.Function):
         g_outs = [None if g is None else _as_rows(g) for g in gs[:n_out]]
         g_mu = None if gs[n_out] is None else gs[n_out].contiguous().float()
         g_lv = None if gs[n_out + 1] is None else gs[n_out + 1].contiguous().float()
-        flags = [False] * n_out
-        lg = state.loss_grads
-        if lg is not None and lg.armed:                              # the loss handle's backward ran: its gradients are the ones to use
-            if lg.scale is not None:                                 # None: unit_grad promised by the caller (fused_loss)
-                ops.scale_many(list(lg.g_outs) + [lg.g_mu, lg.g_lv], lg.scale)       # one launch, not five
-            for i, sg in enumerate(lg.g_outs):
-                if sg is None:
-                    continue
-                if g_outs[i] is not None:            # rare: another loss term also touched this output
-                    sg[:, :g_outs[i].shape[1]] += _to_stash_space(g_outs[i], state.dec[i][1], graph.decoders[i], sg.dtype)
-                g_outs[i], flags[i] = sg, graph.decoders[i].final_sigmoid
+        return (None, None, None, None, None, None, None, *_graph_backward(graph, state, g_outs, g_mu, g_lv))
+
+
+def _graph_backward(graph, state, g_outs, g_mu, g_lv):
+    """The backward of one forward of a VAEGraph / AEGraph (g_mu: the gradient at mu, or at the AEGraph's latent; g_lv None there),
+    with the gradients the fused loss stashed -> the parameters' gradients in param_list() order (None: did not take part)."""
+    flags = [False] * len(g_outs)
+    lg = state.loss_grads
+    if lg is not None and lg.armed:                              # the loss handle's backward ran: its gradients are the ones to use
+        if lg.scale is not None:                                 # None: unit_grad promised by the caller (fused_loss)
+            ops.scale_many(list(lg.g_outs) + [lg.g_mu, lg.g_lv], lg.scale)       # one launch, not five
+        for i, sg in enumerate(lg.g_outs):
+            if sg is None:
+                continue
+            if g_outs[i] is not None:            # rare: another loss term also touched this output
+                sg[:, :g_outs[i].shape[1]] += _to_stash_space(g_outs[i], state.dec[i][1], graph.decoders[i], sg.dtype)
+            g_outs[i], flags[i] = sg, graph.decoders[i].final_sigmoid
+        if lg.g_mu is not None:                  # None: an AEGraph's forward -- the loss has no term on the latent
             for sg, cur in ((lg.g_mu, g_mu), (lg.g_lv, g_lv)):
                 if cur is not None:
                     sg += cur
             g_mu, g_lv = lg.g_mu, lg.g_lv
-        flat, grads = graph.backward(state, g_outs, flags, g_mu, g_lv)
-        state.consumed = True
-        used = _participating(graph, state, g_outs)
-        out = [grads[p] if id(p) in used else None for p in graph.param_list()]
-        del grads                                     # keep the views unique so autograd can adopt them
-        return (None, None, None, None, None, None, None, *out)
+    flat, grads = graph.backward(state, g_outs, flags, g_mu, g_lv)
+    state.consumed = True
+    used = _participating(graph, state, g_outs)
+    out = [grads[p] if id(p) in used else None for p in graph.param_list()]
+    del grads                                     # keep the views unique so autograd can adopt them
+    return out
+
+
+class AEGraphFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, graph, prec, train, want_bwd, x_a, x_b, site, *params):
+        ctx.set_materialize_grads(False)
+        outs, latent, state = graph.forward(prec, x_a, x_b, site, train, want_bwd)
+        ctx.graph, ctx.saved, ctx.n_out = graph, state, len(outs)
+        graph._last_saved = state
+        return (*outs, latent)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *gs):
+        graph, state, n_out = ctx.graph, ctx.saved, ctx.n_out
+        if state.consumed:
+            raise RuntimeError("backward through this forward was already run (buffers are not retained)")
+        g_outs = [None if g is None else _as_rows(g) for g in gs[:n_out]]
+        g_latent = None if gs[n_out] is None else gs[n_out].contiguous().float()
+        return (None, None, None, None, None, None, None, *_graph_backward(graph, state, g_outs, g_latent, None))
 
 
 def _as_rows(g):
@@ -88,7 +115,7 @@ def _participating(graph, state, g_outs):
 class OutTag(NamedTuple):
     """Marks a tensor that run_graph returned (`t._mmvae`): the forward that made it and which of its outputs it is."""
     state: engine.StepState
-    kind: str                       # "out" (a decoder's output) | "mu" | "logvar"
+    kind: str                       # "out" (a decoder's output) | "mu" | "logvar" | "latent" (an AEGraph's)
     index: int                      # the decoder, for "out"
 
 
@@ -109,6 +136,23 @@ def run_graph(graph, prec, train, xa, xb, site):
         mu._mmvae = OutTag(state, "mu", 0)
         logvar._mmvae = OutTag(state, "logvar", 0)
     return outs, mu, logvar
+
+
+def run_ae_graph(graph, prec, train, x_a, x_b, site):
+    """Forward of an engine.AEGraph with autograd wiring (x_a: RNA for a graph with an RNA encoder, x_b: DNA for one with a DNA
+    encoder; either and the site may be None).  Returns (outs, latent)."""
+    params = graph.param_list()
+    want_bwd = train and torch.is_grad_enabled() and any(p.requires_grad for p in params)
+    res = AEGraphFn.apply(graph, prec, train, want_bwd, x_a, x_b, site, *params)
+    n = len(graph.decoders)
+    outs, latent = list(res[:n]), res[n]
+    state = graph._last_saved
+    graph._last_saved = None
+    if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+        for i, o in enumerate(outs):
+            o._mmvae = OutTag(state, "out", i)
+        latent._mmvae = OutTag(state, "latent", 0)
+    return outs, latent
 
 
 # --------------------------------------------------------------------------------------------
@@ -252,7 +296,8 @@ def _fused_loss(terms, beta, gamma, class_weights=None, unit_grad=False, beta_ga
         sums = out4 = None                                 # out4: [total, recon, class, kld, labels out of range]
 
     # ---- fused hand-off: all differentiable inputs are outputs of ONE forward of our model --------------------
-    tags = [_tag_of(t) for t in (ra, rb, lg_real, mu, lv) if t is not None and t.requires_grad]
+    # (the placeholders count: an autoencoder's step has no other differentiable input once its one reconstruction term is fused)
+    tags = [_tag_of(t) for t in (ra, rb, lg_real, mu, lv) if t is not None and t.requires_grad] + [_tag_of(t) for t in placeholders]
     state = tags[0].state if tags and all(t is not None and t.state is tags[0].state for t in tags) else None
     if need_grad and state is not None and not state.consumed and state.loss_grads is None:
         if sums is None:
@@ -300,7 +345,7 @@ def _fused_loss(terms, beta, gamma, class_weights=None, unit_grad=False, beta_ga
             state.loss_tail = (sums, beta, gamma, out4, beta_gamma_dev)
         else:
             ops.loss_finalize(sums, beta, gamma, out4, beta_gamma_dev)
-        if g_mu is None:                       # KL term absent: nothing flows into mu/logvar from this loss
+        if g_mu is None and state.logvar is not None:      # KL term absent: nothing flows into mu/logvar from this loss (an AEGraph has neither)
             g_mu = torch.zeros(B, state.logvar.shape[1], dtype=torch.float32, device=dev)
             g_lv = torch.zeros_like(g_mu)
         state.loss_grads = engine.LossGrads(g_outs=g_outs, g_mu=g_mu, g_lv=g_lv, unit_grad=bool(unit_grad))

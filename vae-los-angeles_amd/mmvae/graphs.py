@@ -26,7 +26,7 @@ from . import functional as F_
 
 
 class GraphedTrainStep:
-    KINDS = ("multimodal", "dna2rna", "rna2dna")
+    KINDS = ("multimodal", "dna2rna", "rna2dna", "dna2rna_ae", "rna2dna_ae")
 
     def __init__(self, model, optimizer, a=None, b=None, site=None, beta=1e-3, gamma=1.0, class_weights=None, warmup=3, reduce=None,
                  preserve_state=False, kind="multimodal", dataset=None, batch_size=None, overlap=True):
@@ -34,6 +34,8 @@ class GraphedTrainStep:
              "multimodal": model(a=, b=, site=) + vae_loss                      (optimize_hyperparameters.py:106-110)
              "dna2rna":    model(dna=b, site=) + dna2rna_loss(recon_rna, a, ..)  (train_dna2rna.py:86-92)
              "rna2dna":    model(rna=a, site=) + rna2dna_loss(recon_dna, b, ..)  (train_rna2dna.py, same lines)
+             "dna2rna_ae" / "rna2dna_ae": the autoencoders' loop, model(dna=b / rna=a, site=) + dna2rna_ae_loss / rna2dna_ae_loss
+                           (vae_cross_modality_cv.py:225-237): the reconstruction term alone, beta = 0; losses() reports kld = 0
            dataset=(A, B, SITE) device-resident full tensors + batch_size: the static batch buffers are owned here and every step
            begins with ONE gather launch through `self.index` (int64 (batch_size,)); call `set_indices(idx)` before a step.
            A / B may be in bf16 storage (mmvae.to_bf16_rows): the static buffers then get the same padded-row layout and the gather
@@ -104,6 +106,12 @@ class GraphedTrainStep:
                 g.fused_recon = [self.a]
                 rec, mu, lv = self.model(dna=self.b, site=self.site)
                 terms = {"a": (rec, self.a), "kl": (mu, lv)}
+            elif self.kind == "dna2rna_ae":
+                g.fused_recon = [self.a]
+                terms = {"a": (self.model(dna=self.b, site=self.site)[0], self.a)}
+            elif self.kind == "rna2dna_ae":
+                g.fused_recon = [self.b]
+                terms = {"b": (self.model(rna=self.a, site=self.site)[0], self.b)}
             else:
                 g.fused_recon = [self.b]
                 rec, mu, lv = self.model(rna=self.a, site=self.site)
@@ -112,6 +120,8 @@ class GraphedTrainStep:
             g.fused_recon = None
             g.defer_class_head = False
             g.tail_riders = False
+        if self.kind.endswith("_ae"):                   # no KL term: beta = 0 by value, the device pair is not consulted
+            return F_.fused_loss(terms, 0.0, self.gamma, None, unit_grad=True)
         return F_.fused_loss(terms, self.beta, self.gamma, self.class_weights, unit_grad=True, beta_gamma_dev=self.hyper)
 
     def run_eager(self):

@@ -577,6 +577,75 @@ def fuse_reparam_bwd(B, Ld, n_mod, g_mu, g_lv, dzs, eps, logvar, d_heads, d_tabl
         L.check(L.load().mmvae_fuse_reparam_bwd(C.byref(a), _stream()), "mmvae_fuse_reparam_bwd")
 
 
+def embed_proj_fwd(emb, w, b, table):
+    """table (S, L) = emb (S, E) @ w (L, E)^T + b: the autoencoders' Embedding -> Linear, the one-head case of embed_table_fwd."""
+    S, E = emb.shape
+    L.check(L.load().mmvae_embed_proj_fwd(S, E, w.shape[0], emb.data_ptr(), w.data_ptr(), b.data_ptr(), table.data_ptr(), _stream()),
+            "mmvae_embed_proj_fwd")
+
+
+def embed_proj_bwd(emb, w, d_table, d_emb, d_w, d_b):
+    """d_table: (S, L) or (copies, S, L) (the copies fuse_mean_bwd scattered into; summed here); d_emb, d_w, d_b are accumulated into."""
+    S, E = emb.shape
+    copies = d_table.shape[0] if d_table.dim() == 3 else 1
+    L.check(L.load().mmvae_embed_proj_bwd(S, E, w.shape[0], emb.data_ptr(), w.data_ptr(), d_table.data_ptr(), copies,
+                                          d_emb.data_ptr(), d_w.data_ptr(), d_b.data_ptr(), _stream()), "mmvae_embed_proj_bwd")
+
+
+def fuse_mean_fwd(B, Ld, head, table, site, latent, z):
+    """latent (B, Ld) fp32 contiguous = the mean of the modalities present (head (B, >= Ld) fp32, the table row of site); z: the same in
+    the activation type, pad columns zeroed."""
+    if tuple(latent.shape) != (B, Ld) or not latent.is_contiguous() or latent.dtype != torch.float32:
+        raise ValueError(f"fuse_mean_fwd: latent must be contiguous fp32 ({B}, {Ld}), got {tuple(latent.shape)} / {latent.stride()}")
+    n_mod = (head is not None) + (table is not None)
+    a = L.FuseMeanFwdArgs(B, Ld, n_mod, _p(head), _ld(head) if head is not None else 0,
+                          _p(table), _p(site), table.shape[0] if table is not None else 0,
+                          latent.data_ptr(), z.data_ptr(), _dt(z), _ld(z))
+    with stream_span("fuse_mean_fwd", B * (4 * Ld * (head is not None) + 8 * (table is not None) + 4 * Ld + z.element_size() * _ld(z))):
+        L.check(L.load().mmvae_fuse_mean_fwd(C.byref(a), _stream()), "mmvae_fuse_mean_fwd")
+
+
+def fuse_mean_bwd(B, Ld, n_mod, dz, g_latent, d_head, d_table, site, d_head_lp=None):
+    """d_head (B, >= Ld) fp32 = (dz + g_latent) / n_mod (g_latent: contiguous (B, Ld) fp32 or None), the optional bf16 copy d_head_lp, and
+    the scatter-add into the zeroed d_table (S, Ld) or (copies, S, Ld) by site."""
+    if g_latent is not None and (tuple(g_latent.shape) != (B, Ld) or not g_latent.is_contiguous() or g_latent.dtype != torch.float32):
+        raise ValueError(f"fuse_mean_bwd: g_latent must be contiguous fp32 ({B}, {Ld})")
+    copies = d_table.shape[0] if (d_table is not None and d_table.dim() == 3) else 1
+    a = L.FuseMeanBwdArgs(B, Ld, n_mod, dz.data_ptr(), _ld(dz), _p(g_latent), d_head.data_ptr(), _ld(d_head),
+                          _p(d_head_lp), _ld(d_head_lp) if d_head_lp is not None else 0,
+                          _p(d_table), _p(site), d_table.shape[-2] if d_table is not None else 0, copies)
+    with stream_span("fuse_mean_bwd", B * Ld * 4 * (2 + (g_latent is not None) + 1)):
+        L.check(L.load().mmvae_fuse_mean_bwd(C.byref(a), _stream()), "mmvae_fuse_mean_bwd")
+
+
+def ae_latent_fwd_args(prec, B, Ld, enc, table, site, latent, z, first, h0):
+    """-> (AELatentFwdArgs of mmvae_ae_latent_fwd, its algorithmic HBM bytes).  The struct holds addresses only."""
+    a = L.AELatentFwdArgs()
+    a.prec, a.B, a.L = prec, B, Ld
+    a.n_mod = (enc is not None) + (table is not None)
+    nbytes = 4 * Ld + z.element_size() * _ld(z) + h0.element_size() * first.N + 8 * (table is not None)
+    if enc is not None:
+        _latent_enc(a.enc, enc)
+        nbytes += enc.heads.K * (enc.y.element_size() + (enc.prologue[2] is not None))
+    if table is not None:
+        a.table, a.site, a.S = table.data_ptr(), _p(site), table.shape[0]
+    a.latent, a.z, a.ldz = latent.data_ptr(), z.data_ptr(), _ld(z)
+    a.w_stem, a.ldw_stem, a.bias_stem, a.N_stem = first.w.data_ptr(), first.w.stride(0), _p(first.bias), first.N
+    a.h0, a.ldh0 = h0.data_ptr(), _ld(h0)
+    return a, B * nbytes
+
+
+def ae_latent_fwd(prec, B, Ld, enc, table, site, latent, z, first, h0):
+    """mmvae_ae_latent_fwd: the head of the encoder (a LatentEncoder or None), the plain mean with the site's table row and the decoder's
+    first layer (`first`, a PreparedLinear; h0 = relu(z @ first^T + b)) in ONE launch.  latent is contiguous fp32 (B, Ld).  Raises
+    MMVAEArgError, with nothing enqueued, for what the kernel does not take: the caller then issues the three launches it replaces."""
+    if tuple(latent.shape) != (B, Ld) or not latent.is_contiguous() or latent.dtype != torch.float32:
+        raise ValueError(f"ae_latent_fwd: latent must be contiguous fp32 ({B}, {Ld}), got {tuple(latent.shape)} / {latent.stride()}")
+    a, nbytes = ae_latent_fwd_args(prec, B, Ld, enc, table, site, latent, z, first, h0)
+    with stream_span("ae_latent.fwd", nbytes):
+        L.check(L.load().mmvae_ae_latent_fwd(C.byref(a), _stream()), "mmvae_ae_latent_fwd")
+
+
 def loss_workspace(device):
     """-> (sums float64[5] zeroed, out5 float32[5]): the accumulators of mmvae_vae_loss and the tuple mmvae_loss_finalize makes of them."""
     buf = torch.zeros(5 * 8 + 5 * 4 + 4, dtype=torch.uint8, device=device)
