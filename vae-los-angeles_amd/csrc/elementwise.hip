@@ -195,25 +195,17 @@ __device__ __forceinline__ void embed_table_fwd_elems(int S, int E, int L, const
     }
 }
 
+template <int HEADS>
 __global__ __launch_bounds__(256) void embed_table_fwd_kernel(int S, int E, int L, const float* emb, const float* w_mu,
                                                                const float* b_mu, const float* w_lv, const float* b_lv, float* table) {
-    embed_table_fwd_elems(S, E, L, emb, w_mu, b_mu, w_lv, b_lv, table, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+    embed_table_fwd_elems<HEADS>(S, E, L, emb, w_mu, b_mu, w_lv, b_lv, table, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
 }
 
 // the body (and why it stages everything in LDS first): tail_riders.h, shared with the rider workgroups of the grouped dW launch
+template <int HEADS>
 __global__ __launch_bounds__(256) void embed_table_bwd_kernel(const EmbedBwd a) {
     extern __shared__ float sm[];
-    embed_table_bwd_body(a, blockIdx.x, gridDim.x, sm);
-}
-
-// the one-head case of the two kernels above: the autoencoders' Embedding -> Linear(embed, latent)
-__global__ __launch_bounds__(256) void embed_proj_fwd_kernel(int S, int E, int L, const float* emb, const float* w, const float* b, float* table) {
-    embed_table_fwd_elems<1>(S, E, L, emb, w, b, nullptr, nullptr, table, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
-}
-
-__global__ __launch_bounds__(256) void embed_proj_bwd_kernel(const EmbedBwd a) {
-    extern __shared__ float sm[];
-    embed_table_bwd_body<1>(a, blockIdx.x, gridDim.x, sm);
+    embed_table_bwd_body<HEADS>(a, blockIdx.x, gridDim.x, sm);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -245,61 +237,6 @@ __global__ __launch_bounds__(256) void fuse_fwd_kernel(mmvae_fuse_fwd_args a) {
     }
 }
 
-__global__ __launch_bounds__(256) void fuse_bwd_kernel(mmvae_fuse_bwd_args a, int rows_per_block, int use_lds) {
-    extern __shared__ float sT[];                 // [S][2L] when use_lds
-    const int L2 = 2 * a.L;
-    if (use_lds) { for (int i = threadIdx.x; i < a.S * L2; i += blockDim.x) sT[i] = 0.f; __syncthreads(); }
-    const int b0 = blockIdx.x * rows_per_block, b1 = min(a.B, b0 + rows_per_block);
-    float* dtab = a.d_table ? a.d_table + (long)(blockIdx.x % (a.table_copies > 0 ? a.table_copies : 1)) * a.S * L2 : nullptr;
-    const float inv_n = 1.f / (float)a.n_mod;
-    // U elements per thread are loaded before any is processed (stores may alias loads for the compiler): with one element
-    // per iteration a thread had ~7 dependent-latency loads in flight at a time and the launch was latency-bound (43 us for 40 MB)
-    constexpr int U = 4;
-    const long iend = (long)b1 * a.L;
-    for (long i0 = (long)b0 * a.L + threadIdx.x; i0 < iend; i0 += (long)U * blockDim.x) {
-        float dz[U], gm[U], gl[U], ep[U], lv[U];
-        int bb[U], ll[U];
-        long sidx[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const long i = min(i0 + (long)u * blockDim.x, iend - 1);        // clamped: the loads always issue
-            const int b = (int)(i / a.L), l = (int)(i - (long)b * a.L);
-            bb[u] = b; ll[u] = l;
-            dz[u] = a.dz[(long)b * a.lddz + l];
-            if (a.dz2) dz[u] += a.dz2[(long)b * a.lddz + l];
-            if (a.dz3) dz[u] += a.dz3[(long)b * a.lddz + l];
-            gm[u] = a.g_mu ? a.g_mu[i] : 0.f; gl[u] = a.g_lv ? a.g_lv[i] : 0.f;
-            ep[u] = a.eps[i]; lv[u] = a.logvar[i];
-            sidx[u] = a.d_table ? a.site[b] : 0;
-            if (sidx[u] < 0 || sidx[u] >= a.S) sidx[u] = -1;                  // out of range: no scatter (the forward poisoned the row)
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            if (i0 + (long)u * blockDim.x >= iend) break;
-            const int b = bb[u], l = ll[u];
-            float dmu = gm[u] + dz[u];
-            float dlv = gl[u] + dz[u] * ep[u] * expf(0.5f * lv[u]) * 0.5f;
-            if (a.n_mod > 1) { dmu *= inv_n; dlv *= inv_n; }
-            a.d_heads[(long)b * a.ld_heads + l] = dmu;
-            a.d_heads[(long)b * a.ld_heads + a.L + l] = dlv;
-            if (a.d_heads_lp) {
-                bf16* lp = (bf16*)a.d_heads_lp + (long)b * a.ld_heads_lp;
-                lp[l] = (bf16)dmu; lp[a.L + l] = (bf16)dlv;
-                if (l == 0) for (int e = 2 * a.L; e < a.ld_heads_lp; ++e) lp[e] = (bf16)0.f;       // pad columns
-            }
-            if (a.d_table && sidx[u] >= 0) {
-                const long sx = sidx[u];
-                if (use_lds) { atomicAdd(&sT[sx * L2 + l], dmu); atomicAdd(&sT[sx * L2 + a.L + l], dlv); }
-                else { unsafeAtomicAdd(&dtab[sx * L2 + l], dmu); unsafeAtomicAdd(&dtab[sx * L2 + a.L + l], dlv); }
-            }
-        }
-    }
-    if (use_lds && a.d_table) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < a.S * L2; i += blockDim.x) if (sT[i] != 0.f) unsafeAtomicAdd(&dtab[i], sT[i]);
-    }
-}
-
 // ------------------------------------------------------------------------------------------
 // the autoencoders' fusion: the plain mean of the encoder's head and the site's table row (no eps, no logvar)
 // ------------------------------------------------------------------------------------------
@@ -327,17 +264,68 @@ __global__ __launch_bounds__(256) void fuse_mean_fwd_kernel(mmvae_fuse_mean_fwd_
     }
 }
 
-// fuse_bwd_kernel without the reparameterisation: one head, d_table is [copies][S][L]
-__global__ __launch_bounds__(256) void fuse_mean_bwd_kernel(mmvae_fuse_mean_bwd_args a, int rows_per_block, int use_lds) {
-    extern __shared__ float sT[];                 // [S][L] when use_lds
-    if (use_lds) { for (int i = threadIdx.x; i < a.S * a.L; i += blockDim.x) sT[i] = 0.f; __syncthreads(); }
+// ------------------------------------------------------------------------------------------
+// backward of both fusions: one kernel on an element policy
+// ------------------------------------------------------------------------------------------
+// What the kernel needs whatever the element arithmetic: d_heads is [B][>= HEADS * L] (head h of latent l in column h * L + l),
+// d_heads_lp its optional bf16 copy, d_table [copies][S][HEADS * L] the zeroed table gradient the same rows are scattered into by site.
+struct FuseBwd {
+    int B, L, n_mod;
+    float* d_heads; long ld_heads;
+    float* d_table; const int64_t* site; int S;
+    bf16* d_heads_lp; long ld_heads_lp;
+    int copies;
+};
+
+// The element policies, in the manner of gemm_src.h's operand sources: fetch() requests what element (b, l), i = b * L + l, needs and
+// finish() turns it into the element's HEADS gradients -- the kernel calls fetch() for all its elements before the first finish().
+struct FuseReparamBwd {                           // mean fusion + reparameterisation: d_mu | d_logvar
+    static constexpr int HEADS = 2;
+    const float* g_mu; const float* g_lv; const float* dz; const float* dz2; const float* dz3; long lddz;
+    const float* eps; const float* logvar;
+    struct Raw { float dz, gm, gl, ep, lv; };
+    __device__ __forceinline__ void fetch(Raw& r, int b, int l, long i) const {
+        const long o = (long)b * lddz + l;
+        r.dz = dz[o];
+        if (dz2) r.dz += dz2[o];
+        if (dz3) r.dz += dz3[o];
+        r.gm = g_mu ? g_mu[i] : 0.f; r.gl = g_lv ? g_lv[i] : 0.f;
+        r.ep = eps[i]; r.lv = logvar[i];
+    }
+    __device__ __forceinline__ void finish(const Raw& r, int n_mod, float inv_n, float (&d)[HEADS]) const {
+        float dmu = r.gm + r.dz;
+        float dlv = r.gl + r.dz * r.ep * expf(0.5f * r.lv) * 0.5f;
+        if (n_mod > 1) { dmu *= inv_n; dlv *= inv_n; }
+        d[0] = dmu; d[1] = dlv;
+    }
+};
+
+struct FuseMeanBwd {                              // the autoencoders' plain mean: one head, no eps, no logvar
+    static constexpr int HEADS = 1;
+    const float* dz; long lddz; const float* g_latent;
+    struct Raw { float dz; };
+    __device__ __forceinline__ void fetch(Raw& r, int b, int l, long i) const {
+        r.dz = dz[(long)b * lddz + l];
+        if (g_latent) r.dz += g_latent[i];
+    }
+    __device__ __forceinline__ void finish(const Raw& r, int n_mod, float inv_n, float (&d)[HEADS]) const { d[0] = fuse_mean_elem(r.dz, n_mod, inv_n); }
+};
+
+template <typename P>
+__global__ __launch_bounds__(256) void fuse_bwd_kernel(const FuseBwd a, const P p, int rows_per_block, int use_lds) {
+    constexpr int H = P::HEADS;
+    extern __shared__ float sT[];                 // [S][H * L] when use_lds
+    const int LW = H * a.L;
+    if (use_lds) { for (int i = threadIdx.x; i < a.S * LW; i += blockDim.x) sT[i] = 0.f; __syncthreads(); }
     const int b0 = blockIdx.x * rows_per_block, b1 = min(a.B, b0 + rows_per_block);
-    float* dtab = a.d_table ? a.d_table + (long)(blockIdx.x % (a.table_copies > 0 ? a.table_copies : 1)) * a.S * a.L : nullptr;
+    float* dtab = a.d_table ? a.d_table + (long)(blockIdx.x % (a.copies > 0 ? a.copies : 1)) * a.S * LW : nullptr;
     const float inv_n = 1.f / (float)a.n_mod;
-    constexpr int U = 4;                          // loads first, as fuse_bwd_kernel
+    // U elements per thread are loaded before any is processed (stores may alias loads for the compiler): with one element
+    // per iteration a thread had ~7 dependent-latency loads in flight at a time and the launch was latency-bound (43 us for 40 MB)
+    constexpr int U = 4;
     const long iend = (long)b1 * a.L;
+    typename P::Raw raw[U];                       // out here, not in the loop: one VGPR less in the two-head form (63, as before the policies)
     for (long i0 = (long)b0 * a.L + threadIdx.x; i0 < iend; i0 += (long)U * blockDim.x) {
-        float dz[U];
         int bb[U], ll[U];
         long sidx[U];
 #pragma unroll
@@ -345,8 +333,7 @@ __global__ __launch_bounds__(256) void fuse_mean_bwd_kernel(mmvae_fuse_mean_bwd_
             const long i = min(i0 + (long)u * blockDim.x, iend - 1);        // clamped: the loads always issue
             const int b = (int)(i / a.L), l = (int)(i - (long)b * a.L);
             bb[u] = b; ll[u] = l;
-            dz[u] = a.dz[(long)b * a.lddz + l];
-            if (a.g_latent) dz[u] += a.g_latent[i];
+            p.fetch(raw[u], b, l, i);
             sidx[u] = a.d_table ? a.site[b] : 0;
             if (sidx[u] < 0 || sidx[u] >= a.S) sidx[u] = -1;                  // out of range: no scatter (the forward poisoned the row)
         }
@@ -354,22 +341,31 @@ __global__ __launch_bounds__(256) void fuse_mean_bwd_kernel(mmvae_fuse_mean_bwd_
         for (int u = 0; u < U; ++u) {
             if (i0 + (long)u * blockDim.x >= iend) break;
             const int b = bb[u], l = ll[u];
-            const float d = fuse_mean_elem(dz[u], a.n_mod, inv_n);
-            a.d_head[(long)b * a.ld_head + l] = d;
-            if (a.d_head_lp) {
-                bf16* lp = (bf16*)a.d_head_lp + (long)b * a.ld_head_lp;
-                lp[l] = (bf16)d;
-                if (l == 0) for (int e = a.L; e < a.ld_head_lp; ++e) lp[e] = (bf16)0.f;       // pad columns
+            float d[H];
+            p.finish(raw[u], a.n_mod, inv_n, d);
+#pragma unroll
+            for (int h = 0; h < H; ++h) a.d_heads[(long)b * a.ld_heads + (h * a.L + l)] = d[h];
+            if (a.d_heads_lp) {
+                bf16* lp = a.d_heads_lp + (long)b * a.ld_heads_lp;
+#pragma unroll
+                for (int h = 0; h < H; ++h) lp[h * a.L + l] = (bf16)d[h];
+                if (l == 0) for (int e = LW; e < a.ld_heads_lp; ++e) lp[e] = (bf16)0.f;       // pad columns
             }
             if (a.d_table && sidx[u] >= 0) {
-                if (use_lds) atomicAdd(&sT[sidx[u] * a.L + l], d);
-                else unsafeAtomicAdd(&dtab[sidx[u] * a.L + l], d);
+                const long sx = sidx[u];
+                if (use_lds) {
+#pragma unroll
+                    for (int h = 0; h < H; ++h) atomicAdd(&sT[sx * LW + (h * a.L + l)], d[h]);
+                } else {
+#pragma unroll
+                    for (int h = 0; h < H; ++h) unsafeAtomicAdd(&dtab[sx * LW + (h * a.L + l)], d[h]);
+                }
             }
         }
     }
     if (use_lds && a.d_table) {
         __syncthreads();
-        for (int i = threadIdx.x; i < a.S * a.L; i += blockDim.x) if (sT[i] != 0.f) unsafeAtomicAdd(&dtab[i], sT[i]);
+        for (int i = threadIdx.x; i < a.S * LW; i += blockDim.x) if (sT[i] != 0.f) unsafeAtomicAdd(&dtab[i], sT[i]);
     }
 }
 
@@ -1012,25 +1008,48 @@ extern "C" int mmvae_bn_bwd_finalize_apply(int32_t dtype, int32_t M, int32_t N, 
     return 0;
 }
 
+// the launches of the site table, HEADS = 2 (EncoderC) or 1 (the autoencoders); w_lv / b_lv and their gradients are not read at 1
+template <int HEADS>
+static int launch_embed_table_fwd(int S, int E, int L, const float* emb, const float* w_mu, const float* b_mu, const float* w_lv,
+                                  const float* b_lv, float* table, void* stream) {
+    hipLaunchKernelGGL(embed_table_fwd_kernel<HEADS>, dim3((S * HEADS * L + 63) / 64), dim3(64), 0, (hipStream_t)stream, S, E, L, emb, w_mu, b_mu, w_lv, b_lv, table);
+    MM_CHECK_LAUNCH();
+    return 0;
+}
+
+template <int HEADS>
+static int launch_embed_table_bwd(EmbedBwd a, void* stream) {
+    if (a.copies < 1) a.copies = 1;
+    const size_t lds = embed_bwd_lds(a.S, a.E, a.L, HEADS);
+    if (lds > EMBED_BWD_LDS_MAX) return MMVAE_ERR_ARG;
+    hipLaunchKernelGGL(embed_table_bwd_kernel<HEADS>, dim3(embed_bwd_blocks(a.S, a.E, a.L, HEADS)), dim3(256), lds, (hipStream_t)stream, a);
+    MM_CHECK_LAUNCH();
+    return 0;
+}
+
 extern "C" int mmvae_embed_table_fwd(int32_t S, int32_t E, int32_t L, const float* emb, const float* w_mu, const float* b_mu,
                                      const float* w_lv, const float* b_lv, float* table, void* stream) {
     if (S <= 0 || E <= 0 || L <= 0 || !emb || !w_mu || !b_mu || !w_lv || !b_lv || !table) return MMVAE_ERR_ARG;
-    hipLaunchKernelGGL(embed_table_fwd_kernel, dim3((S * 2 * L + 63) / 64), dim3(64), 0, (hipStream_t)stream, S, E, L, emb, w_mu, b_mu, w_lv, b_lv, table);
-    MM_CHECK_LAUNCH();
-    return 0;
+    return launch_embed_table_fwd<2>(S, E, L, emb, w_mu, b_mu, w_lv, b_lv, table, stream);
 }
 
 extern "C" int mmvae_embed_table_bwd(int32_t S, int32_t E, int32_t L, const float* emb, const float* w_mu, const float* w_lv,
                                      const float* d_table, int32_t table_copies, float* d_emb, float* d_w_mu, float* d_b_mu, float* d_w_lv,
                                      float* d_b_lv, void* stream) {
     if (S <= 0 || E <= 0 || L <= 0 || !emb || !w_mu || !w_lv || !d_table || !d_emb || !d_w_mu || !d_b_mu || !d_w_lv || !d_b_lv) return MMVAE_ERR_ARG;
-    if (table_copies < 1) table_copies = 1;
-    const size_t lds = embed_bwd_lds(S, E, L);
-    if (lds > EMBED_BWD_LDS_MAX) return MMVAE_ERR_ARG;
-    const EmbedBwd a{S, E, L, table_copies, emb, w_mu, w_lv, d_table, d_emb, d_w_mu, d_b_mu, d_w_lv, d_b_lv};
-    hipLaunchKernelGGL(embed_table_bwd_kernel, dim3(embed_bwd_blocks(S, E, L)), dim3(256), lds, (hipStream_t)stream, a);
-    MM_CHECK_LAUNCH();
-    return 0;
+    return launch_embed_table_bwd<2>(EmbedBwd{S, E, L, table_copies, emb, w_mu, w_lv, d_table, d_emb, d_w_mu, d_b_mu, d_w_lv, d_b_lv}, stream);
+}
+
+extern "C" int mmvae_embed_proj_fwd(int32_t S, int32_t E, int32_t L, const float* emb, const float* w, const float* b, float* table,
+                                    void* stream) {
+    if (S <= 0 || E <= 0 || L <= 0 || !emb || !w || !b || !table) return MMVAE_ERR_ARG;
+    return launch_embed_table_fwd<1>(S, E, L, emb, w, b, nullptr, nullptr, table, stream);
+}
+
+extern "C" int mmvae_embed_proj_bwd(int32_t S, int32_t E, int32_t L, const float* emb, const float* w, const float* d_table,
+                                    int32_t table_copies, float* d_emb, float* d_w, float* d_b, void* stream) {
+    if (S <= 0 || E <= 0 || L <= 0 || !emb || !w || !d_table || !d_emb || !d_w || !d_b) return MMVAE_ERR_ARG;
+    return launch_embed_table_bwd<1>(EmbedBwd{S, E, L, table_copies, emb, w, nullptr, d_table, d_emb, d_w, d_b, nullptr, nullptr}, stream);
 }
 
 extern "C" int mmvae_fuse_reparam_fwd(const mmvae_fuse_fwd_args* a, void* stream) {
@@ -1041,38 +1060,6 @@ extern "C" int mmvae_fuse_reparam_fwd(const mmvae_fuse_fwd_args* a, void* stream
     const int grid = grid_for((long)a->B * a->ldz);
     if (a->z_dtype == MMVAE_BF16) hipLaunchKernelGGL(fuse_fwd_kernel<bf16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, *a);
     else hipLaunchKernelGGL(fuse_fwd_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, *a);
-    MM_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int mmvae_fuse_reparam_bwd(const mmvae_fuse_bwd_args* a, void* stream) {
-    if (!a || a->B <= 0 || a->L <= 0 || a->n_mod <= 0 || !a->dz || !a->eps || !a->logvar || !a->d_heads) return MMVAE_ERR_ARG;
-    if (a->d_table && (!a->site || a->S <= 0)) return MMVAE_ERR_ARG;
-    const int rows_per_block = 128;          // 512 workgroups at B = 65 536: two per CU
-    const int grid = (a->B + rows_per_block - 1) / rows_per_block;
-    const size_t lds = a->d_table ? (size_t)a->S * 2 * a->L * sizeof(float) : 0;
-    const int use_lds = lds > 0 && lds <= 48 * 1024;
-    hipLaunchKernelGGL(fuse_bwd_kernel, dim3(grid), dim3(256), use_lds ? lds : 0, (hipStream_t)stream, *a, rows_per_block, use_lds);
-    MM_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int mmvae_embed_proj_fwd(int32_t S, int32_t E, int32_t L, const float* emb, const float* w, const float* b, float* table,
-                                    void* stream) {
-    if (S <= 0 || E <= 0 || L <= 0 || !emb || !w || !b || !table) return MMVAE_ERR_ARG;
-    hipLaunchKernelGGL(embed_proj_fwd_kernel, dim3((S * L + 63) / 64), dim3(64), 0, (hipStream_t)stream, S, E, L, emb, w, b, table);
-    MM_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int mmvae_embed_proj_bwd(int32_t S, int32_t E, int32_t L, const float* emb, const float* w, const float* d_table,
-                                    int32_t table_copies, float* d_emb, float* d_w, float* d_b, void* stream) {
-    if (S <= 0 || E <= 0 || L <= 0 || !emb || !w || !d_table || !d_emb || !d_w || !d_b) return MMVAE_ERR_ARG;
-    if (table_copies < 1) table_copies = 1;
-    const size_t lds = embed_bwd_lds(S, E, L, 1);
-    if (lds > EMBED_BWD_LDS_MAX) return MMVAE_ERR_ARG;
-    const EmbedBwd a{S, E, L, table_copies, emb, w, nullptr, d_table, d_emb, d_w, d_b, nullptr, nullptr};
-    hipLaunchKernelGGL(embed_proj_bwd_kernel, dim3(embed_bwd_blocks(S, E, L, 1)), dim3(256), lds, (hipStream_t)stream, a);
     MM_CHECK_LAUNCH();
     return 0;
 }
@@ -1091,17 +1078,31 @@ extern "C" int mmvae_fuse_mean_fwd(const mmvae_fuse_mean_fwd_args* a, void* stre
     return 0;
 }
 
+// the launch of both fusion backwards: the table gradient goes through LDS when one copy of its true width fits 48 KiB
+template <typename P>
+static int launch_fuse_bwd(const FuseBwd& a, const P& p, void* stream) {
+    const int rows_per_block = 128;          // 512 workgroups at B = 65 536: two per CU
+    const int grid = (a.B + rows_per_block - 1) / rows_per_block;
+    const size_t lds = a.d_table ? (size_t)a.S * P::HEADS * a.L * sizeof(float) : 0;
+    const int use_lds = lds > 0 && lds <= 48 * 1024;
+    hipLaunchKernelGGL(fuse_bwd_kernel<P>, dim3(grid), dim3(256), use_lds ? lds : 0, (hipStream_t)stream, a, p, rows_per_block, use_lds);
+    MM_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int mmvae_fuse_reparam_bwd(const mmvae_fuse_bwd_args* a, void* stream) {
+    if (!a || a->B <= 0 || a->L <= 0 || a->n_mod <= 0 || !a->dz || !a->eps || !a->logvar || !a->d_heads) return MMVAE_ERR_ARG;
+    if (a->d_table && (!a->site || a->S <= 0)) return MMVAE_ERR_ARG;
+    const FuseBwd k{a->B, a->L, a->n_mod, a->d_heads, a->ld_heads, a->d_table, a->site, a->S, (bf16*)a->d_heads_lp, a->ld_heads_lp, a->table_copies};
+    return launch_fuse_bwd(k, FuseReparamBwd{a->g_mu, a->g_lv, a->dz, a->dz2, a->dz3, a->lddz, a->eps, a->logvar}, stream);
+}
+
 extern "C" int mmvae_fuse_mean_bwd(const mmvae_fuse_mean_bwd_args* a, void* stream) {
     if (!a || a->B <= 0 || a->L <= 0 || a->n_mod < 1 || a->n_mod > 2 || !a->dz || a->lddz < a->L || !a->d_head || a->ld_head < a->L) return MMVAE_ERR_ARG;
     if (a->d_head_lp && a->ld_head_lp < a->L) return MMVAE_ERR_ARG;
     if (a->d_table && (!a->site || a->S <= 0)) return MMVAE_ERR_ARG;
-    const int rows_per_block = 128;          // as mmvae_fuse_reparam_bwd
-    const int grid = (a->B + rows_per_block - 1) / rows_per_block;
-    const size_t lds = a->d_table ? (size_t)a->S * a->L * sizeof(float) : 0;
-    const int use_lds = lds > 0 && lds <= 48 * 1024;
-    hipLaunchKernelGGL(fuse_mean_bwd_kernel, dim3(grid), dim3(256), use_lds ? lds : 0, (hipStream_t)stream, *a, rows_per_block, use_lds);
-    MM_CHECK_LAUNCH();
-    return 0;
+    const FuseBwd k{a->B, a->L, a->n_mod, a->d_head, a->ld_head, a->d_table, a->site, a->S, (bf16*)a->d_head_lp, a->ld_head_lp, a->table_copies};
+    return launch_fuse_bwd(k, FuseMeanBwd{a->dz, a->lddz, a->g_latent}, stream);
 }
 
 template <typename GT, typename TA, typename TB>

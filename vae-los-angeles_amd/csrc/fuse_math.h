@@ -1,5 +1,6 @@
-// Mean fusion + reparameterisation of ONE latent element (reference src/models/vae.py:65-73, 11-15), shared by
-// fuse_fwd_kernel (elementwise.hip) and the fused latent launch (latent.hip) so that both round alike.
+// The fusion of ONE latent element in its two forms, shared by the stand-alone kernels (elementwise.hip: fuse_fwd_kernel,
+// fuse_mean_fwd_kernel, the plain-mean policy of fuse_bwd_kernel) and the fused latent launch (latent.hip) so that all round alike.
+// Mean fusion + reparameterisation (reference src/models/vae.py:65-73, 11-15):
 #pragma once
 #include "common.h"
 

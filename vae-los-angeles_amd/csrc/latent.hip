@@ -256,51 +256,48 @@ static int lat_enc(const mmvae_latent_enc& e, int B, LatEnc& o) {
     return 0;
 }
 
+// What mmvae_latent_fwd (DET = false) and mmvae_ae_latent_fwd (DET = true) refuse alike, the LatArgs fields both fill alike, and the launch.
+// own_ok: the entry point's own requirements (its output pointers, the limits that depend on its head count), tested here behind the
+// precision so that a wrong precision is MMVAE_ERR_DTYPE whatever else is wrong; k arrives with the entry point's own fields set.
+// enc_b: nullptr where the entry point has one encoder.
+template <bool DET, typename A>
+static int latent_check_launch(const A& a, bool own_ok, const mmvae_latent_enc& enc_a, const mmvae_latent_enc* enc_b, LatArgs& k, void* stream) {
+    if (a.prec != MMVAE_PREC_BF16) return MMVAE_ERR_DTYPE;
+    if (a.B <= 0 || a.L <= 0 || (long)a.B * a.L >= (1L << 31) || !own_ok) return MMVAE_ERR_ARG;
+    if (!a.z || !a.w_stem || !a.h0) return MMVAE_ERR_ARG;
+    const int present = (enc_a.y != nullptr) + (enc_b && enc_b->y != nullptr) + (a.table != nullptr);
+    if (present == 0 || present != a.n_mod) return MMVAE_ERR_ARG;
+    if (a.table && (!a.site || a.S <= 0)) return MMVAE_ERR_ARG;
+    if (a.ldz % 8 || a.ldz < a.L || a.ldz > 32 || ((uintptr_t)a.z & 15)) return MMVAE_ERR_ARG;
+    if (a.N_stem < 64 || a.N_stem % 64 || a.N_stem > LAT_NS || a.ldw_stem % 64 || a.ldw_stem < 32 || ((uintptr_t)a.w_stem & 15)) return MMVAE_ERR_ARG;
+    if (a.ldh0 % 64 || a.ldh0 < a.N_stem || ((uintptr_t)a.h0 & 127) || (long)a.B * a.ldh0 * 2 >= (1L << 32)) return MMVAE_ERR_ARG;
+    { const int rc = lat_enc(enc_a, a.B, k.e[0]); if (rc) return rc; }
+    if (enc_b) { const int rc = lat_enc(*enc_b, a.B, k.e[1]); if (rc) return rc; }
+    k.B = a.B; k.L = a.L; k.n_mod = a.n_mod; k.S = a.S;
+    k.table = a.table; k.site = (const long long*)a.site;
+    k.z = (bf16*)a.z; k.ldz = a.ldz;
+    k.ws = (const bf16*)a.w_stem; k.ldws = a.ldw_stem; k.bs = a.bias_stem; k.ns = a.N_stem;
+    k.h0 = (bf16*)a.h0; k.ldh0 = a.ldh0;
+    k.nslabs = (a.B + 15) / 16;
+    return launch_lds<latent_fwd_kernel<DET>>(dim3(persistent_grid(k.nslabs, LAT_WAVES)), dim3(LAT_THREADS), LAT_LDS, (hipStream_t)stream, k);
+}
+
 }  // namespace mm
 
 extern "C" int mmvae_latent_fwd(const mmvae_latent_fwd_args* a, void* stream) {
     using namespace mm;
     if (!a || !g_tuning.latent_on) return MMVAE_ERR_ARG;
-    if (a->prec != MMVAE_PREC_BF16) return MMVAE_ERR_DTYPE;
-    if (a->B <= 0 || a->L <= 0 || 2 * a->L > LAT_HN || (long)a->B * a->L >= (1L << 31)) return MMVAE_ERR_ARG;
-    if (!a->eps || !a->mu || !a->logvar || !a->z || !a->w_stem || !a->h0) return MMVAE_ERR_ARG;
-    const int present = (a->enc_a.y != nullptr) + (a->enc_b.y != nullptr) + (a->table != nullptr);
-    if (present == 0 || present != a->n_mod) return MMVAE_ERR_ARG;
-    if (a->table && (!a->site || a->S <= 0 || (long)a->S * 2 * a->L > LAT_MAXTAB)) return MMVAE_ERR_ARG;
-    if (a->ldz % 8 || a->ldz < a->L || a->ldz > 32 || ((uintptr_t)a->z & 15)) return MMVAE_ERR_ARG;
-    if (a->N_stem < 64 || a->N_stem % 64 || a->N_stem > LAT_NS || a->ldw_stem % 64 || a->ldw_stem < 32 || ((uintptr_t)a->w_stem & 15)) return MMVAE_ERR_ARG;
-    if (a->ldh0 % 64 || a->ldh0 < a->N_stem || ((uintptr_t)a->h0 & 127) || (long)a->B * a->ldh0 * 2 >= (1L << 32)) return MMVAE_ERR_ARG;
+    const bool own_ok = 2 * a->L <= LAT_HN && a->eps && a->mu && a->logvar && (!a->table || (long)a->S * 2 * a->L <= LAT_MAXTAB);
     LatArgs k{};
-    { const int rc = lat_enc(a->enc_a, a->B, k.e[0]); if (rc) return rc; }
-    { const int rc = lat_enc(a->enc_b, a->B, k.e[1]); if (rc) return rc; }
-    k.B = a->B; k.L = a->L; k.n_mod = a->n_mod; k.S = a->S;
-    k.table = a->table; k.site = (const long long*)a->site; k.eps = a->eps; k.mu = a->mu; k.logvar = a->logvar;
-    k.z = (bf16*)a->z; k.ldz = a->ldz;
-    k.ws = (const bf16*)a->w_stem; k.ldws = a->ldw_stem; k.bs = a->bias_stem; k.ns = a->N_stem;
-    k.h0 = (bf16*)a->h0; k.ldh0 = a->ldh0;
-    k.nslabs = (a->B + 15) / 16;
-    return launch_lds<latent_fwd_kernel<false>>(dim3(persistent_grid(k.nslabs, LAT_WAVES)), dim3(LAT_THREADS), LAT_LDS, (hipStream_t)stream, k);
+    k.eps = a->eps; k.mu = a->mu; k.logvar = a->logvar;
+    return latent_check_launch<false>(*a, own_ok, a->enc_a, &a->enc_b, k, stream);
 }
 
 extern "C" int mmvae_ae_latent_fwd(const mmvae_ae_latent_fwd_args* a, void* stream) {
     using namespace mm;
     if (!a || !g_tuning.ae_latent_on) return MMVAE_ERR_ARG;
-    if (a->prec != MMVAE_PREC_BF16) return MMVAE_ERR_DTYPE;
-    if (a->B <= 0 || a->L <= 0 || a->L > LAT_HN / 2 || (long)a->B * a->L >= (1L << 31)) return MMVAE_ERR_ARG;
-    if (!a->latent || !a->z || !a->w_stem || !a->h0) return MMVAE_ERR_ARG;
-    const int present = (a->enc.y != nullptr) + (a->table != nullptr);
-    if (present == 0 || present != a->n_mod) return MMVAE_ERR_ARG;
-    if (a->table && (!a->site || a->S <= 0 || (long)a->S * a->L > LAT_MAXTAB)) return MMVAE_ERR_ARG;
-    if (a->ldz % 8 || a->ldz < a->L || a->ldz > 32 || ((uintptr_t)a->z & 15)) return MMVAE_ERR_ARG;
-    if (a->N_stem < 64 || a->N_stem % 64 || a->N_stem > LAT_NS || a->ldw_stem % 64 || a->ldw_stem < 32 || ((uintptr_t)a->w_stem & 15)) return MMVAE_ERR_ARG;
-    if (a->ldh0 % 64 || a->ldh0 < a->N_stem || ((uintptr_t)a->h0 & 127) || (long)a->B * a->ldh0 * 2 >= (1L << 32)) return MMVAE_ERR_ARG;
+    const bool own_ok = a->L <= LAT_HN / 2 && a->latent && (!a->table || (long)a->S * a->L <= LAT_MAXTAB);
     LatArgs k{};
-    { const int rc = lat_enc(a->enc, a->B, k.e[0]); if (rc) return rc; }
-    k.B = a->B; k.L = a->L; k.n_mod = a->n_mod; k.S = a->S;
-    k.table = a->table; k.site = (const long long*)a->site; k.mu = a->latent;
-    k.z = (bf16*)a->z; k.ldz = a->ldz;
-    k.ws = (const bf16*)a->w_stem; k.ldws = a->ldw_stem; k.bs = a->bias_stem; k.ns = a->N_stem;
-    k.h0 = (bf16*)a->h0; k.ldh0 = a->ldh0;
-    k.nslabs = (a->B + 15) / 16;
-    return launch_lds<latent_fwd_kernel<true>>(dim3(persistent_grid(k.nslabs, LAT_WAVES)), dim3(LAT_THREADS), LAT_LDS, (hipStream_t)stream, k);
+    k.mu = a->latent;
+    return latent_check_launch<true>(*a, own_ok, a->enc, nullptr, k, stream);
 }

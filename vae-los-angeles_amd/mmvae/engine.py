@@ -254,7 +254,7 @@ class StepZeros:
     loss_ws: Optional[tuple]            # (sums float64[5], out5 float32[5]) as ops.loss_workspace; None once the loss took it
     arena: Optional[torch.Tensor]       # flat fp32 gradient arena (param_list() order)
     bwd_stats: list                     # per BN layer: float64 (2, width) sums of the BatchNorm backward
-    d_table: Optional[torch.Tensor]     # (copies, sites, 2 * latent): the EncoderC table gradient, summed over the copies in its backward; AEGraph: (copies, sites, latent)
+    d_table: Optional[torch.Tensor]     # (copies, sites, table_width * latent): the EmbedEncoder's table gradient, summed over the copies in its backward
     unfilled: Optional[torch.Tensor] = None     # zero_pack(fill=False): the whole allocation, still to be zeroed by the caller
 
 
@@ -443,78 +443,45 @@ def _span(t, n):
 
 
 class EmbedEncoder:
-    """EncoderC (encoders.py:49-61): Embedding(S,E) + two heads == a [S][2L] table + gather."""
+    """EncoderC (encoders.py:49-61): Embedding(S,E) + two heads == a [S][2L] table + gather.
+    fc_logvar=None: the autoencoders' site path (directional_ae.py:29-30, 52-56) -- Embedding(S,E) -> ONE Linear(E, latent) (`fc_mu`
+    here) == a [S][L] table + gather, through the one-head launches ops.embed_proj_fwd / embed_proj_bwd."""
 
-    def __init__(self, embedding, fc_mu, fc_logvar):
+    def __init__(self, embedding, fc_mu, fc_logvar=None):
         self.embedding, self.fc_mu, self.fc_logvar = embedding, fc_mu, fc_logvar
         self.latent = fc_mu.out_features
+        self.table_width = 1 if fc_logvar is None else 2       # table columns per latent dimension
+        # the two-head table has a role in the step's shared launches: ops.step_head may make it, and its backward may run as rider
+        # workgroups of the grouped dW launch (ops.tn_riders).  The one-head table and its backward are always launches of their own.
+        self.rides = fc_logvar is not None
+        self._heads = [fc_mu] if fc_logvar is None else [fc_mu, fc_logvar]
 
     def prepare(self, prec, device):
         return []
 
     def params(self):
-        return [self.embedding.weight, self.fc_mu.weight, self.fc_mu.bias, self.fc_logvar.weight, self.fc_logvar.bias]
+        """Order of the gradient arena: the embedding, then weight and bias head by head."""
+        return [self.embedding.weight] + [p for h in self._heads for p in (h.weight, h.bias)]
 
     def table_args(self):
-        """ops.embed_table_fwd's arguments, the table (the last of them) freshly allocated."""
+        """ops.embed_table_fwd's arguments (ops.embed_proj_fwd's in the one-head form), the table (the last of them) freshly allocated."""
         emb = self.embedding.weight
-        t = torch.empty(emb.shape[0], 2 * self.latent, dtype=torch.float32, device=emb.device)
-        return (emb, self.fc_mu.weight, self.fc_mu.bias, self.fc_logvar.weight, self.fc_logvar.bias, t)
+        t = torch.empty(emb.shape[0], self.table_width * self.latent, dtype=torch.float32, device=emb.device)
+        return (emb, *(p for h in self._heads for p in (h.weight, h.bias)), t)
 
-    def table(self):
-        args = self.table_args()
-        ops.embed_table_fwd(*args)
+    def table(self, args=None):
+        """The table by a launch of its own (args: table_args() made earlier)."""
+        args = self.table_args() if args is None else args
+        (ops.embed_table_fwd if self.rides else ops.embed_proj_fwd)(*args)
         return args[-1]
 
     def backward_args(self, d_table, grads):
-        """ops.embed_table_bwd's arguments."""
-        return (self.embedding.weight, self.fc_mu.weight, self.fc_logvar.weight, d_table,
-                grads[self.embedding.weight], grads[self.fc_mu.weight], grads[self.fc_mu.bias],
-                grads[self.fc_logvar.weight], grads[self.fc_logvar.bias])
-
-    rides = True                       # its backward may run as rider workgroups of the grouped dW launch (ops.tn_riders)
-    table_width = 2                    # table columns per latent dimension
+        """ops.embed_table_bwd's arguments (ops.embed_proj_bwd's in the one-head form)."""
+        return (self.embedding.weight, *(h.weight for h in self._heads), d_table, grads[self.embedding.weight],
+                *(grads[p] for h in self._heads for p in (h.weight, h.bias)))
 
     def launch_backward(self, *args):
-        ops.embed_table_bwd(*args)
-
-    def backward(self, d_table, grads):
-        self.launch_backward(*self.backward_args(d_table, grads))
-
-
-class ProjectedEmbedding:
-    """The autoencoders' site path (directional_ae.py:29-30, 52-56): Embedding(S,E) -> Linear(E, latent) == a [S][L] table + gather.
-    The one-head EmbedEncoder: the table is a launch of its own (ops.embed_proj_fwd), and so is its backward."""
-    rides = False
-    table_width = 1
-
-    def __init__(self, embedding, projection):
-        self.embedding, self.projection = embedding, projection
-        self.latent = projection.out_features
-
-    def prepare(self, prec, device):
-        return []
-
-    def params(self):
-        return [self.embedding.weight, self.projection.weight, self.projection.bias]
-
-    def table_args(self):
-        """ops.embed_proj_fwd's arguments, the table (the last of them) freshly allocated."""
-        emb = self.embedding.weight
-        return (emb, self.projection.weight, self.projection.bias, torch.empty(emb.shape[0], self.latent, dtype=torch.float32, device=emb.device))
-
-    def table(self):
-        args = self.table_args()
-        ops.embed_proj_fwd(*args)
-        return args[-1]
-
-    def backward_args(self, d_table, grads):
-        """ops.embed_proj_bwd's arguments."""
-        return (self.embedding.weight, self.projection.weight, d_table,
-                grads[self.embedding.weight], grads[self.projection.weight], grads[self.projection.bias])
-
-    def launch_backward(self, *args):
-        ops.embed_proj_bwd(*args)
+        (ops.embed_table_bwd if self.rides else ops.embed_proj_bwd)(*args)
 
     def backward(self, d_table, grads):
         self.launch_backward(*self.backward_args(d_table, grads))
@@ -713,7 +680,7 @@ class VAEGraph:
                          unfilled=unfilled)
 
     def forward(self, prec, xa, xb, site, train, want_bwd=False):
-        """Returns (outs(list, fp32), mu, logvar, state).  want_bwd: a backward will follow (training only) -- decided by the caller
+        """Returns (outs(list, fp32), mu, logvar, state); an AEGraph (outs, latent, state).  want_bwd: a backward will follow (training only) -- decided by the caller
         (functional.run_graph) BEFORE it enters the autograd.Function, inside which grad mode is always off."""
         ref = xa if xa is not None else (xb if xb is not None else site)
         if not ref.is_cuda or any(p.device != ref.device for p in self.param_list()):
@@ -757,61 +724,80 @@ class VAEGraph:
             zeros.unfilled = None
         return masks, eps, zeros, len(widths_a), head
 
+    draws_eps = True                   # the head of the step draws eps of the latent width (an AEGraph: dropout masks only)
+    flatten_a = False                  # input a is taken as given; b is always flattened (encoders.py:44 view)
+
     def _forward(self, prec, xa, xb, site, train, want_bwd):
+        """The step up to the latent stage, that stage (_latent_forward, the one part a subclass replaces), the decoders.
+        Returns (outs, *latent tensors, state)."""
+        for x, enc in ((xa, self.enc_a), (xb, self.enc_b)):
+            if x is not None and enc is None:
+                raise RuntimeError(f"{type(self).__name__}: this graph has no encoder for that input")
         ref = xa if xa is not None else (xb if xb is not None else site)
         dev, B = ref.device, ref.shape[0]
         state = StepState(prec, B, train, tail_riders=self.tail_riders and want_bwd)
-        heads_a = heads_b = table = None
-        Ld = self.latent
-        table_args = self.enc_c.table_args() if site is not None else None
+        enc_out = [None, None]                         # per MLP encoder: its heads, or the ops.LatentEncoder it stopped at
+        table = None
+        # a two-head table is handed to the head launch; a one-head table is a launch of its own behind the encoders
+        table_args = self.enc_c.table_args() if (site is not None and self.enc_c.rides) else None
         masks, eps, zeros, n_a, head = self._head_of_step(prec, dev, B, xa is not None, xb is not None, site is not None, train, want_bwd,
-                                                          Ld, table_args)
+                                                          self.latent if self.draws_eps else None, table_args)
         if head and table_args is not None:
             table = table_args[-1]
         if want_bwd:
             state.zeros = zeros
-        # With merged decoder first layers in bf16 mode the encoders stop before their heads: heads, fusion, reparameterisation and the
-        # stems are ONE launch (mmvae_latent_fwd); where the library does not take it, the launches it replaces run below.  The refusal
-        # is only known once both encoders have run, so that fallback issues [A layers, B layers, A heads, B heads, fusion, stems]
-        # where graphs without a stem (and every graph before the fused launch) issue [A layers, A heads, B layers, B heads, ...]: the
-        # same launches on the same operands with the same results, EncoderA's last pre-BatchNorm output is simply read later.
-        stem = self.dec_stem
-        fuse_latent = stem is not None and prec == PREC_BF16
+        # Where the latent stage is ONE launch the encoders stop before their heads; where the library does not take it, the launches it
+        # replaces run inside the stage.  The refusal is only known once both encoders have run, so that fallback issues
+        # [A layers, B layers, A heads, B heads, fusion, stems] where graphs without a fused stage issue [A layers, A heads, B layers,
+        # B heads, ...]: the same launches on the same operands with the same results, EncoderA's last pre-BatchNorm output is simply read later.
+        fuse_latent = self._fuses_latent(prec)
         if xa is not None:
-            xa = _check_input(xa, "a", self.enc_a.in_dim, prec)
-            heads_a, state.enc_a = self.enc_a.forward(prec, xa, train, masks[:n_a] if train else None,
-                                                      zeros.fwd_stats[:n_a] if train else None, want_bwd=want_bwd, heads=not fuse_latent)
+            xa = _check_input(xa.reshape(xa.shape[0], -1) if self.flatten_a else xa, "a", self.enc_a.in_dim, prec)
+            enc_out[0], state.enc_a = self.enc_a.forward(prec, xa, train, masks[:n_a] if train else None,
+                                                         zeros.fwd_stats[:n_a] if train else None, want_bwd=want_bwd, heads=not fuse_latent)
         if xb is not None:
             xb = _check_input(xb.reshape(xb.shape[0], -1), "b", self.enc_b.in_dim, prec)     # encoders.py:44 view
-            heads_b, state.enc_b = self.enc_b.forward(prec, xb, train, masks[n_a:] if train else None,
-                                                      zeros.fwd_stats[n_a:] if train else None, want_bwd=want_bwd, heads=not fuse_latent)
+            enc_out[1], state.enc_b = self.enc_b.forward(prec, xb, train, masks[n_a:] if train else None,
+                                                         zeros.fwd_stats[n_a:] if train else None, want_bwd=want_bwd, heads=not fuse_latent)
         if site is not None:
             if site.dtype != torch.int64:
                 site = site.long()
-            site = site.contiguous()
+            site = state.site = site.contiguous()
             if table is None:                          # not made by the head launch
-                ops.embed_table_fwd(*table_args)
-                table = table_args[-1]
-            state.site = site
+                table = self.enc_c.table(table_args)
+        state.eps = eps
+        state.n_mod = (xa is not None) + (xb is not None) + (table is not None)
+        latents, z, H0, stem_done, first0 = self._latent_forward(prec, B, dev, enc_out, table, site, eps, fuse_latent, state)
+        return (self._decode(prec, B, dev, z, H0, stem_done, state, zeros, want_bwd, site, first0=first0), *latents, state)
+
+    def _fuses_latent(self, prec):
+        """Whether the latent stage is tried as one launch (the encoders then stop before their heads)."""
+        return self.dec_stem is not None and prec == PREC_BF16
+
+    def _latent_forward(self, prec, B, dev, enc_out, table, site, eps, fused, state):
+        """Heads, mean fusion, reparameterisation and the decoders' stems -> ((mu, logvar), z, and _decode's H0, stem_done, first0).
+        enc_out: per MLP encoder its heads, or (fused) the LatentEncoder it stopped at: ONE launch (mmvae_latent_fwd) with merged decoder
+        first layers in bf16 mode."""
+        Ld, stem = self.latent, self.dec_stem
+        heads_a, heads_b = enc_out
         mu = torch.empty(B, Ld, dtype=torch.float32, device=dev)
         logvar = torch.empty(B, Ld, dtype=torch.float32, device=dev)
         z = torch.empty(B, ceil_to(Ld, 8), dtype=act_dtype(prec), device=dev)
         H0 = torch.empty(B, stem.N, dtype=act_dtype(prec), device=dev) if stem is not None else None
-        if fuse_latent:
+        if fused:
             try:
                 ops.latent_fwd(prec, B, Ld, heads_a, heads_b, table, site, eps, mu, logvar, z, stem, H0)
             except L_.MMVAEArgError:                   # refused before anything was enqueued
-                fuse_latent = False
+                fused = False
                 heads_a = self.enc_a.run_heads(prec, heads_a) if heads_a is not None else None
                 heads_b = self.enc_b.run_heads(prec, heads_b) if heads_b is not None else None
-        if not fuse_latent:
+        if not fused:
             ops.fuse_reparam_fwd(B, Ld, heads_a, heads_b, table, site, eps, mu, logvar, z)
-        # .detach(): aliases of the RETURNED tensors, so the saved state holds no reference to objects that own the
+        # .detach(): an alias of the RETURNED tensor, so the saved state holds no reference to objects that own the
         # autograd node (tensor -> grad_fn -> ctx -> state -> tensor would be a cycle only the cyclic GC frees,
         # i.e. every step's activations would pile up in HBM until it runs)
-        state.eps, state.logvar = eps, logvar.detach()
-        state.n_mod = (heads_a is not None) + (heads_b is not None) + (table is not None)
-        return self._decode(prec, B, dev, z, H0, fuse_latent, state, zeros, want_bwd, site), mu, logvar, state
+        state.logvar = logvar.detach()
+        return (mu, logvar), z, H0, fused, None
 
     def _decode(self, prec, B, dev, z, H0, stem_done, state, zeros, want_bwd, site, first0=None):
         """The decoders on z -> their outputs; fills state.dec / fused / class_tail.  H0: the merged first layers' output buffer (None
@@ -948,7 +934,7 @@ class VAEGraph:
         # the loss finalisation the loss left behind have nothing to do with the grouped dW launch that ends the backward: with
         # tail_riders they run as extra workgroups of it.  Without, where there is no such launch, or where the library refuses
         # (nothing enqueued), they are the launches of their own they were.
-        # (A ProjectedEmbedding's backward does not ride: the rider role is EncoderC's two-head table; it is always its own launch.)
+        # (A one-head EmbedEncoder's backward does not ride: the rider role is EncoderC's two-head table; it is always its own launch.)
         embed_bwd = self.enc_c.backward_args(zeros.d_table, grads) if site is not None else None
         ride_embed = embed_bwd if (embed_bwd is not None and self.enc_c.rides) else None
         loss_tail, state.loss_tail = state.loss_tail, None
@@ -982,63 +968,45 @@ class VAEGraph:
 # --------------------------------------------------------------------------------------------
 class AEGraph(VAEGraph):
     """Compute graph of RNA2DNAAE / DNA2RNAAE (reference src/models/directional_ae.py:10-134): a single-head MLP encoder (in slot a for
-    RNA, slot b for DNA), the site through a ProjectedEmbedding, the plain mean of the latents present, one decoder.  No eps is drawn,
+    RNA, slot b for DNA), the site through a one-head EmbedEncoder, the plain mean of the latents present, one decoder.  No eps is drawn,
     no logvar exists, nothing of a KL term: forward returns (outs, latent, state).  Everything else -- the head of the step, the one
     memset, the decoders, fused_recon, tail_riders, the gradient arena, grad_sync -- is VAEGraph's."""
 
     def __init__(self, enc_a=None, enc_b=None, site=None, decoder=None):
         if (enc_a is None) == (enc_b is None) or site is None or decoder is None:
             raise ValueError("AEGraph: exactly one MLP encoder, the projected site embedding and one decoder")
-        if (enc_a or enc_b).fc_logvar is not None or not isinstance(site, ProjectedEmbedding):
-            raise ValueError("AEGraph: the encoder must be in its single-head form and the site a ProjectedEmbedding")
+        if (enc_a or enc_b).fc_logvar is not None or site.fc_logvar is not None:
+            raise ValueError("AEGraph: the encoder and the site embedding must be in their single-head form")
         super().__init__(enc_a=enc_a, enc_b=enc_b, enc_c=site, decoders=[decoder])
 
-    def _forward(self, prec, xa, xb, site, train, want_bwd):
-        x = xa if xa is not None else xb
-        enc = self.enc_a if xa is not None else self.enc_b
-        if x is not None and enc is None:
-            raise RuntimeError("AEGraph: this graph has no encoder for that input")
-        ref = x if x is not None else site
-        dev, B, Ld = ref.device, ref.shape[0], self.latent
-        state = StepState(prec, B, train, tail_riders=self.tail_riders and want_bwd)
-        # masks only: the Philox offset advances by exactly the mask draw, and not at all in eval mode.  The table is a launch of its
-        # own (the head launch's table role is EncoderC's two-head table).
-        masks, _, zeros, _, _ = self._head_of_step(prec, dev, B, xa is not None, xb is not None, site is not None, train, want_bwd, None, None)
-        if want_bwd:
-            state.zeros = zeros
-        head = table = None
+    # masks only: the Philox offset advances by exactly the mask draw, and not at all in eval mode
+    draws_eps = False
+    flatten_a = True                   # directional_ae.py flattens whichever input it encodes
+
+    def _fuses_latent(self, prec):
         dec = self.decoders[0]
-        fuse = prec == PREC_BF16 and isinstance(dec, DecoderMLP) and len(dec.linears) >= 2
-        if x is not None:
-            x = _check_input(x.reshape(x.shape[0], -1), "a" if xa is not None else "b", enc.in_dim, prec)
-            # in bf16 mode the encoder stops before its head: head, mean and the decoder's first layer are ONE launch
-            # (mmvae_ae_latent_fwd); where the library does not take it, the three launches it replaces run below
-            head, layers = enc.forward(prec, x, train, masks if train else None, zeros.fwd_stats if train else None, want_bwd=want_bwd,
-                                       heads=not fuse)
-            if xa is not None:
-                state.enc_a = layers
-            else:
-                state.enc_b = layers
-        if site is not None:
-            if site.dtype != torch.int64:
-                site = site.long()
-            site = state.site = site.contiguous()
-            table = self.enc_c.table()
+        return prec == PREC_BF16 and isinstance(dec, DecoderMLP) and len(dec.linears) >= 2
+
+    def _latent_forward(self, prec, B, dev, enc_out, table, site, eps, fused, state):
+        """Head, plain mean with the site's table row and the decoder's first layer -> ((latent,), z, and _decode's H0, stem_done,
+        first0).  In bf16 mode ONE launch (mmvae_ae_latent_fwd) on the LatentEncoder the encoder stopped at; where the library does not
+        take it, the three launches it replaces."""
+        Ld, dec = self.latent, self.decoders[0]
+        enc, head = (self.enc_a, enc_out[0]) if enc_out[0] is not None else (self.enc_b, enc_out[1])
         latent = torch.empty(B, Ld, dtype=torch.float32, device=dev)
         z = torch.empty(B, ceil_to(Ld, 8), dtype=act_dtype(prec), device=dev)
         first = None
-        if fuse:
+        if fused:
             pl0 = dec.pl[0]
             first = torch.empty(B, ceil_to(pl0.N, 8), dtype=act_dtype(prec), device=dev)
             try:
                 ops.ae_latent_fwd(prec, B, Ld, head, table, site, latent, z, pl0, first)
             except L_.MMVAEArgError:                   # refused before anything was enqueued
-                fuse, first = False, None
+                fused, first = False, None
                 head = enc.run_heads(prec, head) if head is not None else None
-        if not fuse:
+        if not fused:
             ops.fuse_mean_fwd(B, Ld, head, table, site, latent, z)
-        state.n_mod = (head is not None) + (table is not None)
-        return self._decode(prec, B, dev, z, None, False, state, zeros, want_bwd, site, first0=first), latent, state
+        return (latent,), z, None, False, first
 
     def _backward(self, state, g_outs, g_logit_flags, g_latent, g_lv=None):
         return super()._backward(state, g_outs, g_logit_flags, g_latent, None)

@@ -24,13 +24,16 @@ from .ops import ceil_to, act_dtype
 
 
 class VAEGraphFn(torch.autograd.Function):
+    """One forward of an engine.VAEGraph or AEGraph.  Whatever graph.forward returns between the decoders' outputs and the state are
+    the latent outputs -- (mu, logvar), or an AEGraph's (latent,) -- and as many gradients go to the graph's backward."""
+
     @staticmethod
     def forward(ctx, graph, prec, train, want_bwd, xa, xb, site, *params):
         ctx.set_materialize_grads(False)
-        outs, mu, logvar, state = graph.forward(prec, xa, xb, site, train, want_bwd)
+        outs, *latents, state = graph.forward(prec, xa, xb, site, train, want_bwd)
         ctx.graph, ctx.saved, ctx.n_out = graph, state, len(outs)
         graph._last_saved = state
-        return (*outs, mu, logvar)
+        return (*outs, *latents)
 
     @staticmethod
     @once_differentiable
@@ -39,9 +42,8 @@ class VAEGraphFn(torch.autograd.Function):
         if state.consumed:
             raise RuntimeError("backward through this forward was already run (buffers are not retained)")
         g_outs = [None if g is None else _as_rows(g) for g in gs[:n_out]]
-        g_mu = None if gs[n_out] is None else gs[n_out].contiguous().float()
-        g_lv = None if gs[n_out + 1] is None else gs[n_out + 1].contiguous().float()
-        return (None, None, None, None, None, None, None, *_graph_backward(graph, state, g_outs, g_mu, g_lv))
+        g_lat = [None if g is None else g.contiguous().float() for g in gs[n_out:]] + [None]      # g_lv: None behind an AEGraph's one latent
+        return (None, None, None, None, None, None, None, *_graph_backward(graph, state, g_outs, g_lat[0], g_lat[1]))
 
 
 def _graph_backward(graph, state, g_outs, g_mu, g_lv):
@@ -69,26 +71,6 @@ def _graph_backward(graph, state, g_outs, g_mu, g_lv):
     out = [grads[p] if id(p) in used else None for p in graph.param_list()]
     del grads                                     # keep the views unique so autograd can adopt them
     return out
-
-
-class AEGraphFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, graph, prec, train, want_bwd, x_a, x_b, site, *params):
-        ctx.set_materialize_grads(False)
-        outs, latent, state = graph.forward(prec, x_a, x_b, site, train, want_bwd)
-        ctx.graph, ctx.saved, ctx.n_out = graph, state, len(outs)
-        graph._last_saved = state
-        return (*outs, latent)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, *gs):
-        graph, state, n_out = ctx.graph, ctx.saved, ctx.n_out
-        if state.consumed:
-            raise RuntimeError("backward through this forward was already run (buffers are not retained)")
-        g_outs = [None if g is None else _as_rows(g) for g in gs[:n_out]]
-        g_latent = None if gs[n_out] is None else gs[n_out].contiguous().float()
-        return (None, None, None, None, None, None, None, *_graph_backward(graph, state, g_outs, g_latent, None))
 
 
 def _as_rows(g):
@@ -119,40 +101,34 @@ class OutTag(NamedTuple):
     index: int                      # the decoder, for "out"
 
 
-def run_graph(graph, prec, train, xa, xb, site):
-    """Forward of a VAEGraph with autograd wiring.  Returns (outs, mu, logvar)."""
+def _run(graph, prec, train, xa, xb, site, kinds):
+    """Forward of a graph with autograd wiring -> (outs, *latent outputs); kinds: the OutTag kind of each latent output."""
     params = graph.param_list()
     # a backward will follow: the forward's ONE memset then also zeroes the gradient arena, the backward's BatchNorm sums, the table
     # gradient and the loss accumulators (3 fill launches per step -> 1)
     want_bwd = train and torch.is_grad_enabled() and any(p.requires_grad for p in params)
     res = VAEGraphFn.apply(graph, prec, train, want_bwd, xa, xb, site, *params)
     n = len(graph.decoders)
-    outs, mu, logvar = list(res[:n]), res[n], res[n + 1]
+    outs, latents = list(res[:n]), res[n:]
     state = graph._last_saved
     graph._last_saved = None
     if torch.is_grad_enabled() and any(p.requires_grad for p in params):
         for i, o in enumerate(outs):
             o._mmvae = OutTag(state, "out", i)
-        mu._mmvae = OutTag(state, "mu", 0)
-        logvar._mmvae = OutTag(state, "logvar", 0)
-    return outs, mu, logvar
+        for t, kind in zip(latents, kinds):
+            t._mmvae = OutTag(state, kind, 0)
+    return (outs, *latents)
+
+
+def run_graph(graph, prec, train, xa, xb, site):
+    """Forward of a VAEGraph with autograd wiring.  Returns (outs, mu, logvar)."""
+    return _run(graph, prec, train, xa, xb, site, ("mu", "logvar"))
 
 
 def run_ae_graph(graph, prec, train, x_a, x_b, site):
     """Forward of an engine.AEGraph with autograd wiring (x_a: RNA for a graph with an RNA encoder, x_b: DNA for one with a DNA
     encoder; either and the site may be None).  Returns (outs, latent)."""
-    params = graph.param_list()
-    want_bwd = train and torch.is_grad_enabled() and any(p.requires_grad for p in params)
-    res = AEGraphFn.apply(graph, prec, train, want_bwd, x_a, x_b, site, *params)
-    n = len(graph.decoders)
-    outs, latent = list(res[:n]), res[n]
-    state = graph._last_saved
-    graph._last_saved = None
-    if torch.is_grad_enabled() and any(p.requires_grad for p in params):
-        for i, o in enumerate(outs):
-            o._mmvae = OutTag(state, "out", i)
-        latent._mmvae = OutTag(state, "latent", 0)
-    return outs, latent
+    return _run(graph, prec, train, x_a, x_b, site, ("latent",))
 
 
 # --------------------------------------------------------------------------------------------

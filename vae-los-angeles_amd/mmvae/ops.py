@@ -531,23 +531,28 @@ def _latent_enc(e, enc):
     e.w, e.ldw, e.bias = enc.heads.w.data_ptr(), enc.heads.w.stride(0), _p(enc.heads.bias)
 
 
+def _latent_common(a, table, site, z, stem, h0):
+    """The fields LatentFwdArgs and AELatentFwdArgs share -- site table, z, first decoder layer(s), h0 -- -> their HBM bytes per row."""
+    if table is not None:
+        a.table, a.site, a.S = table.data_ptr(), _p(site), table.shape[0]
+    a.z, a.ldz = z.data_ptr(), _ld(z)
+    a.w_stem, a.ldw_stem, a.bias_stem, a.N_stem = stem.w.data_ptr(), stem.w.stride(0), _p(stem.bias), stem.N
+    a.h0, a.ldh0 = h0.data_ptr(), _ld(h0)
+    return z.element_size() * _ld(z) + h0.element_size() * stem.N + 8 * (table is not None)
+
+
 def latent_fwd_args(prec, B, Ld, enc_a, enc_b, table, site, eps, mu, logvar, z, stem, h0):
     """-> (LatentFwdArgs of mmvae_latent_fwd, its algorithmic HBM bytes).  The struct holds addresses only: the tensors and the
     encoders' BnFinalizeArgs must outlive the call."""
     a = L.LatentFwdArgs()
     a.prec, a.B, a.L = prec, B, Ld
     a.n_mod = (enc_a is not None) + (enc_b is not None) + (table is not None)
-    nbytes = 12 * Ld + z.element_size() * _ld(z) + h0.element_size() * stem.N + 8 * (table is not None)
+    nbytes = 12 * Ld + _latent_common(a, table, site, z, stem, h0)
     for e, enc in ((a.enc_a, enc_a), (a.enc_b, enc_b)):
         if enc is not None:
             _latent_enc(e, enc)
             nbytes += enc.heads.K * (enc.y.element_size() + (enc.prologue[2] is not None))
-    if table is not None:
-        a.table, a.site, a.S = table.data_ptr(), _p(site), table.shape[0]
     a.eps, a.mu, a.logvar = eps.data_ptr(), mu.data_ptr(), logvar.data_ptr()
-    a.z, a.ldz = z.data_ptr(), _ld(z)
-    a.w_stem, a.ldw_stem, a.bias_stem, a.N_stem = stem.w.data_ptr(), stem.w.stride(0), _p(stem.bias), stem.N
-    a.h0, a.ldh0 = h0.data_ptr(), _ld(h0)
     return a, B * nbytes
 
 
@@ -623,15 +628,11 @@ def ae_latent_fwd_args(prec, B, Ld, enc, table, site, latent, z, first, h0):
     a = L.AELatentFwdArgs()
     a.prec, a.B, a.L = prec, B, Ld
     a.n_mod = (enc is not None) + (table is not None)
-    nbytes = 4 * Ld + z.element_size() * _ld(z) + h0.element_size() * first.N + 8 * (table is not None)
+    nbytes = 4 * Ld + _latent_common(a, table, site, z, first, h0)
     if enc is not None:
         _latent_enc(a.enc, enc)
         nbytes += enc.heads.K * (enc.y.element_size() + (enc.prologue[2] is not None))
-    if table is not None:
-        a.table, a.site, a.S = table.data_ptr(), _p(site), table.shape[0]
-    a.latent, a.z, a.ldz = latent.data_ptr(), z.data_ptr(), _ld(z)
-    a.w_stem, a.ldw_stem, a.bias_stem, a.N_stem = first.w.data_ptr(), first.w.stride(0), _p(first.bias), first.N
-    a.h0, a.ldh0 = h0.data_ptr(), _ld(h0)
+    a.latent = latent.data_ptr()
     return a, B * nbytes
 
 

@@ -31,7 +31,7 @@ class _DirectionalAE(HipModule):
         g = getattr(self, "_g", None)
         if g is None:
             enc, dec = self._parts()
-            g = engine.AEGraph(site=engine.ProjectedEmbedding(self.site_embedding, self.site_projection), decoder=dec._block(),
+            g = engine.AEGraph(site=engine.EmbedEncoder(self.site_embedding, self.site_projection), decoder=dec._block(),
                                **{"enc_" + self._SLOT: _encoder_block(enc, type(self).__name__ + ".encoder")})
             object.__setattr__(self, "_g", g)
         return g
