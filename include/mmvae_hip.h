@@ -178,7 +178,7 @@ int mmvae_gemm_tn_group(const mmvae_gemm_tn_args* args, int32_t n, void* stream)
  *   Loss finalisation (sums != NULL): mmvae_loss_finalize's arguments, one thread.
  * Returns MMVAE_ERR_ARG, with nothing enqueued, when riders is NULL or names no rider, a rider's arguments are incomplete, the
  * EncoderC rider's LDS need (S*2L + S*E + 2L*E floats) exceeds the dynamic LDS the group kernel is launched with (72 KiB) or
- * mmvae_embed_table_bwd's own capacity (64 KiB: 24 sites x latent 128 x embed 32 ride, 59 KiB), tuning key 14 is off, or
+ * 64 KiB (24 sites x latent 128 x embed 32 ride, 59 KiB; mmvae_embed_table_bwd alone takes up to 160 KiB), tuning key 14 is off, or
  * mmvae_gemm_tn_group would refuse the problems: the caller then issues the launches this one replaces. */
 typedef struct {
     int32_t S, E, L, table_copies;
@@ -233,7 +233,11 @@ int mmvae_bn_bwd_finalize_apply(int32_t dtype, int32_t M, int32_t N, void* d, in
  *   T[S][2L] = emb[S][E] x [Wmu;Wlv]^T + [bmu;blv]      (fp32), gathered per sample later.
  * Backward: from dT[S][2L]: dEmb, dWmu, dWlv, dbmu, dblv (all accumulated).
  *   Capacity: every workgroup of mmvae_embed_table_bwd keeps its three operands in LDS, so the call returns MMVAE_ERR_ARG (nothing
- *   enqueued) when (S*2L + S*E + 2L*E) * 4 bytes exceed 64 KiB: 24 sites x latent 128 x embed 32 fit (59 KiB), 32 sites do not.
+ *   enqueued) when (S*2L + S*E + 2L*E) * 4 bytes exceed 160 KiB, the CU's LDS: every (latent <= 100, embed <= 64) of the reference's
+ *   hyperparameter search fits up to 106 sites.  Up to 64 KiB the launch is the one it always was; beyond, the same kernel runs with
+ *   the dynamic-LDS attribute raised (same per-thread arithmetic and accumulation order).  The attribute is set once per process,
+ *   on the device that is current at the first call past 64 KiB, and the flag is not guarded against concurrent first calls: one
+ *   device per process and one calling thread, as for the other launches here that take more than 64 KiB (ranks are processes).
  * ------------------------------------------------------------------------------------------- */
 int mmvae_embed_table_fwd(int32_t S, int32_t E, int32_t L, const float* emb, const float* w_mu, const float* b_mu,
                           const float* w_lv, const float* b_lv, float* table, void* stream);
@@ -283,7 +287,7 @@ int mmvae_fuse_reparam_bwd(const mmvae_fuse_bwd_args* args, void* stream);
  * mmvae_embed_proj_fwd / _bwd: the one-head case of mmvae_embed_table_fwd / _bwd (the same kernels' bodies with one head):
  *   table[S][L] = emb[S][E] x w[L][E]^T + b   (fp32; every element accumulates from the bias over e ascending)
  *   backward, from d_table[table_copies][S][L] (the copies are summed in fixed order): d_emb, d_w, d_b are accumulated into.
- *   Capacity as mmvae_embed_table_bwd, for one head: MMVAE_ERR_ARG (nothing enqueued) when (S*L + S*E + L*E) * 4 bytes exceed 64 KiB.
+ *   Capacity as mmvae_embed_table_bwd, for one head: MMVAE_ERR_ARG (nothing enqueued) when (S*L + S*E + L*E) * 4 bytes exceed 160 KiB.
  *
  * mmvae_fuse_mean_fwd:  latent = (head + table[site]) * (1 / n_mod), the sum formed in the order head, table row, multiplied only
  *   when n_mod > 1 (one or two terms: exact after the one addition).  head: fp32 [B][ld_head] or NULL; table / site / S: the

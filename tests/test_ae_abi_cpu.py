@@ -39,9 +39,10 @@ def test_embed_proj_refusals_need_no_device():
     assert lib.mmvae_embed_proj_fwd(24, 32, 20, p, p, None, p, None) == -1
     assert lib.mmvae_embed_proj_bwd(24, 32, 20, p, p, None, 8, p, p, p, None) == -1
     assert lib.mmvae_embed_proj_bwd(24, 32, 20, p, p, p, 8, p, None, p, None) == -1
-    # the LDS capacity, for one head: (S L + S E + L E) * 4 bytes beyond 64 KiB (64 sites x latent 160 x embed 32 = 68 KiB)
-    S, E, L = 64, 32, 160
-    assert (S * L + S * E + L * E) * 4 > 64 * 1024
+    # the LDS capacity, for one head: (S L + S E + L E) * 4 bytes beyond 160 KiB (77 sites x latent 256 x embed 64 = 160.25 KiB; one site
+    # fewer is a launch, which this file must not make: the buffer is four host floats)
+    S, E, L = 77, 64, 256
+    assert (S * L + S * E + L * E) * 4 > 160 * 1024 >= ((S - 1) * L + (S - 1) * E + L * E) * 4
     assert lib.mmvae_embed_proj_bwd(S, E, L, p, p, p, 8, p, p, p, None) == -1
 
 

@@ -55,16 +55,21 @@ def load_ae(model, P, Bf):
     return model
 
 
-def case(kind, B):
-    key = (kind, B)
+def case(kind, B, dims=(A, D, S, L, E), settle=False):
+    """settle: no kept ReLU gate of the encoder within fp32 rounding of zero (width_cases.settle_gates)."""
+    key = (kind, B, tuple(dims), settle)
     if key not in _cases:
         seed = 700 + B
-        P, Bf = AO.make_params(seed, kind, A, D, S, L, E)
-        a, b, site = O.make_batch(seed + 1, B, A, D, S)
+        A_, D_, S_, L_, E_ = dims
+        P, Bf = AO.make_params(seed, kind, A_, D_, S_, L_, E_)
+        a, b, site = O.make_batch(seed + 1, B, A_, D_, S_)
         rng = np.random.default_rng(seed + 2)
         masks = {n: (rng.random((B, w)) >= O.DROP_P).astype(np.uint8) for n, w in zip(AO.mask_names(kind), AO.HIDDEN[kind])}
         x, tgt = (a, b) if kind == "rna2dna" else (b, a)
-        _cases[key] = dict(kind=kind, B=B, P=P, Bf=Bf, x=x, tgt=tgt, site=site, masks=masks, ref={})
+        if settle:
+            import width_cases as W
+            masks, _ = W.settle_gates(masks, W.ae_gates(kind, P, Bf, x.astype(np.float64), site))
+        _cases[key] = dict(kind=kind, B=B, dims=tuple(dims), P=P, Bf=Bf, x=x, tgt=tgt, site=site, masks=masks, ref={})
     return _cases[key]
 
 
@@ -82,7 +87,8 @@ def oracle(c, q):
 
 
 def build(c, prec):
-    model = load_ae(MODELS[c["kind"]](A, D, S, L, embed_dim=E), c["P"], c["Bf"]).to(DEV).set_precision(prec).train()
+    A_, D_, S_, L_, E_ = c["dims"]
+    model = load_ae(MODELS[c["kind"]](A_, D_, S_, L_, embed_dim=E_), c["P"], c["Bf"]).to(DEV).set_precision(prec).train()
     return model, FusedAdamW(model.parameters(), lr=LR, weight_decay=WD)
 
 

@@ -47,17 +47,22 @@ OUTS = ("out", "mu", "logvar")
 _cases = {}
 
 
-def case(kind, B):
-    """Seeded inputs of one (kind, batch), built once and left unchanged; the oracle results are kept with them."""
-    key = (kind, B)
+def case(kind, B, dims=(A, D, S, L, E), settle=False):
+    """Seeded inputs of one (kind, batch, widths), built once and left unchanged; the oracle results are kept with them.
+    settle: no kept ReLU gate of the encoder within fp32 rounding of zero (width_cases.settle_gates)."""
+    key = (kind, B, tuple(dims), settle)
     if key not in _cases:
         seed = 100 + B
-        P, Bf = O.make_params(seed, A, D, S, L, E)
-        a, b, site = O.make_batch(seed + 1, B, A, D, S)
-        masks, eps = O.make_noise(seed + 2, B, L)
+        A_, D_, S_, L_, E_ = dims
+        P, Bf = O.make_params(seed, A_, D_, S_, L_, E_)
+        a, b, site = O.make_batch(seed + 1, B, A_, D_, S_)
+        masks, eps = O.make_noise(seed + 2, B, L_)
         x, tgt = (a, b) if kind == "rna2dna" else (b, a)
-        _cases[key] = dict(kind=kind, B=B, P=P, Bf=Bf, P64=f64(P), Bf64=f64(Bf), x=x, tgt=tgt, site=site, masks=masks, eps=eps,
-                           ren=O.directional_param_names(kind, A, D, S, L, E), ref={})
+        if settle:
+            import width_cases as W
+            masks, _ = W.settle_gates(masks, W.directional_gates(kind, f64(P), f64(Bf), x.astype(np.float64), site, eps.astype(np.float64)))
+        _cases[key] = dict(kind=kind, B=B, dims=tuple(dims), P=P, Bf=Bf, P64=f64(P), Bf64=f64(Bf), x=x, tgt=tgt, site=site, masks=masks, eps=eps,
+                           ren=O.directional_param_names(kind, A_, D_, S_, L_, E_), ref={})
     return _cases[key]
 
 
@@ -79,7 +84,8 @@ def oracle(c, q, rounded=False):
 
 def build(c, prec):
     cls = RNA2DNAVAE if c["kind"] == "rna2dna" else DNA2RNAVAE
-    model = load_state(cls(A, D, S, L, embed_dim=E), c["P"], c["Bf"], c["ren"]).to(DEV).set_precision(prec).train()
+    A_, D_, S_, L_, E_ = c["dims"]
+    model = load_state(cls(A_, D_, S_, L_, embed_dim=E_), c["P"], c["Bf"], c["ren"]).to(DEV).set_precision(prec).train()
     return model, FusedAdamW(model.parameters(), lr=LR, weight_decay=WD)
 
 

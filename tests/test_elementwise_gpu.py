@@ -268,7 +268,14 @@ def test_fuse_reparam_bwd_refusals():
 # =============================================================================================
 # EncoderC table
 # =============================================================================================
-EMBED_SHAPES = [(6, 8, 4), (24, 32, 20), (24, 32, 128), (5, 3, 7)]
+# (32, 32, 128): 68 KiB of operands, the first size past the default dynamic-LDS limit (refused until the launch learnt to raise it);
+# (24, 64, 100): the corner of the reference's hyperparameter search, 74.75 KiB; (76, 64, 128): 159 KiB, the last size the CU's LDS holds
+EMBED_SHAPES = [(6, 8, 4), (24, 32, 20), (24, 32, 128), (5, 3, 7), (32, 32, 128), (24, 64, 100), (76, 64, 128)]
+EMBED_LDS_MAX = 160 * 1024                       # mmvae_embed_table_bwd's capacity (include/mmvae_hip.h)
+
+
+def embed_lds_bytes(S, Ed, Ld, heads=2):
+    return (S * heads * Ld + S * Ed + heads * Ld * Ed) * 4
 
 
 def _embed_params(rng, S, Ed, Ld):
@@ -314,9 +321,17 @@ def test_embed_table_bwd(S, Ed, Ld, copies):
     inside(np.concatenate([host(d_bm), host(d_bl)]), ref[2], tol[2], tag + " d_b")
 
 
-def test_embed_table_bwd_refuses_operands_beyond_64k_of_lds():
-    S, Ed, Ld = 32, 32, 128                       # (S 2L + S E + 2L E) floats = 68 KiB; 24 sites: 59 KiB, accepted above
-    assert (S * 2 * Ld + S * Ed + 2 * Ld * Ed) * 4 > 64 * 1024 >= (24 * 2 * Ld + 24 * Ed + 2 * Ld * Ed) * 4
+def test_embed_table_bwd_sizes_straddle_both_lds_limits():
+    """EMBED_SHAPES holds the default dynamic-LDS limit (64 KiB) and the capacity (160 KiB) from both sides."""
+    sizes = sorted(embed_lds_bytes(*s) for s in EMBED_SHAPES)
+    assert any(b <= 64 * 1024 for b in sizes) and any(64 * 1024 < b <= EMBED_LDS_MAX for b in sizes)
+    assert embed_lds_bytes(24, 32, 128) <= 64 * 1024 < embed_lds_bytes(32, 32, 128)
+    assert embed_lds_bytes(76, 64, 128) <= EMBED_LDS_MAX < embed_lds_bytes(77, 64, 128)
+
+
+def test_embed_table_bwd_refuses_operands_beyond_the_cu_lds():
+    S, Ed, Ld = 77, 64, 128                       # (S 2L + S E + 2L E) floats = 160.25 KiB; 76 sites: 159 KiB, accepted above
+    assert embed_lds_bytes(S, Ed, Ld) > EMBED_LDS_MAX >= embed_lds_bytes(S - 1, Ed, Ld)
     rng = np.random.default_rng(4)
     emb, wm, bm, wl, bl = _embed_params(rng, S, Ed, Ld)
     outs = [torch.full(s, 5.0, device=DEV) for s in ((S, Ed), (Ld, Ed), (Ld,), (Ld, Ed), (Ld,))]

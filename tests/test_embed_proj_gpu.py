@@ -1,7 +1,8 @@
 """mmvae_embed_proj_fwd / _bwd -- the autoencoders' Embedding -> Linear(embed, latent) table, the one-head case of EncoderC's table
 kernels -- one launch at a time against float64, held to the derived bounds of tests/ae_bounds.py (elementwise_bounds.embed_* with an
-empty second head).  The backward runs with 1, 8 and 11 scatter copies onto non-zero old gradients; what the entry point refuses
-(operands beyond 64 KiB of LDS) must leave every output untouched."""
+empty second head).  The backward runs with 1, 8 and 11 scatter copies onto non-zero old gradients, on both sides of the default
+dynamic-LDS limit (64 KiB) and up to the capacity (160 KiB); what the entry point refuses (operands beyond that) must leave every
+output untouched."""
 import numpy as np
 import pytest
 import torch
@@ -14,7 +15,9 @@ from test_elementwise_gpu import dev, host, rnd, inside, snapshot, unchanged, NA
 from mmvae import _lib as L  # noqa: E402
 from mmvae import ops  # noqa: E402
 
-SHAPES = [(24, 32, 20), (5, 16, 7), (1, 32, 1)]
+# (64, 32, 160): 68 KiB of operands, the first size past the default dynamic-LDS limit (refused until the launch learnt to raise it);
+# (24, 64, 100): the corner of the reference's hyperparameter search; (76, 64, 256): 159 KiB, the last size the CU's LDS holds
+SHAPES = [(24, 32, 20), (5, 16, 7), (1, 32, 1), (64, 32, 160), (24, 64, 100), (76, 64, 256)]
 
 
 def _params(rng, S, Ed, Ld):
@@ -55,9 +58,9 @@ def test_embed_proj_bwd(S, Ed, Ld, copies):
     inside(host(d_b), ref[2], tol[2], tag + " d_b")
 
 
-def test_embed_proj_bwd_refuses_operands_beyond_64k_of_lds():
-    S, Ed, Ld = 64, 32, 160                       # (S L + S E + L E) floats = 68 KiB; 48 sites: 56 KiB, accepted below
-    assert (S * Ld + S * Ed + Ld * Ed) * 4 > 64 * 1024 >= (48 * Ld + 48 * Ed + Ld * Ed) * 4
+def test_embed_proj_bwd_refuses_operands_beyond_the_cu_lds():
+    S, Ed, Ld = 77, 64, 256                       # (S L + S E + L E) floats = 160.25 KiB; 76 sites (159 KiB) and 48 (124 KiB) are accepted
+    assert (S * Ld + S * Ed + Ld * Ed) * 4 > 160 * 1024 >= (76 * Ld + 76 * Ed + Ld * Ed) * 4
     rng = np.random.default_rng(4)
     emb, w, b = _params(rng, S, Ed, Ld)
     outs = [torch.full(s, 5.0, device=DEV) for s in ((S, Ed), (Ld, Ed), (Ld,))]

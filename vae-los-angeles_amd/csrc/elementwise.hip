@@ -1021,7 +1021,18 @@ template <int HEADS>
 static int launch_embed_table_bwd(EmbedBwd a, void* stream) {
     if (a.copies < 1) a.copies = 1;
     const size_t lds = embed_bwd_lds(a.S, a.E, a.L, HEADS);
-    if (lds > EMBED_BWD_LDS_MAX) return MMVAE_ERR_ARG;
+    if (lds > EMBED_BWD_LDS_BIG) return MMVAE_ERR_ARG;
+    if (lds > EMBED_BWD_LDS_MAX) {
+        // the same kernel with more dynamic LDS.  The size varies from call to call, so the attribute is set once to the most the
+        // launch ever takes (launch_lds would set it to the first call's size).  Once per process, for the device current then, and
+        // unguarded -- rt_launch_dyn_lds's contract: one device per process, one calling thread (include/mmvae_hip.h)
+        static bool attr_done = false;
+        if (!attr_done) {
+            hipError_t e = hipFuncSetAttribute((const void*)embed_table_bwd_kernel<HEADS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)EMBED_BWD_LDS_BIG);
+            if (e != hipSuccess) return (int)e;
+            attr_done = true;
+        }
+    }
     hipLaunchKernelGGL(embed_table_bwd_kernel<HEADS>, dim3(embed_bwd_blocks(a.S, a.E, a.L, HEADS)), dim3(256), lds, (hipStream_t)stream, a);
     MM_CHECK_LAUNCH();
     return 0;

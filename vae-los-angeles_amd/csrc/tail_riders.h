@@ -11,7 +11,10 @@ struct EmbedBwd {
     const float* emb; const float* w_mu; const float* w_lv; const float* dTc;
     float* d_emb; float* d_w_mu; float* d_b_mu; float* d_w_lv; float* d_b_lv;
 };
-constexpr size_t EMBED_BWD_LDS_MAX = 64 * 1024;          // the stand-alone launch's capacity (60 KB at latent 128, embed 32, 24 sites); a rider takes no more
+constexpr size_t EMBED_BWD_LDS_MAX = 64 * 1024;          // the default dynamic-LDS limit (60 KB at latent 128, embed 32, 24 sites); a rider takes no more
+// The stand-alone launch's capacity: operands past EMBED_BWD_LDS_MAX run the same kernel with the attribute raised to the CU's whole
+// LDS (74.75 KB at latent 100, embed 64, 24 sites -- the corner of the reference's hyperparameter search)
+constexpr size_t EMBED_BWD_LDS_BIG = 160 * 1024;
 // heads: 2 = EncoderC's (mu | logvar) table, 1 = the autoencoders' one projection (w_lv / d_w_lv / d_b_lv unused, L2 = L below)
 static inline size_t embed_bwd_lds(int S, int E, int L, int heads = 2) { return ((size_t)S * heads * L + (size_t)S * E + (size_t)heads * L * E) * sizeof(float); }
 static inline int embed_bwd_blocks(int S, int E, int L, int heads = 2) { return (S * E + heads * L * E + heads * L + 255) / 256; }       // one output element per thread

@@ -412,15 +412,19 @@ def gemm_tn_group(prec, problems, slab, tag="tiny_dW.group", riders=None):
             arr[j] = _tn_args(prec, pr["p"], pr["q"], pr["dw"], pr["db"], pr["N"], pr["K"], pr.get("q_prologue"), None, 0, slab[off:off + need])
             off += need
             nbytes += pr["p"].shape[0] * (pr["N"] * pr["p"].element_size() + pr["K"] * pr["q"].element_size()) + 4 * pr["N"] * pr["K"]
-        with stream_span(tag if i == 0 else f"{tag}.{i}", nbytes):
+        # the record says which form ran: `grouped` (False: one launch per problem), `riders` (they rode in this launch); built only
+        # when a probe is installed -- probe_span ignores it otherwise
+        meta = dict(kind="stream", bytes=int(nbytes), grouped=True, riders=False) if PROBE is not None else {}
+        with probe_span(tag if i == 0 else f"{tag}.{i}", meta):
             if i == 0 and riders is not None:
                 status = lib.mmvae_gemm_tn_group_riders(C.cast(arr, C.c_void_p), len(chunk), C.byref(riders), _stream())
                 if status != -1:
                     L.check(status, "mmvae_gemm_tn_group_riders")
-                    rode = True
+                    rode = meta["riders"] = True
                     continue
             status = lib.mmvae_gemm_tn_group(C.cast(arr, C.c_void_p), len(chunk), _stream())
             if status == -1:
+                meta["grouped"] = False
                 # a problem outside the grouped kernel's operand combinations (odd widths / alignments): the entry point checks
                 # every problem before it launches anything, so the same argument records go through the one-problem entry
                 for j in range(len(chunk)):
