@@ -433,6 +433,39 @@ int mmvae_class_tail(const mmvae_class_tail_args* args, void* stream);
 int mmvae_class_tail_fits(int32_t prec, int32_t S, int32_t hidden, int32_t L, int64_t ldh0, int64_t ldd0);
 
 /* ---------------------------------------------------------------------------------------------
+ * A Linear whose output rows are reduced in groups ON CHIP (group_moments.hip): the decoder's last layer of a multiple-draw /
+ * all-site reconstruction, where each of B samples owns G consecutive rows of the operand (one per draw and site) and only the
+ * mean and the spread across them are wanted --
+ *   x[b*G + g][j] = act( sum_k a[b*G + g][k] * w[j][k] + bias[j] )     g < G; act = MMVAE_ACT_NONE | MMVAE_ACT_SIGMOID
+ *   mean[b][j]    = (1/G) sum_g x[b*G + g][j]                           (g ascending, one division)
+ *   std[b][j]     = sqrt( sum_g (x[b*G + g][j] - mean[b][j])^2 / (G - 1) )    (optional; a second pass over the stored tile)
+ * i.e. what mmvae_gemm_nt with an fp32 C of B*G rows and a mean / unbiased std over its view [B][G][N] compute, without that C.
+ * x is formed from the fp32 accumulators as mmvae_gemm_nt's store epilogue forms it (bias added in fp32, sigmoid = rcp(1 + exp(-v)))
+ * and is NOT rounded to a storage type.
+ *   a: bf16 [B*G][lda], rows padded to 8 elements with zeroed pad columns, as mmvae_gemm_nt takes its bf16 A.  w / bias: the
+ *   prepared operand ([ceil128(N)][ceil64(K)] bf16, what mmvae_prep_weights writes) and the fp32 bias (or NULL) of the Linear.
+ *   mean / std: fp32 [B][ld_mean] / [B][ld_std]; columns >= N are not touched.  std == NULL: no standard deviation.
+ * Limits (anything else: MMVAE_ERR_ARG / MMVAE_ERR_DTYPE before anything is enqueued; the caller then issues mmvae_gemm_nt and
+ * the reduction this launch replaces):
+ *   prec == MMVAE_PREC_BF16 (MMVAE_PREC_F32: MMVAE_ERR_DTYPE); B >= 1; 1 <= G <= 128 (a 128-row tile holds floor(128 / G) whole
+ *   groups); std only with G >= 2; K % 64 == 0 and 64 <= K <= 512; N >= 1; act one of the two above; a and w 16-byte aligned,
+ *   lda % 8 == 0, lda >= K, ldw % 64 == 0, ldw >= K; mean and std 4-byte aligned, ld_mean >= N, ld_std >= N; B*G*lda*2 and
+ *   (N + 256)*ldw*4 below 2^32 (the 32-bit offsets of the NT kernels; there are no row blocks here).
+ * mmvae_gemm_nt_group_moments_fits answers everything but the pointers and the output strides without operands: 0, or the
+ * error mmvae_gemm_nt_group_moments would return (with_std: std != NULL).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t prec, B, G, N, K, act;
+    const void* a; int64_t lda;
+    const void* w; int64_t ldw; const float* bias;
+    float* mean; int64_t ld_mean;
+    float* std; int64_t ld_std;
+} mmvae_group_moments_args;
+int mmvae_gemm_nt_group_moments(const mmvae_group_moments_args* args, void* stream);
+int mmvae_gemm_nt_group_moments_fits(int32_t prec, int32_t B, int32_t G, int32_t N, int32_t K, int32_t act, int32_t with_std,
+                                     int64_t lda, int64_t ldw);
+
+/* ---------------------------------------------------------------------------------------------
  * vae_loss (src/utils/losses.py:8-46) and the directional losses
  * (src/utils/directional_losses.py:8-55), one pass, optional terms (NULL pointers skip a term):
  *   sums[0] += sum (recon_a-a)^2                               (losses.py:31)

@@ -146,6 +146,14 @@ class ClassTailArgs(C.Structure):
                 ("g_mu", vp), ("g_lv", vp)]
 
 
+class GroupMomentsArgs(C.Structure):
+    _fields_ = [("prec", i32), ("B", i32), ("G", i32), ("N", i32), ("K", i32), ("act", i32),
+                ("a", vp), ("lda", i64),
+                ("w", vp), ("ldw", i64), ("bias", vp),
+                ("mean", vp), ("ld_mean", i64),
+                ("std", vp), ("ld_std", i64)]
+
+
 class FuseBwdArgs(C.Structure):
     _fields_ = [("B", i32), ("L", i32), ("n_mod", i32),
                 ("g_mu", vp), ("g_lv", vp), ("dz", vp), ("dz2", vp), ("dz3", vp), ("lddz", i64),
@@ -291,6 +299,8 @@ _SIGNATURES = {
     "mmvae_ae_latent_fwd": [C.POINTER(AELatentFwdArgs), vp],
     "mmvae_class_tail": [C.POINTER(ClassTailArgs), vp],
     "mmvae_class_tail_fits": [i32, i32, i32, i32, i64, i64],
+    "mmvae_gemm_nt_group_moments": [C.POINTER(GroupMomentsArgs), vp],
+    "mmvae_gemm_nt_group_moments_fits": [i32, i32, i32, i32, i32, i32, i32, i64, i64],
     "mmvae_vae_loss": [C.POINTER(LossArgs), vp],
     "mmvae_loss_finalize": [vp, f32, f32, vp, vp, vp],
     "mmvae_recon_metrics": [C.POINTER(MetricsArgs), vp],

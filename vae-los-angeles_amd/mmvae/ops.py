@@ -732,6 +732,47 @@ def class_tail(prec, B, h0, head, site, class_weights, mu, logvar, beta, gamma, 
         L.check(L.load().mmvae_class_tail(C.byref(a), _stream()), "mmvae_class_tail")
 
 
+GROUP_MOMENTS_MAX_G = TILE      # rows of the kernel's tile: a group must fit into one
+
+
+def group_moments_fits(prec, B, G, N, K, act=ACT_NONE, with_std=False, lda=None, ldw=None):
+    """Would mmvae_gemm_nt_group_moments take this shape?  The library's own limits (lda / ldw default to the padded widths)."""
+    lda = ceil_to(K, 8) if lda is None else lda
+    ldw = ceil_to(K, 64) if ldw is None else ldw
+    return L.load().mmvae_gemm_nt_group_moments_fits(prec, B, G, N, K, act, int(with_std), lda, ldw) == 0
+
+
+def gemm_nt_group_moments(prec, a, pl_w, N, K, G, mean, std=None, bias=None, act=ACT_NONE):
+    """mmvae_gemm_nt_group_moments: x = act(a[B G, K] @ W[N, K]^T + bias) reduced over every G consecutive rows, on chip, to
+    mean (B, N) and, if given, the unbiased std (B, N) -- both fp32 views with unit inner stride whose columns >= N stay untouched.
+    a: bf16 padded rows (is_bf16_rows); pl_w: the prepared weight of a PreparedLinear.  Raises MMVAEArgError, with nothing
+    enqueued, for what the kernel does not take (fp32 mode, G > 128, ...): the caller then issues gemm_nt and the reduction."""
+    what = "gemm_nt_group_moments"
+    a = _operand(a, "a", what, dtypes=None)
+    if G < 1 or a.shape[0] % G:
+        raise ValueError(f"{what}: a has {a.shape[0]} rows, not a multiple of G = {G}")
+    B, dev = a.shape[0] // G, a.device
+    pl_w = _operand(pl_w, "w", what, dtypes=None, dev=dev)
+    mean = _operand(mean, "mean", what, dtypes=(torch.float32,), rows=B, dev=dev)
+    if std is not None:
+        std = _operand(std, "std", what, dtypes=(torch.float32,), rows=B, dev=dev)
+    if mean.shape[1] < N or (std is not None and std.shape[1] < N) or a.shape[1] < K:
+        raise ValueError(f"{what}: a needs >= {K} columns, mean / std >= {N}")
+    if N < 1 or pl_w.shape[0] < ceil_to(N, TILE) or pl_w.shape[1] < K:      # the kernel reads whole 128-row tiles of W
+        raise ValueError(f"{what}: w must be a prepared operand of at least ({ceil_to(max(N, 1), TILE)}, {K}), got {tuple(pl_w.shape)}")
+    if a.dtype != torch.bfloat16 or pl_w.dtype != torch.bfloat16:        # the fp32 compute mode: MMVAE_ERR_DTYPE, as the library answers it
+        raise L.MMVAEArgError(f"{what} failed: dtype not supported for this precision")
+    g = L.GroupMomentsArgs()
+    g.prec, g.B, g.G, g.N, g.K, g.act = prec, B, G, N, K, act
+    g.a, g.lda = a.data_ptr(), _ld(a)
+    g.w, g.ldw, g.bias = pl_w.data_ptr(), pl_w.stride(0), _p(bias)
+    g.mean, g.ld_mean = mean.data_ptr(), _ld(mean)
+    g.std, g.ld_std = _p(std), _ld0(std)
+    with stream_span(what, B * G * K * 2 + N * K * 2 + B * N * 4 * (1 + (std is not None))):
+        L.check(L.load().mmvae_gemm_nt_group_moments(C.byref(g), _stream()), "mmvae_gemm_nt_group_moments")
+    return mean, std
+
+
 def loss_finalize(sums, beta, gamma, out5, beta_gamma_dev=None):
     assert out5.numel() >= 5
     L.check(L.load().mmvae_loss_finalize(sums.data_ptr(), beta, gamma, _p(beta_gamma_dev), out5.data_ptr(), _stream()), "mmvae_loss_finalize")
