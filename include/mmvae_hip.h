@@ -828,6 +828,60 @@ typedef struct {
 int mmvae_pca_project(const mmvae_pca_project_args* args, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * sklearn.preprocessing.StandardScaler on the device (standardize.hip), the first step of every row of the clustering tables
+ * (src/clustering_evaluation/cluster_imputation_methods.py:112-118, cluster_reconstructed.py), on a feature matrix that is GIVEN AS
+ * COLUMN BLOCKS and assembled while it is standardised: the [original | imputed] matrix never exists unstandardised.
+ *
+ * Operand: `rows` samples and n_parts (1 .. MMVAE_STD_MAX_PARTS) parts.  A part is x, dtype (MMVAE_F32 / MMVAE_BF16), cols >= 1 and
+ *   either a (rows, cols) row-major matrix with ld >= cols (in elements), or, with one_row != 0, ONE row of cols values that stands
+ *   for every sample (ld is ignored).  F = the sum of the parts' cols (64-bit: no upper limit); column j of the matrix lies in exactly
+ *   one part.  A part's pointer is aligned to its element and to nothing more; pad columns and rows outside a part are never read.
+ *
+ * mmvae_standardize_fit: StandardScaler().fit on float32 data.  mean, var, scale: float64 [F] each.
+ *   a_i = (double)x_ij - (double)x_0j  (the column's first row is the shift, the same in every split)
+ *   S0 = sum_i a_i,  S1 = sum_i a_i^2,  d = S0 / rows,  mean = x_0j + d,  var = max(S1 / rows - d^2, 0)     (all float64)
+ *   scale = 1 where var <= rows eps var + (rows mean eps)^2 (eps of float64: sklearn's constant-feature rule), else sqrt(var).
+ *   A column of one value, and every column of a one-row part, has a_i = 0: mean = the value, var = 0 and scale = 1 exactly.
+ *   The rows are cut into splits_used consecutive runs of rows_per_split = ceil(rows / want) rows (the last may be short, none is empty):
+ *     ctiles = ceil(F / 64);  want = splits > 0 ? splits : max(1, min(floor(2048 / ctiles), floor(rows / 32)))
+ *     want = min(want, 64, rows);  splits_used = ceil(rows / rows_per_split)                (mmvae_standardize_fit_splits)
+ *   Inside a split the rows r0 + w, r0 + w + 4, ... are summed in ascending order by wave w = 0 .. 3, the four waves are added in wave
+ *   order, the pair (S0, S1) of a split goes to work[split][2][F], and a second launch adds the splits in ascending order.  No
+ *   floating-point atomics: the same arguments and split count give the same bits, whatever `work` held before (every slot that is
+ *   read is written first by the same call).  Additions on the longest path of a sum: at most rows + 3 + splits_used.
+ *   work: caller-owned, 8-byte aligned, at least mmvae_standardize_fit_work_bytes(rows, F, splits) = 16 F splits_used bytes.
+ *   MMVAE_ERR_ARG (nothing enqueued): a null struct, rows < 1, n_parts outside 1 .. MMVAE_STD_MAX_PARTS, a part with cols < 1, a null
+ *   or misaligned x, or (a matrix part) ld < cols; no matrix part at all; null or misaligned (8 bytes) mean / var / scale / work;
+ *   work_bytes too small; splits outside [0, 64].  MMVAE_ERR_DTYPE: a part's dtype that is neither MMVAE_F32 nor MMVAE_BF16.
+ *
+ * mmvae_standardize_apply: StandardScaler.transform.  mean, scale: float64 [F], from any fit.  z [rows][ldz]: fp32, ldz >= F.
+ *   z_ij = (float)(((double)x_ij - mean_j) / scale_j): one float64 subtraction, one float64 DIVISION (not a multiplication by a
+ *   reciprocal), one rounding to fp32, nothing contracted -- the bits of numpy's ((x.astype(f8) - mean) / scale).astype(f4).
+ *   Columns F .. ldz - 1 of z are not written.  z must not overlap a part.  Parts may all be one-row here.
+ *   MMVAE_ERR_ARG (nothing enqueued): as above for rows and the parts; null mean / scale / z or one not aligned to its element;
+ *   ldz < F.  MMVAE_ERR_DTYPE: as above.
+ * ------------------------------------------------------------------------------------------- */
+#define MMVAE_STD_MAX_PARTS 4
+typedef struct { const void* x; int64_t ld; int32_t cols, dtype, one_row, pad_; } mmvae_std_part;
+typedef struct {
+    mmvae_std_part part[MMVAE_STD_MAX_PARTS];
+    double* mean; double* var; double* scale; void* work;
+    int64_t work_bytes;
+    int32_t rows, n_parts, splits, pad_;
+} mmvae_standardize_fit_args;
+int mmvae_standardize_fit(const mmvae_standardize_fit_args* args, void* stream);
+/* need no device; MMVAE_ERR_ARG for rows < 1, F < 1, splits outside [0, 64] or a null result pointer */
+int mmvae_standardize_fit_splits(int32_t rows, int64_t F, int32_t splits, int32_t* splits_used);
+int mmvae_standardize_fit_work_bytes(int32_t rows, int64_t F, int32_t splits, int64_t* bytes);
+typedef struct {
+    mmvae_std_part part[MMVAE_STD_MAX_PARTS];
+    const double* mean; const double* scale; float* z;
+    int64_t ldz;
+    int32_t rows, n_parts;
+} mmvae_standardize_apply_args;
+int mmvae_standardize_apply(const mmvae_standardize_apply_args* args, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * t-SNE in two dimensions with the exact all-pairs repulsion (tsne.hip): sklearn's TSNE(2, method="barnes_hut") at angle = 0 -- the
  * sparse P of the int(3 perplexity + 1) nearest neighbours, every pair in the repulsion -- with no tree.  Replaces
  * TSNE(n_components=2, random_state=42, perplexity=min(30, n - 1)) over host copies

@@ -24,6 +24,7 @@ SIL_MAXC = 64           # MMVAE_SIL_MAXC
 PCA_MAXK = 64           # MMVAE_PCA_MAXK
 LN_MAXN = 1024          # MMVAE_LN_MAXN
 WCE_MAXC = 64           # MMVAE_WCE_MAXC
+STD_MAX_PARTS = 4       # MMVAE_STD_MAX_PARTS
 CTR_COPIES = 16384      # MMVAE_CTR_COPIES: self-advancing device counters are stored as this many identical int64 copies
 
 i32, i64, f32, vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
@@ -228,6 +229,24 @@ class PcaProjectArgs(C.Structure):
                 ("N", i32), ("F", i32), ("k", i32), ("x_dtype", i32)]
 
 
+class StdPart(C.Structure):
+    _fields_ = [("x", vp), ("ld", i64), ("cols", i32), ("dtype", i32), ("one_row", i32), ("pad_", i32)]
+
+
+class StandardizeFitArgs(C.Structure):
+    _fields_ = [("part", StdPart * STD_MAX_PARTS),
+                ("mean", vp), ("var", vp), ("scale", vp), ("work", vp),
+                ("work_bytes", i64),
+                ("rows", i32), ("n_parts", i32), ("splits", i32), ("pad_", i32)]
+
+
+class StandardizeApplyArgs(C.Structure):
+    _fields_ = [("part", StdPart * STD_MAX_PARTS),
+                ("mean", vp), ("scale", vp), ("z", vp),
+                ("ldz", i64),
+                ("rows", i32), ("n_parts", i32)]
+
+
 class TsneAffinitiesArgs(C.Structure):
     _fields_ = [("dist2", vp), ("p", vp), ("beta", vp),
                 ("ld_dist2", i64), ("ld_p", i64),
@@ -320,6 +339,10 @@ _SIGNATURES = {
     "mmvae_pca_scatter_splits": [i32, i32, i32, C.POINTER(i32)],
     "mmvae_pca_scatter_work_bytes": [i32, i32, i32, C.POINTER(i64)],
     "mmvae_pca_project": [C.POINTER(PcaProjectArgs), vp],
+    "mmvae_standardize_fit": [C.POINTER(StandardizeFitArgs), vp],
+    "mmvae_standardize_fit_splits": [i32, i64, i32, C.POINTER(i32)],
+    "mmvae_standardize_fit_work_bytes": [i32, i64, i32, C.POINTER(i64)],
+    "mmvae_standardize_apply": [C.POINTER(StandardizeApplyArgs), vp],
     "mmvae_tsne_affinities": [C.POINTER(TsneAffinitiesArgs), vp],
     "mmvae_tsne_gradient": [C.POINTER(TsneGradientArgs), vp],
     "mmvae_tsne_gradient_splits": [i32, i32, C.POINTER(i32)],

@@ -2,6 +2,8 @@
 labels) and calculate_neighborhood_hit (src/clustering_evaluation/cluster_imputation_methods.py:478-504, cluster_reconstructed.py:299-317).
 
     Z = standardize(features)                      # StandardScaler().fit_transform, fp32 on the device
+    Z = StandardScaler().fit_transform([original, imputed])    # the same on mmvae_standardize_fit / _apply: the matrix is assembled from
+                                                   # its column blocks while it is standardised (an imputed mean row stays one row)
     s = silhouette_samples(Z, labels)              # fp32 (N,) on the device
     score = silhouette_score(Z, labels)            # Python float
     nh = neighborhood_hit(Z, labels, k=5)
@@ -18,7 +20,7 @@ from .knn import neighborhood_hit  # noqa: F401  (neighborhood_hit: re-exported)
 from .pca import PCA  # noqa: F401  (re-exported: the table's PCA columns)
 from .tsne import TSNE  # noqa: F401  (re-exported: the table's t-SNE columns)
 
-__all__ = ["silhouette_samples", "silhouette_score", "standardize", "neighborhood_hit", "PCA", "TSNE"]
+__all__ = ["silhouette_samples", "silhouette_score", "standardize", "StandardScaler", "neighborhood_hit", "PCA", "TSNE"]
 
 
 def _encode(labels, N, device):
@@ -67,3 +69,33 @@ def standardize(X):
     constant = var <= n * eps * var + (n * mean * eps) ** 2
     scale = torch.where(constant, torch.ones_like(var), var.sqrt())
     return ((Xd - mean) / scale).float().contiguous()
+
+
+class StandardScaler:
+    """sklearn.preprocessing.StandardScaler() (with_mean, with_std) on mmvae_standardize_fit / mmvae_standardize_apply.  `parts` is one
+    tensor or a sequence of up to four column blocks of the feature matrix: each a 2-D fp32 / bf16 device matrix, or a 1-D tensor, one
+    row that stands for every sample (a mean imputation); the row count is that of the matrix parts, of which there is at least one.
+    mean_, var_, scale_: float64 (F,) device tensors; transform gives fp32 (rows, F), contiguous."""
+
+    def __init__(self):
+        self.mean_ = self.var_ = self.scale_ = self.n_samples_seen_ = None
+
+    @staticmethod
+    def _parts(parts):
+        """the parts detached; what they must be is checked in one place, ops._std_parts"""
+        parts = (parts,) if isinstance(parts, torch.Tensor) else tuple(parts)
+        return tuple(t.detach() if isinstance(t, torch.Tensor) else t for t in parts)
+
+    def fit(self, parts):
+        parts = self._parts(parts)
+        self.mean_, self.var_, self.scale_ = ops.standardize_fit(parts)
+        self.n_samples_seen_ = next(t.shape[0] for t in parts if t.dim() == 2)
+        return self
+
+    def transform(self, parts):
+        if self.mean_ is None:
+            raise RuntimeError("StandardScaler.transform before fit")
+        return ops.standardize_apply(self._parts(parts), self.mean_, self.scale_)
+
+    def fit_transform(self, parts):
+        return self.fit(parts).transform(parts)

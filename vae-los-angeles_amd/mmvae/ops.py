@@ -1249,6 +1249,91 @@ def pca_project(x, shift, v, out=None):
 
 
 # --------------------------------------------------------------------------------------------
+# StandardScaler on column blocks (include/mmvae_hip.h: mmvae_standardize_fit, mmvae_standardize_apply)
+# --------------------------------------------------------------------------------------------
+def standardize_fit_splits(rows, F, splits=0):
+    """The number of row splits standardize_fit uses for these sizes and this request (mmvae_standardize_fit_splits); needs no device."""
+    return _plan("mmvae_standardize_fit_splits", rows, F, splits)
+
+
+def standardize_fit_work_bytes(rows, F, splits=0):
+    return _plan("mmvae_standardize_fit_work_bytes", rows, F, splits, outs=(C.c_int64,))
+
+
+def _std_parts(parts, what, rows=None):
+    """(parts, rows, F, device, bytes read) of a feature matrix given as column blocks: one tensor or a sequence of 1 .. STD_MAX_PARTS,
+    each a 2-D fp32 / bf16 device matrix (checked with _operand) or a 1-D tensor: one row that stands for every sample."""
+    if isinstance(parts, torch.Tensor):
+        parts = (parts,)
+    parts = tuple(parts)
+    if not 1 <= len(parts) <= L.STD_MAX_PARTS:
+        raise ValueError(f"{what}: {len(parts)} parts, need 1 .. {L.STD_MAX_PARTS}")
+    dev = None
+    for i, t in enumerate(parts):
+        _no_cpu(t, f"parts[{i}]", what)
+        dev = t.device if dev is None else dev
+        if t.dim() == 1:
+            if t.dtype not in (torch.float32, torch.bfloat16) or t.shape[0] < 1 or (t.shape[0] > 1 and t.stride(0) != 1) or t.device != dev:
+                raise ValueError(f"{what}: parts[{i}] (one row) must be a fp32 / bf16 (cols >= 1,) tensor with unit stride on the operands' "
+                                 f"device; got {tuple(t.shape)} {t.dtype} / {t.stride()}")
+        else:
+            _operand(t, f"parts[{i}]", what, rows=rows, dev=dev)
+            rows = t.shape[0]
+    if rows is None:
+        raise ValueError(f"{what}: every part is one row: the row count must come from a matrix part or from rows=")
+    F = sum(t.shape[-1] for t in parts)
+    nbytes = sum((1 if t.dim() == 1 else rows) * t.shape[-1] * t.element_size() for t in parts)
+    return parts, int(rows), F, dev, nbytes
+
+
+def _std_fill(a, parts):
+    for i, t in enumerate(parts):
+        a.part[i] = L.StdPart(t.data_ptr(), 0 if t.dim() == 1 else _ld(t), t.shape[-1], _dt(t), int(t.dim() == 1), 0)
+    a.n_parts = len(parts)
+
+
+def standardize_fit(parts, *, splits=0, mean_out=None, var_out=None, scale_out=None, work=None):
+    """StandardScaler().fit of the matrix whose column blocks are `parts` (mmvae_standardize_fit): (mean, var, scale), float64 (F,) each.
+    parts: see _std_parts; at least one is a matrix.  splits: 0 = the library's choice, 1 .. 64 forces that many row splits.  *_out:
+    write into these.  work: a workspace to use (an int64 tensor of at least standardize_fit_work_bytes(rows, F, splits) bytes, any
+    contents)."""
+    what = "standardize_fit"
+    parts, rows, F, dev, nbytes = _std_parts(parts, what)
+    if all(t.dim() == 1 for t in parts):
+        raise ValueError(f"{what}: every part is one row: at least one matrix part is required")
+    splits = _splits_arg(splits, what)
+    outs = [_out_vector(o, name, what, torch.float64, F, dev) for o, name in ((mean_out, "mean_out"), (var_out, "var_out"), (scale_out, "scale_out"))]
+    work = _work(work, standardize_fit_work_bytes(rows, F, splits), what, dev)
+    a = L.StandardizeFitArgs()
+    _std_fill(a, parts)
+    a.mean, a.var, a.scale, a.work, a.work_bytes = outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(), work.data_ptr(), work.numel() * 8
+    a.rows, a.splits = rows, splits
+    with stream_span("standardize_fit", nbytes + 24 * F):
+        L.check(L.load().mmvae_standardize_fit(C.byref(a), _stream()), "mmvae_standardize_fit")
+    return tuple(outs)
+
+
+def standardize_apply(parts, mean, scale, *, rows=None, out=None):
+    """StandardScaler.transform of the matrix whose column blocks are `parts` (mmvae_standardize_apply): z = (float)(((double)x - mean) /
+    scale), fp32 (rows, F).  mean, scale: float64 (F,), from any fit.  rows: only where every part is one row.  out: write into this
+    (a view with a row stride >= F is allowed; its other columns are not written); it may not share STORAGE with a part: the refusal
+    compares the storages, not the extents, so disjoint views of one buffer are refused too (an `out` allocated here shares nothing)."""
+    what = "standardize_apply"
+    parts, rows, F, dev, nbytes = _std_parts(parts, what, rows)
+    mean = _vector(mean, "mean", what, torch.float64, F, dev)
+    scale = _vector(scale, "scale", what, torch.float64, F, dev)
+    z = _out_view(out, "out", what, torch.float32, rows, F, dev)
+    if out is not None and any(t.untyped_storage().data_ptr() == z.untyped_storage().data_ptr() for t in parts):
+        raise ValueError(f"{what}: out shares its storage with a part")
+    a = L.StandardizeApplyArgs()
+    _std_fill(a, parts)
+    a.mean, a.scale, a.z, a.ldz, a.rows = mean.data_ptr(), scale.data_ptr(), z.data_ptr(), _ld(z), rows
+    with stream_span("standardize_apply", nbytes + 16 * F + 4 * rows * F):
+        L.check(L.load().mmvae_standardize_apply(C.byref(a), _stream()), "mmvae_standardize_apply")
+    return z
+
+
+# --------------------------------------------------------------------------------------------
 # t-SNE (include/mmvae_hip.h: mmvae_tsne_affinities, mmvae_tsne_gradient, mmvae_tsne_update)
 # --------------------------------------------------------------------------------------------
 def tsne_affinities(dist2, perplexity, *, p_out=None, beta_out=None):
