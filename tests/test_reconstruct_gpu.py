@@ -158,6 +158,46 @@ def test_a_group_above_128_goes_through_the_fallback(monkeypatch):
     within(host(std), s, ts, "reconstruct G 129 (fallback) std")
 
 
+@pytest.mark.parametrize("kind,sites,draws", [("rna2dna", "given", 1), ("rna2dna", "given", 3), ("dna2rna", "all", 2)])
+def test_batched_is_the_batches_in_one_stream_bit_for_bit(kind, sites, draws):
+    """reconstruct_batched over 9 rows in batches of 4 (two full, one ragged) = reconstruct() over the same slices, concatenated, in ONE
+    Philox stream from (seed, offset 0): the position is set before the first batch, not per batch; and a second call repeats it."""
+    model, rec, x, site = setup(kind)                           # the noise position is kept per device: x.device, cuda:0, not "cuda"
+    rows, batch, seed = 9, 4, 77
+    x, site = x[:rows], site[:rows]
+    xh = x.cpu().numpy()
+    sh = site.cpu().numpy() if sites == "given" else None
+    want_std = rec.group_size(draws, sites) > 1
+    assert rec.group_size(draws, sites) == {"given": draws, "all": 10}[sites]
+    seed0, pos0 = torch.initial_seed(), engine.GLOBAL_NOISE.state_dict(x.device)
+    try:
+        got = [rec.reconstruct_batched(xh, sh, draws=draws, sites=sites, batch_size=batch, seed=seed) for _ in range(2)]
+        torch.manual_seed(seed)
+        engine.GLOBAL_NOISE.load_state_dict({"offset": 0}, x.device)
+        parts = [rec.reconstruct(x[i:i + batch], site[i:i + batch] if sites == "given" else None, draws=draws, sites=sites, return_std=want_std)
+                 for i in range(0, rows, batch)]
+    finally:
+        torch.manual_seed(seed0)
+        engine.GLOBAL_NOISE.load_state_dict(pos0, x.device)
+    assert [p[0].shape[0] for p in parts] == [4, 4, 1]
+    mean = torch.cat([p[0] for p in parts]).cpu().numpy()
+    for m, s in got:
+        assert m.dtype == np.float32 and m.shape == (rows, mean.shape[1]) and np.array_equal(m, mean)
+        if want_std:
+            assert s.dtype == np.float32 and np.array_equal(s, torch.cat([p[1] for p in parts]).cpu().numpy())
+        else:
+            assert s is None
+    # the stream moves from batch to batch: were the position set per batch, equal rows of two batches would reconstruct equally
+    twice = np.concatenate([xh[:batch], xh[:batch]])
+    st = None if sh is None else np.concatenate([sh[:batch], sh[:batch]])
+    try:
+        m2, _ = rec.reconstruct_batched(twice, st, draws=draws, sites=sites, batch_size=batch, seed=seed)
+    finally:
+        torch.manual_seed(seed0)
+        engine.GLOBAL_NOISE.load_state_dict(pos0, x.device)
+    assert np.array_equal(m2[:batch], mean[:batch]) and not np.array_equal(m2[batch:], m2[:batch])
+
+
 def test_value_errors():
     model, rec, x, site = setup("rna2dna")
     with pytest.raises(ValueError):

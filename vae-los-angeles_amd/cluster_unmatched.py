@@ -14,7 +14,6 @@ import argparse
 import glob
 import json
 import os
-import pickle
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -24,12 +23,12 @@ if HERE not in sys.path:
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+import hostlib  # noqa: E402
+from hostlib import ORIGINAL, RECON  # noqa: E402
+from mmvae.data import load_pickled_dataset, synthetic_dataset  # noqa: E402
+from mmvae.reconstruct import Reconstructor  # noqa: E402
 from mmvae.unmatched import METHODS, SAMPLE_TYPES, SCALINGS  # noqa: E402
 from src.config import Config  # noqa: E402
-
-RECON = {"RNA-only": ("rna_with_reconstructed_dna_", "reconstructed_beta_value"),
-         "DNA-only": ("dna_with_reconstructed_rna_", "reconstructed_tpm_unstranded")}
-ORIGINAL = {"RNA-only": "tpm_unstranded", "DNA-only": "beta_value"}
 
 
 def build_parser():
@@ -50,11 +49,9 @@ def build_parser():
     ap.add_argument("--checkpoint-dir", default=Config.CHECKPOINT_DIR)
     ap.add_argument("--checkpoint-rna2dna", default=None)
     ap.add_argument("--checkpoint-dna2rna", default=None)
-    ap.add_argument("--input-dim-a", type=int, default=int(os.getenv("INPUT_DIM_A", 782)))
-    ap.add_argument("--input-dim-b", type=int, default=int(os.getenv("INPUT_DIM_B", 572)))
-    ap.add_argument("--latent-dim", type=int, default=int(os.getenv("LATENT_DIM", Config.LATENT_DIM)))
+    hostlib.add_model_args(ap)
     ap.add_argument("--batch-size", type=int, default=4096)
-    ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32"])
+    hostlib.add_precision_args(ap, input_dtype=False)
     return ap
 
 
@@ -73,68 +70,42 @@ def find_latest_reconstruction_files(data_dir, ts=None):
 
 def synthetic_inputs(args):
     """-> (train (rna, dna, site) tensors, classes, RNA-only frame with RAW TPM, DNA-only frame), sites on both frames"""
-    import pandas as pd
-    from trainer import synthetic_dataset
-    n, n_sites = args.synthetic, 24
-    classes = np.array([f"site_{i:02d}" for i in range(n_sites)])
-    train = synthetic_dataset(n, args.input_dim_a, args.input_dim_b, n_sites, args.seed)
-    tpm, _, site_r = synthetic_dataset(n, args.input_dim_a, args.input_dim_b, n_sites, args.seed + 1)
-    _, beta, site_d = synthetic_dataset(n, args.input_dim_a, args.input_dim_b, n_sites, args.seed + 2)
-    rna = pd.DataFrame({"case_barcode": [f"RNA-{i:06d}" for i in range(n)], "tpm_unstranded": list(np.expm1(tpm.numpy())),
-                        "primary_site": classes[site_r.numpy()]})
-    dna = pd.DataFrame({"case_barcode": [f"DNA-{i:06d}" for i in range(n)], "beta_value": list(beta.numpy()),
-                        "primary_site": classes[site_d.numpy()]})
-    return train, classes, rna, dna
+    n, classes = args.synthetic, hostlib.SYNTHETIC_CLASSES
+    train = synthetic_dataset(n, args.input_dim_a, args.input_dim_b, len(classes), args.seed)
+    tpm, _, site_r = synthetic_dataset(n, args.input_dim_a, args.input_dim_b, len(classes), args.seed + 1)
+    _, beta, site_d = synthetic_dataset(n, args.input_dim_a, args.input_dim_b, len(classes), args.seed + 2)
+    return train, classes, hostlib.synthetic_frame("RNA-only", np.expm1(tpm.numpy()), classes[site_r.numpy()]), \
+        hostlib.synthetic_frame("DNA-only", beta.numpy(), classes[site_d.numpy()])
 
 
 def load_inputs(args):
-    import pandas as pd
-    from trainer import load_pickled_dataset
-    path = lambda name: os.path.join(args.data_dir, name)
-    with open(path("label_encoder.pkl"), "rb") as f:
-        classes = np.asarray(pickle.load(f).classes_)
-    train = load_pickled_dataset(path("processed_data.pkl")) if os.path.exists(path("processed_data.pkl")) else None
+    classes = hostlib.read_classes(args.data_dir)
+    matched = os.path.join(args.data_dir, "processed_data.pkl")
+    train = load_pickled_dataset(matched) if os.path.exists(matched) else None
     if train is None:
-        print(f"Training data not found: {path('processed_data.pkl')}: mean / knn / cond_knn cannot run")
-    frames = []
-    for name, what in (("rna_only_unmatched.pkl", "RNA-only"), ("dna_only_unmatched.pkl", "DNA-only")):
-        if os.path.exists(path(name)):
-            frames.append(pd.read_pickle(path(name)))
-        else:
-            print(f"{what} data file not found: {path(name)} (the reference's scripts/prepare_data.py writes it)")
-            frames.append(None)
-    return train, classes, frames[0], frames[1]
+        print(f"Training data not found: {matched}: mean / knn / cond_knn cannot run")
+    return (train, classes, *hostlib.read_unmatched_frames(args.data_dir))
 
 
 def known_sites(df, classes, what):
     """the frame filtered to the sites the label encoder knows, and their codes (None without primary_site)"""
-    if df is None or "primary_site" not in df.columns:
-        return df, None
-    known = df["primary_site"].isin(classes)
-    if not known.all():
-        print(f"  {what}: filtered out {int((~known).sum())} samples with primary_site not in label_encoder")
-    df = df[known]
-    return df, np.searchsorted(classes, df["primary_site"].to_numpy()).astype(np.int64)
+    return hostlib.known_sites(df, classes, f"  {what}: filtered out {{n}} samples with primary_site not in label_encoder")
 
 
 def column(df, name, dev):
-    return torch.from_numpy(np.array(df[name].tolist()).astype(np.float32)).to(dev)
+    return torch.from_numpy(hostlib.column_matrix(df, name)).to(dev)
 
 
 def vae_block(kind, df, sites, args, n_classes, dev):
     """the reconstructed modality of the frame's samples from the directional model, as reconstruct.py computes it; None without a model"""
-    import types
-    import reconstruct as R
     direction = SAMPLE_TYPES[kind]
-    model = R.load_model(direction, args, n_classes, dev)
+    model = hostlib.load_directional(direction, getattr(args, f"checkpoint_{direction}"), args.checkpoint_dir,
+                                     (args.input_dim_a, args.input_dim_b, n_classes, args.latent_dim), args.precision, args.seed, args.synthetic, dev)
     if model is None:
         return None
-    run = types.SimpleNamespace(seed=args.seed, draws=1, batch_size=args.batch_size)
-    x = np.array(df[ORIGINAL[kind]].tolist()).astype(np.float32)
-    if kind == "RNA-only":
-        mean, _ = R.run_batches(model, np.log1p(x), sites, run, "given", dev)
-    else:
-        mean, _ = R.run_batches(model, x, None, run, "none", dev)
+    x = hostlib.column_matrix(df, ORIGINAL[kind])
+    x, sites, how = (np.log1p(x), sites, "given") if kind == "RNA-only" else (x, None, "none")
+    mean, _ = Reconstructor(model).reconstruct_batched(x, sites, draws=1, sites=how, batch_size=args.batch_size, seed=args.seed)
     return torch.from_numpy(mean).to(dev)
 
 
@@ -142,8 +113,7 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.neighbors < 1:
         raise SystemExit("--neighbors must be at least 1")
-    if not torch.cuda.is_available():
-        raise SystemExit("cluster_unmatched.py needs an MI355X: the product path has no CPU fallback")
+    hostlib.require_device("cluster_unmatched.py")
     from mmvae import unmatched as U
     dev = torch.device("cuda", 0)
     if args.synthetic:

@@ -20,8 +20,9 @@ if HERE not in sys.path:
 
 import torch  # noqa: E402
 
-import trainer  # noqa: E402
+import hostlib  # noqa: E402
 from mmvae import crossval  # noqa: E402
+from mmvae.data import load_matched  # noqa: E402
 from src.config import Config  # noqa: E402
 
 NO_AE = "the AE rows of the reference are not produced, because the project has no AE models"
@@ -35,14 +36,9 @@ def build_parser():
     ap.add_argument("--neighbors", type=int, nargs="+", default=[5, 10], help="k values of the kNN")
     ap.add_argument("--epochs", type=int, default=200, help="most VAE epochs per fold (early stopping may end sooner)")
     ap.add_argument("--batch-size", type=int, default=32)
-    ap.add_argument("--data", default=None, help="processed_data.pkl produced by the reference's prepare scripts (default: synthetic)")
-    ap.add_argument("--samples", type=int, default=262144, help="synthetic dataset size")
-    ap.add_argument("--input-dim-a", type=int, default=int(os.getenv("INPUT_DIM_A", 782)))
-    ap.add_argument("--input-dim-b", type=int, default=int(os.getenv("INPUT_DIM_B", 572)))
-    ap.add_argument("--n-sites", type=int, default=24)
-    ap.add_argument("--latent-dim", type=int, default=int(os.getenv("LATENT_DIM", Config.LATENT_DIM)))
-    ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32"])
-    ap.add_argument("--input-dtype", default="fp32", choices=["fp32", "bf16"], help="storage of the device-resident RNA / DNA matrices")
+    hostlib.add_dataset_args(ap)
+    hostlib.add_model_args(ap, n_sites=True)
+    hostlib.add_precision_args(ap)
     ap.add_argument("--seed", type=int, default=Config.RANDOM_SEED, help="folds, subset, VAE initialisation, noise and batch order")
     ap.add_argument("--models", nargs="+", default=["mean", "knn", "vae"], help="any of: mean knn vae")
     ap.add_argument("--knn-by-site", action="store_true", help="with knn: add the site-conditioned kNN under the same folds")
@@ -94,17 +90,10 @@ def run(argv=None):
         raise SystemExit("--knn-by-site needs knn among --models")
     if args.folds < 2 or not 0.0 < args.subset <= 1.0 or min(args.neighbors) < 1 or args.epochs < 1 or args.batch_size < 1:
         raise SystemExit("--folds must be at least 2, --subset in (0, 1], --neighbors, --epochs and --batch-size at least 1")
-    if not torch.cuda.is_available():
-        raise SystemExit("cross_validate.py needs an MI355X: the product path has no CPU fallback")
+    hostlib.require_device("cross_validate.py")
     dev = torch.device("cuda", 0)
-    if args.data:
-        tpm, beta_v, site = trainer.load_pickled_dataset(args.data)
-        args.input_dim_a, args.input_dim_b, args.n_sites = tpm.shape[1], beta_v.shape[1], int(site.max()) + 1
-    else:
-        tpm, beta_v, site = trainer.synthetic_dataset(args.samples, args.input_dim_a, args.input_dim_b, args.n_sites, Config.RANDOM_SEED)
-    lo, hi = int(site.min()), int(site.max())
-    if lo < 0 or hi >= args.n_sites:
-        raise SystemExit(f"site labels must lie in [0, {args.n_sites}); found [{lo}, {hi}]")
+    tpm, beta_v, site, (args.input_dim_a, args.input_dim_b, args.n_sites) = load_matched(
+        args.data, args.samples, args.input_dim_a, args.input_dim_b, args.n_sites, Config.RANDOM_SEED)
     if args.subset < 1.0:
         rows = torch.from_numpy(crossval.subset_rows(tpm.shape[0], args.subset, args.seed))
         tpm, beta_v, site = tpm[rows], beta_v[rows], site[rows]

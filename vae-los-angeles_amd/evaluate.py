@@ -49,27 +49,25 @@ if HERE not in sys.path:
 
 import torch  # noqa: E402
 
-from mmvae import to_bf16_rows  # noqa: E402
+import hostlib  # noqa: E402
+from mmvae import clustering, to_bf16_rows  # noqa: E402
 from mmvae._lib import PCA_MAXK, SIL_MAXC, WCE_MAXC  # noqa: E402
+from mmvae.clustering import CLUSTERING_COLUMNS, NH_K, PCA_COLUMNS, TSNE_COLUMNS, TSNE_PCA_K, tsne_embedding  # noqa: E402,F401  (re-exported)
+from mmvae.data import load_matched, split_indices  # noqa: E402
 from mmvae.knn import GRID as TUNE_GRID  # noqa: E402  (the reference's 16-point grid, run_comparison.py:63-67)
 from mmvae.metrics import ImputationMetrics  # noqa: E402
 from src.config import Config  # noqa: E402
-from trainer import KINDS, load_pickled_dataset, make_model, split_indices, synthetic_dataset  # noqa: E402
+from src.models import KINDS, make_model  # noqa: E402
 
 COLUMNS = ("MAE", "MSE", "RMSE", "R2", "MeanR2", "CosineSimilarity", "PearsonMean", "PearsonStd", "PearsonValid")
 
 
 def build_parser(kind):
     ap = argparse.ArgumentParser(description=f"{KINDS[kind]['title']} imputation metrics on MI355X")
-    ap.add_argument("--data", default=None, help="processed_data.pkl produced by the reference's prepare scripts (default: synthetic)")
-    ap.add_argument("--samples", type=int, default=262144, help="synthetic dataset size")
-    ap.add_argument("--input-dim-a", type=int, default=int(os.getenv("INPUT_DIM_A", 782)))
-    ap.add_argument("--input-dim-b", type=int, default=int(os.getenv("INPUT_DIM_B", 572)))
-    ap.add_argument("--n-sites", type=int, default=24)
-    ap.add_argument("--latent-dim", type=int, default=int(os.getenv("LATENT_DIM", Config.LATENT_DIM)))
+    hostlib.add_dataset_args(ap)
+    hostlib.add_model_args(ap, n_sites=True)
     ap.add_argument("--batch-size", type=int, default=4096)
-    ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32"])
-    ap.add_argument("--input-dtype", default="fp32", choices=["fp32", "bf16"], help="storage of the device-resident RNA / DNA matrices")
+    hostlib.add_precision_args(ap)
     ap.add_argument("--checkpoint", default=None, help="state_dict as the trainers save it (default: the run named by latest_<tag>_run_id.txt)")
     ap.add_argument("--checkpoint-dir", default=Config.CHECKPOINT_DIR)
     ap.add_argument("--seed", type=int, default=Config.RANDOM_SEED, help="Philox stream of eps")
@@ -139,13 +137,6 @@ def print_table(rows):
               + "".join(f"{r[c]:>17d}" if c == "PearsonValid" else f"{r[c]:>17.6f}" for c in COLUMNS))
 
 
-CLUSTERING_COLUMNS = ("Silhouette", "NeighborhoodHit")
-PCA_COLUMNS = ("PCASilhouette", "PCANeighborhoodHit", "PCAExplained")
-TSNE_COLUMNS = ("TSNESilhouette", "TSNENeighborhoodHit")
-TSNE_PCA_K = 50                                              # the reference reduces to 50 components in front of t-SNE
-NH_K = 5
-
-
 def print_clustering_table(rows):
     cols = CLUSTERING_COLUMNS + (PCA_COLUMNS if rows and PCA_COLUMNS[0] in rows[0] else ()) \
         + (TSNE_COLUMNS if rows and TSNE_COLUMNS[0] in rows[0] else ())
@@ -156,44 +147,26 @@ def print_clustering_table(rows):
         print(f"{r['Features']:<16}{r['Model']:<16}" + "".join(f"{r[c]:>{max(17, len(c) + 2)}.6f}" for c in cols))
 
 
-def tsne_embedding(z, perplexity, iters, seed):
-    """The reference's t-SNE of a standardised matrix: PCA(50) first when it has more than 50 columns, perplexity capped at rows - 1."""
-    from mmvae import clustering
-    if z.shape[1] > TSNE_PCA_K:
-        z = clustering.PCA(TSNE_PCA_K).fit_transform(z)
-    return clustering.TSNE(2, perplexity=min(perplexity, z.shape[0] - 1), max_iter=iters, random_state=seed).fit_transform(z)
-
-
 def clustering_table(entries, va, dims, B, pca_k=0, tsne=None):
     """[(features, model name, target, fill)] -> table rows.  fill(a, b, s) gives the imputed target modality of that batch, or is None
     for the true features.  ONE (rows, A + D) fp32 matrix is filled batch by batch, standardised, judged and reused.  pca_k > 0: the
     same two numbers on the standardised matrix's projection onto its first pca_k principal components as well.  tsne = (perplexity,
     iterations, seed): and on its t-SNE embedding."""
-    from mmvae import clustering
     n_val, labels = va[0].shape[0], va[2]
     n_labels = int(torch.unique(labels).numel())
-    if not 2 <= n_labels <= min(n_val - 1, SIL_MAXC):
+    if not clustering.can_judge(n_labels, n_val):
         print(f"clustering table skipped: {n_labels} distinct sites among {n_val} validation rows "
               f"(need 2 .. min(rows - 1, {SIL_MAXC}))")
         return []
     feats = torch.empty(n_val, dims["a"] + dims["b"], dtype=torch.float32, device=labels.device)
     part = {"a": feats[:, :dims["a"]], "b": feats[:, dims["a"]:]}
     rows = []
-
-    def judged(y):
-        return clustering.silhouette_score(y, labels), clustering.neighborhood_hit(y, labels, k=NH_K)
-
     for features, model_name, tgt, fill in entries:
         for i, a, b, s in batches(va, B):
             for m, true in (("a", a), ("b", b)):
                 part[m][i:i + B].copy_(fill(a, b, s) if m == tgt else true)
         z = clustering.standardize(feats)
-        rows.append({"Features": features, "Model": model_name, **dict(zip(CLUSTERING_COLUMNS, judged(z)))})
-        if pca_k > 0:
-            pca = clustering.PCA(pca_k)
-            rows[-1].update(zip(PCA_COLUMNS, judged(pca.fit_transform(z)) + (float(pca.explained_variance_ratio_.sum()),)))
-        if tsne is not None:
-            rows[-1].update(zip(TSNE_COLUMNS, judged(tsne_embedding(z, *tsne))))
+        rows.append({"Features": features, "Model": model_name, **clustering.judge_matrix(z, labels, pca_k=pca_k, tsne=tsne)})
         del z
     return rows
 
@@ -282,15 +255,8 @@ def check_args(args):
 def load_split(args, dev):
     """((tpm, beta, site) on the host, training indices, the validation split on the device as the model reads it, the training column
     means) of --data or of the synthetic set.  --data sets the dims and the site count of `args`."""
-    if args.data:
-        tpm, beta_v, site = load_pickled_dataset(args.data)
-        args.input_dim_a, args.input_dim_b = tpm.shape[1], beta_v.shape[1]
-        args.n_sites = int(site.max()) + 1
-    else:
-        tpm, beta_v, site = synthetic_dataset(args.samples, args.input_dim_a, args.input_dim_b, args.n_sites, Config.RANDOM_SEED)
-    lo_, hi_ = int(site.min()), int(site.max())
-    if lo_ < 0 or hi_ >= args.n_sites:                       # the trainer's check: the site encoder's Embedding has no row for them
-        raise SystemExit(f"site labels must lie in [0, {args.n_sites}); found [{lo_}, {hi_}]")
+    tpm, beta_v, site, (args.input_dim_a, args.input_dim_b, args.n_sites) = load_matched(
+        args.data, args.samples, args.input_dim_a, args.input_dim_b, args.n_sites, Config.RANDOM_SEED)
     val_idx, train_idx = split_indices(tpm.shape[0])
     if val_idx.numel() == 0:
         raise SystemExit(f"{tpm.shape[0]} samples leave no validation rows")
@@ -306,24 +272,18 @@ def load_split(args, dev):
 
 def load_model(kind, args, dev):
     """(the model of --checkpoint, or of the run the trainer named last, in eval mode at --precision; the checkpoint's path)"""
-    tag, title = KINDS[kind]["tag"], KINDS[kind]["title"]
-    path = args.checkpoint
+    path, cause = hostlib.resolve_checkpoint(kind, args.checkpoint, args.checkpoint_dir)
     if path is None:
-        id_file = f"latest_{tag}_run_id.txt"
-        if not os.path.exists(id_file):
-            raise SystemExit(f"no --checkpoint given and {id_file} (written by the trainer) is not here")
-        with open(id_file) as f:
-            path = os.path.join(args.checkpoint_dir, f"best_{tag}_{f.read().strip()}.pt")
-    if not os.path.exists(path):
-        raise SystemExit(f"checkpoint {path} not found")
-    model = make_model(kind, args)
+        raise SystemExit(f"no --checkpoint given and {cause[1]} (written by the trainer) is not here" if cause[0] == hostlib.NO_RUN_ID
+                         else f"checkpoint {cause[1]} not found")
+    model = make_model(kind, args.input_dim_a, args.input_dim_b, args.n_sites, args.latent_dim)
     state = torch.load(path, map_location="cpu")
     own = model.state_dict()
     bad = [f"{k}: checkpoint {tuple(state[k].shape)}, model {tuple(v.shape)}" for k, v in own.items()
            if k in state and tuple(state[k].shape) != tuple(v.shape)]
     missing = [k for k in own if k not in state]
     if bad or missing:
-        raise SystemExit(f"{path} is not a {title} of RNA {args.input_dim_a} / DNA {args.input_dim_b} / {args.n_sites} sites / latent "
+        raise SystemExit(f"{path} is not a {KINDS[kind]['title']} of RNA {args.input_dim_a} / DNA {args.input_dim_b} / {args.n_sites} sites / latent "
                          f"{args.latent_dim}: " + "; ".join(bad[:4] + [f"missing {k}" for k in missing[:4]]))
     model.load_state_dict(state)
     return model.to(dev).set_precision(args.precision).eval(), path
@@ -418,8 +378,7 @@ def _dump(obj, path):
 def run(kind, argv=None, return_clustering=False):
     args = build_parser(kind).parse_args(argv)
     check_args(args)
-    if not torch.cuda.is_available():
-        raise SystemExit("evaluate.py needs an MI355X: the product path has no CPU fallback")
+    hostlib.require_device("evaluate.py")
     dev = torch.device("cuda", torch.cuda.current_device())
     host, train_idx, va, means = load_split(args, dev)
     model, path = load_model(kind, args, dev)

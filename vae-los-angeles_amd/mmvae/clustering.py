@@ -20,7 +20,14 @@ from .knn import neighborhood_hit  # noqa: F401  (neighborhood_hit: re-exported)
 from .pca import PCA  # noqa: F401  (re-exported: the table's PCA columns)
 from .tsne import TSNE  # noqa: F401  (re-exported: the table's t-SNE columns)
 
-__all__ = ["silhouette_samples", "silhouette_score", "standardize", "StandardScaler", "neighborhood_hit", "PCA", "TSNE"]
+__all__ = ["silhouette_samples", "silhouette_score", "standardize", "StandardScaler", "neighborhood_hit", "PCA", "TSNE", "judge_matrix",
+           "can_judge", "tsne_embedding", "CLUSTERING_COLUMNS", "PCA_COLUMNS", "TSNE_COLUMNS", "TSNE_PCA_K", "NH_K"]
+
+CLUSTERING_COLUMNS = ("Silhouette", "NeighborhoodHit")
+PCA_COLUMNS = ("PCASilhouette", "PCANeighborhoodHit", "PCAExplained")
+TSNE_COLUMNS = ("TSNESilhouette", "TSNENeighborhoodHit")
+TSNE_PCA_K = 50                                              # the reference reduces to 50 components in front of t-SNE
+NH_K = 5
 
 
 def _encode(labels, N, device):
@@ -99,3 +106,36 @@ class StandardScaler:
 
     def fit_transform(self, parts):
         return self.fit(parts).transform(parts)
+
+
+def tsne_embedding(z, perplexity, iters, seed):
+    """The reference's t-SNE of a standardised matrix: PCA(50) first when it has more than 50 columns, perplexity capped at rows - 1."""
+    if z.shape[1] > TSNE_PCA_K:
+        z = PCA(TSNE_PCA_K).fit_transform(z)
+    return TSNE(2, perplexity=min(perplexity, z.shape[0] - 1), max_iter=iters, random_state=seed).fit_transform(z)
+
+
+def can_judge(n_labels, rows):                              # the silhouette's label-count guard
+    return 2 <= n_labels <= min(rows - 1, L.SIL_MAXC)
+
+
+def judge_matrix(z, labels, *, pca_k=0, tsne=None, k=NH_K, embeddings=None):
+    """One table row of a standardised matrix z, computed in column order: silhouette and neighbourhood hit (k) on z; pca_k > 0: on its
+    first pca_k principal components, with their explained-variance share; tsne = (perplexity, iterations, seed): on tsne_embedding(z).
+    embeddings: a dict that receives "pca" / "tsne" (host arrays).  labels=None: nothing is judged, z is only embedded."""
+    def judged(y):
+        return () if labels is None else (silhouette_score(y, labels), neighborhood_hit(y, labels, k=k))
+
+    row = dict(zip(CLUSTERING_COLUMNS, judged(z)))
+    if pca_k > 0:
+        pca = PCA(pca_k)
+        y = pca.fit_transform(z)
+        row.update(zip(PCA_COLUMNS, judged(y) + (float(pca.explained_variance_ratio_.sum()),)))
+        if embeddings is not None:
+            embeddings["pca"] = y.cpu().numpy()
+    if tsne is not None:
+        y = tsne_embedding(z, *tsne)
+        row.update(zip(TSNE_COLUMNS, judged(y)))
+        if embeddings is not None:
+            embeddings["tsne"] = y.cpu().numpy()
+    return row

@@ -14,7 +14,6 @@ The host part (fold / subset / inner-split index sets, the paired t-test, the co
 """
 import math
 import time
-from types import SimpleNamespace
 
 import numpy as np
 
@@ -225,9 +224,8 @@ def fit_vae(kind, A, B, S, dims, *, epochs, batch_size, seed=42, fold=0, precisi
     (BestState).  The model's initialisation and its noise stream are functions of (seed, fold): the Philox offset of the device is
     reset.  dims: (input_dim_a, input_dim_b, n_sites, latent_dim).  val_loss_fn(model, epoch) replaces the validation pass (tests).
     Returns (model in eval mode, BestState)."""
-    import trainer
-    args = SimpleNamespace(input_dim_a=dims[0], input_dim_b=dims[1], n_sites=dims[2], latent_dim=dims[3])
-    return _fit(kind, lambda: trainer.make_model(kind, args), lambda model, a, b, s, beta: trainer.forward_loss(kind, model, a, b, s, beta, None),
+    from src.models import forward_loss, make_model
+    return _fit(kind, lambda: make_model(kind, *dims), lambda model, a, b, s, beta: forward_loss(kind, model, a, b, s, beta, None),
                 True, A, B, S, epochs=epochs, batch_size=batch_size, seed=seed, fold=fold, precision=precision, eager=eager, val_loss_fn=val_loss_fn)
 
 

@@ -16,6 +16,7 @@ import torch
 from . import _lib as L
 from . import ops
 from .clustering import standardize
+from .data import balanced_class_weights
 
 BATCH_SIZE = 32                 # Config.BATCH_SIZE of the reference
 LN_EPS = 1e-5                   # nn.LayerNorm's default
@@ -498,7 +499,6 @@ def cross_validate(features, labels, names, n_folds=5, *, epochs=100, seed=42, h
     SiteClassifier is trained per fold with the fold's balanced class weights, and the folds' classification reports are aggregated."""
     if not isinstance(features, torch.Tensor) or not features.is_cuda or not isinstance(labels, torch.Tensor) or not labels.is_cuda:
         raise RuntimeError("cross_validate: features and labels must be CUDA/HIP tensors; there is no CPU fallback")
-    from trainer import balanced_class_weights
     n_classes = len(names)
     z = standardize(features.float())
     labels = labels.to(torch.int64).contiguous()

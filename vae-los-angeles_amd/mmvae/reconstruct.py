@@ -6,6 +6,7 @@ DNA-only samples, `site=None`; it names "iterate through all possible sites and 
 Here every sample owns G = draws (x sites) consecutive rows of the decoder's input; the decoder's last Linear reduces each
 group on chip (ops.gemm_nt_group_moments), so the B G x N reconstructions are never stored.
 """
+import numpy as np
 import torch
 
 from . import _lib as L_, engine, ops
@@ -71,6 +72,23 @@ class Reconstructor:
                 return self._grouped(x, site, int(draws), sites, G, return_std)
         finally:
             self.model.train(was_training)
+
+    def reconstruct_batched(self, x, site, *, draws, sites, batch_size, seed):
+        """reconstruct() over the host float32 rows x (site: host int64 or None) in batches, from the Philox position (seed, offset 0) set
+        ONCE before the first batch -> (mean, std or None for a group of one) as host float32 arrays"""
+        dev = next(self.model.parameters()).device
+        torch.manual_seed(seed)
+        engine.GLOBAL_NOISE.load_state_dict({"offset": 0}, dev)
+        want_std = self.group_size(draws, sites) > 1
+        means, stds = [], []
+        for i in range(0, x.shape[0], batch_size):
+            xb = torch.from_numpy(x[i:i + batch_size]).to(dev)
+            sb = torch.from_numpy(site[i:i + batch_size]).to(dev) if site is not None else None
+            m, s = self.reconstruct(xb, sb, draws=draws, sites=sites, return_std=want_std)
+            means.append(m.cpu().numpy())
+            if want_std:
+                stds.append(s.cpu().numpy())
+        return np.concatenate(means), (np.concatenate(stds) if want_std else None)
 
     def _grouped(self, x, site, draws, sites, G, return_std):
         g, enc, dec, prec = self.graph, self.enc, self.dec, self.model._prec()

@@ -25,7 +25,6 @@ IMPUTERS = METHODS[:3]
 DIRECTIONS = ("rna2dna", "dna2rna")
 SAMPLE_TYPES = {"RNA-only": "rna2dna", "DNA-only": "dna2rna"}
 SCALINGS = ("consistent", "reference")
-NH_K = 5
 
 __all__ = ["impute", "query_features", "feature_parts", "judge", "log1p_host", "METHODS", "SCALINGS", "SAMPLE_TYPES"]
 
@@ -79,13 +78,12 @@ def feature_parts(sample_type, original, imputed, scaling="consistent", method="
     return [original, imputed]
 
 
-def judge(parts, labels, pca=True, tsne=None, k=NH_K, embeddings=None):
+def judge(parts, labels, pca=True, tsne=None, k=clustering.NH_K, embeddings=None):
     """One table row of the feature matrix whose column blocks are `parts`, or None with a printed message where the labels allow no
     silhouette.  Z = StandardScaler().fit_transform(parts); silhouette and neighbourhood hit (k) on Z; with pca on PCA(2) of Z, with
     the explained-variance sum; with tsne = (iterations, seed) on the t-SNE of Z by perform_dimensionality_reduction's rule (PCA(50) first
     only above 50 columns, perplexity min(30, rows - 1)).  embeddings: a dict that receives "pca" / "tsne" (host arrays).  labels=None
     (a DNA-only frame without primary_site): the samples are embedded, nothing is judged, None is returned."""
-    from evaluate import CLUSTERING_COLUMNS, PCA_COLUMNS, TSNE_COLUMNS, tsne_embedding
     parts = (parts,) if isinstance(parts, torch.Tensor) else tuple(parts)
     rows = next((t.shape[0] for t in parts if isinstance(t, torch.Tensor) and t.dim() == 2), 0)
     if labels is not None:
@@ -93,7 +91,7 @@ def judge(parts, labels, pca=True, tsne=None, k=NH_K, embeddings=None):
         if labels.dim() != 1 or labels.shape[0] != rows:
             raise ValueError(f"labels must be ({rows},)")
         n_labels = int(torch.unique(labels).numel())
-        if not 2 <= n_labels <= L.SIL_MAXC or n_labels >= rows:
+        if not clustering.can_judge(n_labels, rows):
             print(f"  not judged: {n_labels} distinct label(s) among {rows} rows (need 2 .. min(rows - 1, {L.SIL_MAXC}))")
             return None
         if rows < k + 1:
@@ -101,21 +99,7 @@ def judge(parts, labels, pca=True, tsne=None, k=NH_K, embeddings=None):
             return None
     z = clustering.StandardScaler().fit_transform(parts)
     labels = None if labels is None else labels.to(z.device)
-
-    def judged(y):
-        return () if labels is None else (clustering.silhouette_score(y, labels), clustering.neighborhood_hit(y, labels, k=k))
-
-    row = dict(zip(CLUSTERING_COLUMNS, judged(z)))
-    if pca and (labels is not None or embeddings is not None):
-        p = clustering.PCA(min(2, z.shape[1]))
-        y = p.fit_transform(z)
-        row.update(zip(PCA_COLUMNS, judged(y) + (float(p.explained_variance_ratio_.sum()),)))
-        if embeddings is not None:
-            embeddings["pca"] = y.cpu().numpy()
-    if tsne is not None and rows >= 2 and (labels is not None or embeddings is not None):
-        iters, seed = tsne
-        y = tsne_embedding(z, 30, iters, seed)
-        row.update(zip(TSNE_COLUMNS, judged(y)))
-        if embeddings is not None:
-            embeddings["tsne"] = y.cpu().numpy()
+    wanted = labels is not None or embeddings is not None          # without labels the projections only serve `embeddings`
+    row = clustering.judge_matrix(z, labels, pca_k=min(2, z.shape[1]) if pca and wanted else 0,
+                                  tsne=(30, *tsne) if tsne is not None and rows >= 2 and wanted else None, k=k, embeddings=embeddings)
     return row if labels is not None else None

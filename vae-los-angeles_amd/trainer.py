@@ -19,71 +19,26 @@ import os
 import time
 from datetime import datetime
 
-import numpy as np
 import torch
 import torch.distributed as dist
 
+import hostlib
 from mmvae import parallel, checkpoint
+from mmvae.data import balanced_class_weights, load_matched, load_pickled_dataset, split_indices, synthetic_dataset  # noqa: F401  (re-exported)
 from mmvae.graphs import GraphedTrainStep
 from mmvae.optim import FusedAdamW
 from src.config import Config
-
-KINDS = {
-    "multimodal": dict(tag="multivae", title="MultiModalVAE"),
-    "dna2rna": dict(tag="dna2rna", title="DNA2RNAVAE"),
-    "rna2dna": dict(tag="rna2dna", title="RNA2DNAVAE"),
-}
-
-
-def balanced_class_weights(site, n_sites):
-    """compute_class_weights of the reference (optimize_hyperparameters.py:33-44): sklearn's 'balanced' weights over the classes
-    PRESENT in the training labels, n / (k_present * count_c); classes that do not occur keep weight 1."""
-    counts = torch.bincount(site.reshape(-1), minlength=n_sites).double()
-    present = counts > 0
-    w = torch.ones(n_sites, dtype=torch.float64)
-    w[present] = site.numel() / (present.sum().double() * counts[present])
-    return w.float()
-
-
-def synthetic_dataset(n, a_dim, d_dim, n_sites, seed):
-    g = torch.Generator().manual_seed(seed)
-    tpm = torch.log1p(torch.exp(1.5 * torch.randn(n, a_dim, generator=g)))          # log1p(TPM)-like, >= 0 (prepare_data.py:123-125)
-    beta = torch.rand(n, d_dim, generator=g)                                          # methylation beta values in [0, 1]
-    site = torch.randint(0, n_sites, (n,), generator=g, dtype=torch.int64)
-    return tpm, beta, site
-
-
-def load_pickled_dataset(path):
-    """Same columns as the reference's processed_data.pkl (src/data/dataset.py:20-30)."""
-    import pandas as pd
-    df = pd.read_pickle(path)          # a file the USER produced with the reference's own scripts -- never one from the reference tree
-    tpm = torch.tensor(np.stack(df["tpm_unstranded"].values), dtype=torch.float32)
-    beta = torch.tensor(np.stack(df["beta_value"].values), dtype=torch.float32)
-    site = torch.tensor(df["primary_site_encoded"].values, dtype=torch.int64)
-    return tpm, beta, site
-
-
-def split_indices(n):
-    """(val_idx, train_idx) of n samples: the one validation split of the trainers and of evaluate.py."""
-    perm = torch.randperm(n, generator=torch.Generator().manual_seed(Config.RANDOM_SEED))       # train_test_split(random_state=42) stand-in
-    n_val = int(n * Config.TRAIN_TEST_SPLIT)
-    return perm[:n_val], perm[n_val:]
+from src.models import KINDS, forward_loss, make_model  # noqa: F401  (KINDS: re-exported)
 
 
 def build_parser(kind):
     ap = argparse.ArgumentParser(description=f"{KINDS[kind]['title']} trainer on MI355X")
-    ap.add_argument("--data", default=None, help="processed_data.pkl produced by the reference's prepare scripts (default: synthetic)")
-    ap.add_argument("--samples", type=int, default=262144, help="synthetic dataset size")
-    ap.add_argument("--input-dim-a", type=int, default=int(os.getenv("INPUT_DIM_A", 782)))      # env overrides as train_dna2rna.py:172-174
-    ap.add_argument("--input-dim-b", type=int, default=int(os.getenv("INPUT_DIM_B", 572)))
-    ap.add_argument("--n-sites", type=int, default=24)
-    ap.add_argument("--latent-dim", type=int, default=int(os.getenv("LATENT_DIM", Config.LATENT_DIM)))
+    hostlib.add_dataset_args(ap)
+    hostlib.add_model_args(ap, n_sites=True)
     ap.add_argument("--batch-size", type=int, default=4096, help="rows per GPU")
     ap.add_argument("--epochs", type=int, default=Config.NUM_EPOCHS)
-    ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32"])
-    ap.add_argument("--input-dtype", default="fp32", choices=["fp32", "bf16"],
-                    help="storage of the device-resident RNA / DNA matrices: bf16 converts them ONCE (mmvae.to_bf16_rows, padded bf16 rows); "
-                         "the first-layer GEMMs, their dW GEMMs and the reconstruction losses then read 2 bytes per element")
+    hostlib.add_precision_args(ap, input_dtype_help=hostlib.INPUT_DTYPE_HELP + ": bf16 converts them ONCE (mmvae.to_bf16_rows, padded bf16 "
+                               "rows); the first-layer GEMMs, their dW GEMMs and the reconstruction losses then read 2 bytes per element")
     ap.add_argument("--checkpoint-dir", default=Config.CHECKPOINT_DIR)
     ap.add_argument("--resume", default=None, help="training state written by --save-state (model + optimiser + scheduler + noise)")
     ap.add_argument("--save-state", default=None, help="write a resumable training state here after every epoch")
@@ -93,26 +48,6 @@ def build_parser(kind):
     ap.add_argument("--log-json", default=None, help="append one JSON object per epoch (steps, train/val loss, lr, early-stop counter) to "
                                                      "<path>.rank<r>: every rank writes its own file, so that a run can be checked for identical decisions")
     return ap
-
-
-def make_model(kind, args):
-    from src.models import MultiModalVAE, DNA2RNAVAE, RNA2DNAVAE
-    cls = {"multimodal": MultiModalVAE, "dna2rna": DNA2RNAVAE, "rna2dna": RNA2DNAVAE}[kind]
-    return cls(args.input_dim_a, args.input_dim_b, args.n_sites, args.latent_dim)
-
-
-def forward_loss(kind, model, a, b, s, beta, class_weights):
-    """One reference-shaped forward + loss; returns the total loss tensor."""
-    from src.utils import vae_loss
-    from src.utils.directional_losses import dna2rna_loss, rna2dna_loss
-    if kind == "multimodal":
-        ra, rb, rc, mu, lv = model(a=a, b=b, site=s)
-        return vae_loss(ra, a, rb, b, rc, s, mu, lv, beta=beta, gamma=Config.GAMMA, class_weights=class_weights)[0]
-    if kind == "dna2rna":
-        rec, mu, lv = model(dna=b, site=s)
-        return dna2rna_loss(rec, a, mu, lv, beta=beta)[0]
-    rec, mu, lv = model(rna=a, site=s)
-    return rna2dna_loss(rec, b, mu, lv, beta=beta)[0]
 
 
 def run(kind, argv=None):
@@ -136,18 +71,8 @@ def run(kind, argv=None):
         else:
             dist.init_process_group(args.backend)
 
-    if args.data:
-        tpm, beta_v, site = load_pickled_dataset(args.data)
-        args.input_dim_a, args.input_dim_b = tpm.shape[1], beta_v.shape[1]
-        args.n_sites = int(site.max()) + 1
-    else:
-        tpm, beta_v, site = synthetic_dataset(args.samples, args.input_dim_a, args.input_dim_b, args.n_sites, Config.RANDOM_SEED)
-    # class indices are validated ONCE, on the host, before any rank trains: inside the loop a bad label only shows up in the loss
-    # read of the rank that holds it (read_losses raises there) and the other ranks would wait in the all-reduce.  -100 is
-    # F.cross_entropy's ignore_index (losses.py:39): legal for the loss, but the site encoder's Embedding has no row for it.
-    lo_, hi_ = int(site.min()), int(site.max())
-    if lo_ < 0 or hi_ >= args.n_sites:
-        raise SystemExit(f"site labels must lie in [0, {args.n_sites}); found [{lo_}, {hi_}]")
+    tpm, beta_v, site, (args.input_dim_a, args.input_dim_b, args.n_sites) = load_matched(
+        args.data, args.samples, args.input_dim_a, args.input_dim_b, args.n_sites, Config.RANDOM_SEED)
     n = tpm.shape[0]
     val_idx, train_idx = split_indices(n)
     lo, hi = parallel.shard_rows(train_idx.numel(), rank, world, equal=True)   # equal shards: every rank runs the same number of steps
@@ -165,7 +90,7 @@ def run(kind, argv=None):
         raise SystemExit(f"batch size {B} exceeds the {n_train} training rows of this rank")
 
     torch.manual_seed(Config.RANDOM_SEED)
-    model = make_model(kind, args).to(dev).set_precision(args.precision)
+    model = make_model(kind, args.input_dim_a, args.input_dim_b, args.n_sites, args.latent_dim).to(dev).set_precision(args.precision)
     if world > 1:
         parallel.broadcast_parameters(model)
     optimizer = FusedAdamW(model.parameters(), lr=Config.LEARNING_RATE, weight_decay=Config.WEIGHT_DECAY)
